@@ -23,8 +23,14 @@ N = 16384, fp32, dense D1 input (floydwarshall_amd/synth.py), matrices resident 
   roofline  = per-k kernel `relax_k` against HBM: algorithmic bytes per launch
               (s*N^2 + s*U/N + 2*s*N) / average launch duration measured
               live with HIP events on the launch stream over the timed region
+
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes
+what the last timed step computed (dump_outputs).  Everything else runs only with --full, after the
+timed steps, and adds keys to the same line:
   cpu_baseline = the oracle's multithreaded dense loop (a C restatement of the reference loop --
               the Haskell reference cannot be built here) on a bounded k-slice of the same matrix
+  the extra legs (other engines, f64, serpentine off, event-timed solves, the reference's sizes)
+              and `check`, the result's digests against the committed whole-oracle digests
 
 The single-process forms run WITHOUT torch: device buffers, the stream and the events come from the
 HIP runtime directly (floydwarshall_amd/hip.py), so the process holds one HIP runtime -- the one
@@ -51,6 +57,8 @@ SEGMENTS = 16
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 INFINITY_CACHE_BYTES = 256 << 20
 PMC_PROFILE = os.path.join("profiles", "r04_pmc_traffic.json")
+DUMP_BUDGET_BYTES = 64 * 10**6      # --dump-outputs: all .npy files of one run together, headers included
+DUMP_SEED = 20240
 
 
 class Watchdog:
@@ -193,7 +201,20 @@ def parse_args():
     ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 4, 5],
                     help="preset for one of BASELINE.json's configs (2: N=1024 f64 per-k; 3: N=8192 f32 "
                          "fused; 4: the default headline; 5: N=32768 f32 + next-hop matrix, fused)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the extra legs "
+                         "(other engines, precisions and sizes, serpentine off, event-timed solves, result checks "
+                         "against the committed digests) and the CPU baseline; without it a run only sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of rows where the whole would exceed %d MB)"
+                         % (DUMP_BUDGET_BYTES // 10**6))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = True
     if args.config == 2:
         args.n, args.dtype, args.engine = 1024, "f64", "perk"
     elif args.config == 3:
@@ -299,6 +320,23 @@ def digest(a):
             for off in range(0, len(buf), 1 << 26):
                 c = zlib.crc32(buf[off:off + (1 << 26)], c)
         return "crc32:%08x" % c
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: `arrays` = [(name, n x n host array or None)], what a caller of the timed path receives,
+    written as DIR/<name>.npy in float64 (f64 rates) or float32 (f32 rates; int32 next-hop indices are < 2^24, so
+    exact).  Where the arrays together would exceed DUMP_BUDGET_BYTES, the same rows of each are written: a sorted
+    sample drawn with DUMP_SEED, so that two runs with the same arguments write the same entries."""
+    arrays = [(name, a, np.float64 if a.dtype == np.float64 else np.float32) for name, a in arrays if a is not None]
+    n = arrays[0][1].shape[0]
+    row_bytes = sum(np.dtype(t).itemsize * a.shape[1] for _, a, t in arrays)
+    budget = DUMP_BUDGET_BYTES - 1024 * len(arrays)          # (room for the .npy headers)
+    rows = None
+    if row_bytes * n > budget:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=budget // row_bytes, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a, t in arrays:
+        np.save(os.path.join(outdir, name + ".npy"), (a if rows is None else a[rows]).astype(t))
 
 
 def alg_bytes_per_launch(n, es, u_per_launch, with_next):
@@ -416,6 +454,11 @@ def run_single(args):
         step(timed=True)
     hip.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        got = handle.download()[:2] if handle is not None else \
+            (rate.numpy(stream), nxt.numpy(stream) if nxt is not None else None)
+        dump_outputs(args.dump_outputs, [("rate", got[0]), ("next", got[1])])
+        del got
 
     out = {
         "metric": "edge-relaxations/sec (N^3/t), N=%d %s" % (n, "fp32" if es == 4 else "fp64"),
@@ -861,6 +904,12 @@ def run_multi(args):
         dog.disarm()
     hip.synchronize(devs)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dog.arm("dump the outputs")
+        got = h.download()
+        dump_outputs(args.dump_outputs, [("rate", got[0]), ("next", got[1])])
+        del got
+        dog.disarm()
 
     bounds = [n * p // world for p in range(world + 1)]
     slab_bytes = es * n * max(bounds[p + 1] - bounds[p] for p in range(world))
@@ -1074,6 +1123,27 @@ def run_dist(args, world, rank, local_rank):
         dist.barrier()
         torch.cuda.synchronize()
 
+    def local_result():
+        """This rank's slab of the last solve, as host tensors (rates, next-hops or None)."""
+        if ph is not None:
+            got = ph.download()
+            return torch.from_numpy(got[0]), (torch.from_numpy(got[1]) if args.with_next else None)
+        return rate.cpu(), (nxt.cpu() if nxt is not None else None)
+
+    def gather_rows(t):
+        """Every rank's slab on rank 0 (device tensors over RCCL; host tensors under the gloo rehearsal), as a list
+        in row order; None on the other ranks."""
+        rows_max = max(bounds[p + 1] - bounds[p] for p in range(world))
+        buf = torch.zeros((rows_max, n), dtype=t.dtype)
+        buf[:r1 - r0] = t
+        if args.backend == "nccl":
+            buf = buf.to(dev)
+        parts = [torch.empty_like(buf) for _ in range(world)] if rank == 0 else None
+        dist.gather(buf, parts, dst=0)
+        if rank != 0:
+            return None
+        return [parts[p][:bounds[p + 1] - bounds[p]].cpu().numpy() for p in range(world)]
+
     for w in range(args.warmup):
         dog.arm("warm-up step %d" % (w + 1))
         step()
@@ -1092,6 +1162,16 @@ def run_dist(args, world, rank, local_rank):
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs:
+        dog.arm("dump the outputs (gather of the slabs on rank 0)")
+        mine, mine_next = local_result()
+        slabs = gather_rows(mine)
+        slabs_next = gather_rows(mine_next) if mine_next is not None else None
+        if rank == 0:
+            dump_outputs(args.dump_outputs, [("rate", np.concatenate(slabs)),
+                                             ("next", np.concatenate(slabs_next) if slabs_next is not None else None)])
+        del mine, mine_next, slabs, slabs_next
+        dog.disarm()
 
     def max_over_ranks(values):
         v = torch.tensor(values, dtype=torch.float64, device=dev)
@@ -1206,25 +1286,7 @@ def run_dist(args, world, rank, local_rank):
             dog.arm("result check (gather of the slabs on rank 0)")
             step()                                   # the timed engine's result again
             torch.cuda.synchronize()
-            if ph is not None:
-                got = ph.download()
-                mine, mine_next = torch.from_numpy(got[0]), (torch.from_numpy(got[1]) if args.with_next else None)
-                del got
-            else:
-                mine, mine_next = rate.cpu(), (nxt.cpu() if nxt is not None else None)
-            rows_max = max(bounds[p + 1] - bounds[p] for p in range(world))
-
-            def gather_rows(t):
-                buf = torch.zeros((rows_max, n), dtype=t.dtype)
-                buf[:r1 - r0] = t
-                if args.backend == "nccl":
-                    buf = buf.to(dev)
-                parts = [torch.empty_like(buf) for _ in range(world)] if rank == 0 else None
-                dist.gather(buf, parts, dst=0)
-                if rank != 0:
-                    return None
-                return [parts[p][:bounds[p + 1] - bounds[p]].cpu().numpy() for p in range(world)]
-
+            mine, mine_next = local_result()
             slabs = gather_rows(mine)
             slabs_next = gather_rows(mine_next) if mine_next is not None else None
             if rank == 0:

@@ -209,3 +209,51 @@ def test_digest_of_row_slabs_equals_the_digest_of_the_matrix():
     a = np.random.default_rng(5).random((37, 11)).astype(np.float32)
     assert bench.digest([a[:5], a[5:20], a[20:]]) == bench.digest(a)
     assert bench.digest([a[:5], a[5:20], a[20:36]]) != bench.digest(a)
+
+
+def test_a_plain_run_leaves_everything_but_the_timed_steps_to_full(monkeypatch):
+    """Without --full no extra leg and no CPU baseline runs; with it every leg runs as before, and the --no-*
+    switches still take legs out of a --full run."""
+    import bench
+
+    def parse(argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        return bench.parse_args()
+
+    legs = ("no_extras", "no_cpu_baseline", "no_fused_extra", "no_f64_extra")
+    a = parse(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.dump_outputs) == (4, 2, None) and not a.full
+    assert all(getattr(a, k) for k in legs)
+    a = parse(["--full"])
+    assert not any(getattr(a, k) for k in legs)
+    a = parse(["--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    assert a.no_cpu_baseline and not a.no_extras and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            parse(bad)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget_and_the_same_sample_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    n = 300
+    rate = (np.arange(n * n, dtype=np.float32) / 7).reshape(n, n)       # every row tells its index
+    nxt = np.tile(np.arange(n, dtype=np.int32), (n, 1)) - 1
+    bench.dump_outputs(str(tmp_path / "whole"), [("rate", rate), ("next", nxt), ("hops", None)])
+    assert sorted(os.listdir(tmp_path / "whole")) == ["next.npy", "rate.npy"]
+    got = np.load(tmp_path / "whole" / "next.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, nxt)
+    assert np.array_equal(np.load(tmp_path / "whole" / "rate.npy"), rate)
+    bench.dump_outputs(str(tmp_path / "f64"), [("rate", rate.astype(np.float64))])
+    assert np.load(tmp_path / "f64" / "rate.npy").dtype == np.float64
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 100000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), [("rate", rate), ("next", nxt)])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 100000
+    r, x = np.load(tmp_path / "a" / "rate.npy"), np.load(tmp_path / "a" / "next.npy")
+    rows = np.round(r[:, 0] * 7 / n).astype(np.int64)
+    assert len(rows) > 10 and np.all(np.diff(rows) > 0)                 # distinct rows, in order
+    assert np.array_equal(r, rate[rows]) and np.array_equal(x, nxt[rows].astype(np.float32))
+    for f in ("rate.npy", "next.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

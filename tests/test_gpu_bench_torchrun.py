@@ -10,6 +10,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,8 +33,8 @@ def _line(stdout):
 
 
 @pytest.mark.parametrize("with_next", [False, True])
-def test_torchrun_two_ranks_one_line_and_the_gathered_result(with_next):
-    common = ["--size", "768", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--step-timeout", "120"]
+def test_torchrun_two_ranks_one_line_and_the_gathered_result(with_next, tmp_path):
+    common = ["--size", "768", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--step-timeout", "120"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -43,7 +44,8 @@ def test_torchrun_two_ranks_one_line_and_the_gathered_result(with_next):
     one = _line(single.stdout)
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo"] + common +
+                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
+                          "--dump-outputs", str(tmp_path / "two")] + common +
                          (["--with-next"] if with_next else []),
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert two.returncode == 0, two.stderr[-3000:]
@@ -59,3 +61,15 @@ def test_torchrun_two_ranks_one_line_and_the_gathered_result(with_next):
     assert d["check"]["rate_digest"] == one["check"]["rate_digest"], (d["check"], one["check"])
     if with_next:
         assert d["check"]["next_digest"] == one["fused_engine_next"]["check"]["next_digest"]
+    # --dump-outputs: the slabs gathered on rank 0 are the arrays a plain single-GPU run writes
+    plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "768", "--steps", "1",
+                            "--dump-outputs", str(tmp_path / "one")] + (["--with-next"] if with_next else []),
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert plain.returncode == 0, plain.stderr[-2000:]
+    names = sorted(os.listdir(tmp_path / "one"))
+    assert names == (["next.npy", "rate.npy"] if with_next else ["rate.npy"])
+    assert sorted(os.listdir(tmp_path / "two")) == names
+    for name in names:
+        a, b = np.load(tmp_path / "one" / name), np.load(tmp_path / "two" / name)
+        assert a.dtype == b.dtype == np.float32 and a.shape == b.shape == (768, 768)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), name

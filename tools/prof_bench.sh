@@ -1,7 +1,9 @@
-# rocprofv3 kernel-trace summary of the default bench command (profiles/r01_bench_kernel_stats.csv)
+# rocprofv3 kernel-trace summary of the bench command with all its legs (profiles/r01_bench_kernel_stats.csv)
+# usage: tools/prof_bench.sh OUTPUT_DIR   (an absolute path: the profiler runs from /tmp)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out/prof_bench
-rocprofv3 --kernel-trace --stats -f csv -d $R/gpurun_out/prof_bench -o bench -- python3 $R/bench.py --no-cpu-baseline > $R/gpurun_out/prof_bench/bench_under_rocprof.json 2> $R/gpurun_out/prof_bench/err.log
-ls $R/gpurun_out/prof_bench
-tail -c 400 $R/gpurun_out/prof_bench/bench_under_rocprof.json
+OUT=${1:?usage: tools/prof_bench.sh OUTPUT_DIR}
+mkdir -p $OUT
+rocprofv3 --kernel-trace --stats -f csv -d $OUT -o bench -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/err.log
+ls $OUT
+tail -c 400 $OUT/bench_under_rocprof.json
