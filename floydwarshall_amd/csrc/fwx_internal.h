@@ -4,6 +4,7 @@
 #define FWX_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -416,6 +417,28 @@ int domain_bits(const T *rate, const int32_t *next, size_t count, int *d_flag, h
 }
 
 
+// Temporal-tail budget of the per-k engine (fwx::RelaxArgs::temporal_bytes): the bytes of a slab's last
+// rows that are loaded with the default cache policy in every launch; the rest of a larger slab is
+// streamed non-temporally (presumably not allocating in the 256 MiB Infinity Cache, so the tail stays
+// resident there).  Default from profiles/r05_tune_relax_policy.txt; FWX_PERK_TEMPORAL_MIB=<MiB> overrides it
+// (may be fractional; 0: the whole slab non-temporal, a huge value: all default policy), read on
+// every call.
+#define FWX_PERK_TEMPORAL_MIB_DEFAULT 256
+// Build switch for A/B runs (`python -m floydwarshall_amd.build --variant NAME -DFWX_XCD_SERPENTINE=0`): 0 =
+// the serpentine sweep reverses tile by tile even where the split applies.
+#ifndef FWX_XCD_SERPENTINE
+#define FWX_XCD_SERPENTINE 1
+#endif
+inline long long perk_temporal_bytes(size_t slab_bytes)
+{
+    double mib = FWX_PERK_TEMPORAL_MIB_DEFAULT;
+    if (const char *e = getenv("FWX_PERK_TEMPORAL_MIB"))
+        if (*e) mib = std::max(0.0, strtod(e, nullptr));
+    const double b = mib * (1 << 20);
+    if (!(b < (double)slab_bytes)) return -1;          // the slab fits (or NaN): all default policy
+    return (long long)b;
+}
+
 // One launch per pivot over a slab; pivot rows from `prow0 + (k-k_begin)*stride`.
 template <typename T>
 inline int relax_range(T *rate, int32_t *next, int32_t *hops, int rows, int n, int row0, const T *prow0,
@@ -428,12 +451,16 @@ inline int relax_range(T *rate, int32_t *next, int32_t *hops, int rows, int n, i
     a.rate = rate; a.next = next; a.hops = hops;
     a.rows = rows; a.n = n; a.row0 = row0; a.updates = d_updates; a.plog = plog;
     a.skip_lo = skip_lo; a.skip_hi = skip_hi;
+    a.temporal_bytes = perk_temporal_bytes((size_t)rows * n * sizeof(T));
+    // serpentine: reversed in groups of 8 (tiles keep their XCD) where the split applies -- the regime
+    // it was measured in (profiles/r05_tune_relax_policy.txt) -- tile by tile otherwise
+    const int rev = FWX_XCD_SERPENTINE && a.temporal_bytes >= 0 ? 2 : 1;
     for (int k = k_begin; k < k_end; ++k) {
         a.prow = prow0 + (int64_t)(k - k_begin) * stride;
         a.phops = phops0 ? phops0 + (int64_t)(k - k_begin) * stride : nullptr;
         a.pnext = pnext0 ? pnext0 + (int64_t)(k - k_begin) * stride : nullptr;
         a.k = k;
-        a.flip = serpentine ? (k & 1) : 0;
+        a.flip = serpentine ? rev * (k & 1) : 0;
         const hipError_t e = fwx::launch_relax<T>(a, s);
         if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;   // misaligned skip range
         FWX_HIP(e);

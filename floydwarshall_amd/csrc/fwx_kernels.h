@@ -38,7 +38,11 @@ template <typename T> struct RelaxArgs {
                                    // (next[i][k] < 0), then it is next[k][j].  nullptr: the caller
                                    // vouches that a winning product never has an empty ikPath (true
                                    // on the reference's domain, see fwx.h "Domain")
-    int rows, n, row0, k, flip;
+    int rows, n, row0, k;
+    int flip;                      // 0: tiles in order; 1: reversed; 2: reversed in groups of 8 (XCD kept)
+    long long temporal_bytes = -1; // the slab's last rows, this many bytes, are streamed with default-policy
+                                   // loads in every launch, all rows before them non-temporally; < 0: all
+                                   // default policy
     int skip_lo = 0, skip_hi = 0;  // slab rows [skip_lo, skip_hi) are left alone (multiples of 4):
                                    //   a look-ahead launch has already relaxed them
     unsigned long long *updates;   // FWX_UPDATE_SHARDS_K counters or nullptr

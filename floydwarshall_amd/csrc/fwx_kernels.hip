@@ -19,6 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
+#include <type_traits>
+
 #include "fwx_kernels.h"
 
 #pragma clang fp contract(off)
@@ -47,6 +51,16 @@ template <typename V, bool NT, typename T> __device__ __forceinline__ V load_vec
     return *reinterpret_cast<const V *>(p);
 }
 
+// Dispatch position -> tile.  flip 0: in order; 1: reversed; 2: reversed in groups of 8, so that a
+// tile keeps blockIdx.x % 8 and with it its XCD under round-robin dispatch (needs gridDim.x % 8 == 0,
+// the launcher passes 1 otherwise).  Speed only: every mapping is a permutation of the tiles.
+__device__ __forceinline__ int visit_tile(int flip)
+{
+    const int g = (int)gridDim.x, b = (int)blockIdx.x;
+    if (flip == 2) return (g / 8 - 1 - b / 8) * 8 + (b & 7);
+    return flip ? g - 1 - b : b;
+}
+
 template <typename T> struct Lanes<T, 1> {
     using V = T;
     static __device__ __forceinline__ T get(const V &v, int) { return v; }
@@ -68,17 +82,26 @@ template <typename T> struct Lanes<T, 1> {
 // Appendix B), as one exec-masked 16-byte store of the updated vector plus scalar stores of
 // next/hops for the updated components.
 //
-// `flip` reverses the block order: launches alternate direction so that the rows streamed last
-// by pivot k are streamed first by pivot k+1 and are served from the 256 MiB Infinity Cache.
+// `flip` (visit_tile) reverses the block order: launches alternate direction so that the tiles
+// streamed last by pivot k are streamed first by pivot k+1; in groups of 8 (flip 2) they also run on
+// the XCD whose L2 still holds them.
+//
+// `nt_below`: the tiles below it (the slab's first rows) stream r[i][j] with non-temporal loads, the
+// rest (its last rows) with default-policy loads, the same rows in every launch whatever the sweep
+// order.  Measured 4-5 % faster per launch at N = 16384 (profiles/r05_tune_relax_policy.txt); the
+// presumed reason, which no counter shows: non-temporal loads do not allocate in the 256 MiB Infinity
+// Cache, so the default-policy rows stay resident there while the rest streams past them.  The pivot
+// row, the pivot-column gather and all stores keep the default policy.  A cache hint only: no result
+// bit depends on it.
 // -------------------------------------------------------------------------------------------------
 template <typename T, int W, int NV, int RPB, int UNROLL, bool HAS_NEXT, bool HAS_HOPS, bool COUNT,
-          int MINW = 1, bool NT = false>
+          int MINW = 1>
 __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int32_t *hops,
                                                const T *prow, const int32_t *phops,
                                                const int32_t *pnext, int rows,
                                                int n, int row0, int k, int nstrips, int flip,
                                                unsigned long long *updates, PathLog plog,
-                                               int skip_lo, int skip_hi)
+                                               int skip_lo, int skip_hi, int nt_below)
 {
     using L = Lanes<T, W>;
     using V = typename L::V;
@@ -90,7 +113,7 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
     __shared__ unsigned int s_cnt;
 
     const int t = threadIdx.x;
-    const int bid = flip ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+    const int bid = visit_tile(flip);
     const int strip = bid % nstrips;
     const int chunk = bid / nstrips;
     const int r_begin = chunk * RPB;
@@ -183,31 +206,37 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
         }
     };
 
-    int r = 0;
-    // Main loop: UNROLL rows x NV vectors of unconditional 16-byte loads in flight per thread.
-    for (; r + UNROLL <= r_cnt; r += UNROLL) {
-        V x[UNROLL][NV];
+    auto stream = [&](auto nt) {
+        constexpr bool NT = decltype(nt)::value;
+        int r = 0;
+        // Main loop: UNROLL rows x NV vectors of unconditional 16-byte loads in flight per thread.
+        for (; r + UNROLL <= r_cnt; r += UNROLL) {
+            V x[UNROLL][NV];
 #pragma unroll
-        for (int u = 0; u < UNROLL; ++u)
+            for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+                for (int v = 0; v < NV; ++v)
+                    x[u][v] = load_vec<V, NT>(base + (size_t)(r + u) * n + col[v]);
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+                for (int v = 0; v < NV; ++v)
+                    relax_vec(x[u][v], p[v], r + u, col[v]);
+        }
+        // Row tail (slab height not a multiple of UNROLL).
+        for (; r < r_cnt; ++r) {
+            V x[NV];
 #pragma unroll
             for (int v = 0; v < NV; ++v)
-                x[u][v] = load_vec<V, NT>(base + (size_t)(r + u) * n + col[v]);
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u)
+                x[v] = load_vec<V, NT>(base + (size_t)r * n + col[v]);
 #pragma unroll
             for (int v = 0; v < NV; ++v)
-                relax_vec(x[u][v], p[v], r + u, col[v]);
-    }
-    // Row tail (slab height not a multiple of UNROLL).
-    for (; r < r_cnt; ++r) {
-        V x[NV];
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-            x[v] = *reinterpret_cast<const V *>(base + (size_t)r * n + col[v]);
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-            relax_vec(x[v], p[v], r, col[v]);
-    }
+                relax_vec(x[v], p[v], r, col[v]);
+        }
+    };
+    // workgroup-uniform: one of the two instantiations, never both
+    if (bid < nt_below) stream(std::true_type());
+    else stream(std::false_type());
 
     if (COUNT) {
         if (my_updates) atomicAdd(&s_cnt, my_updates);
@@ -410,7 +439,7 @@ __global__ __launch_bounds__(256) void snapshot_row(T *dst, const T *src, int32_
 // -------------------------------------------------------------------------------------------------
 // Host-side launchers
 // -------------------------------------------------------------------------------------------------
-template <typename T, int W, int NV, int RPB, int UNROLL, int MINW = 1, bool NT = false>
+template <typename T, int W, int NV, int RPB, int UNROLL, int MINW = 1>
 static hipError_t launch_relax_cfg(const RelaxArgs<T> &a, hipStream_t s)
 {
     constexpr int SW = 256 * NV * W;
@@ -419,10 +448,19 @@ static hipError_t launch_relax_cfg(const RelaxArgs<T> &a, hipStream_t s)
     const dim3 grid((unsigned)(nstrips * nchunks)), block(256);
     if (grid.x == 0) return hipSuccess;
     if (a.skip_hi > a.skip_lo && (a.skip_lo % RPB || a.skip_hi % RPB)) return hipErrorInvalidValue;
+    const int flip = a.flip == 2 && grid.x % 8 ? 1 : a.flip;
+    // Cache policy split: the tiles that hold the last `temporal_bytes` of the slab load with the
+    // default policy, all before them non-temporally (relax_k, `nt_below`).
+    int nt_below = 0;
+    const double slab = (double)a.rows * a.n * sizeof(T);
+    if (a.temporal_bytes >= 0 && slab > (double)a.temporal_bytes) {
+        const double tail = std::ceil((double)a.temporal_bytes / slab * grid.x);
+        nt_below = (int)grid.x - (int)std::min(tail, (double)grid.x);
+    }
 #define FWX_LAUNCH(HN, HH, CN)                                                                     \
-    hipLaunchKernelGGL((relax_k<T, W, NV, RPB, UNROLL, HN, HH, CN, MINW, NT>), grid, block, 0, s, a.rate,    \
+    hipLaunchKernelGGL((relax_k<T, W, NV, RPB, UNROLL, HN, HH, CN, MINW>), grid, block, 0, s, a.rate,  \
                        a.next, a.hops, a.prow, a.phops, a.pnext, a.rows, a.n, a.row0, a.k, nstrips, \
-                       a.flip, a.updates, a.plog, a.skip_lo, a.skip_hi)
+                       flip, a.updates, a.plog, a.skip_lo, a.skip_hi, nt_below)
     const bool hn = a.next != nullptr, hh = a.hops != nullptr, cn = a.updates != nullptr;
     if (hh) {
         if (cn) FWX_LAUNCH(true, true, true); else FWX_LAUNCH(true, true, false);

@@ -27,10 +27,61 @@ __global__ void fill_uniform(float *a, size_t n2, int n, unsigned seed)
 
 struct Cfg { const char *name; hipError_t (*fn)(const fwx::RelaxArgs<float> &, hipStream_t); };
 
-template <int NV, int RPB, int UNROLL, int MINW = 1, bool NT = false>
+template <int NV, int RPB, int UNROLL, int MINW = 1>
 static hipError_t run_cfg(const fwx::RelaxArgs<float> &a, hipStream_t s)
 {
-    return fwx::launch_relax_cfg<float, 4, NV, RPB, UNROLL, MINW, NT>(a, s);
+    return fwx::launch_relax_cfg<float, 4, NV, RPB, UNROLL, MINW>(a, s);
+}
+
+// `policy` mode: the production geometry (fwx::launch_relax) under every combination of temporal-tail
+// budget (RelaxArgs::temporal_bytes: the slab's last rows that keep default-policy loads) and sweep order (flip 0 = plain stream, 1 = serpentine,
+// 2 = serpentine reversed in groups of 8 so tiles keep their XCD), interleaved round by round in one
+// process.  Run once per warm-up (early / late pivots):
+//   tune_relax 16384 1024 32 8 policy      tune_relax 16384 9000 32 8 policy
+static int policy_sweep(float *d, int n, int warm, int per, int rounds)
+{
+    const long long budgets[] = {-1, 0, 128, 160, 192, 224, 240, 256, 288};   // MiB; -1 = all default policy
+    const int nb = sizeof(budgets) / sizeof(budgets[0]), modes = 3;
+    fwx::RelaxArgs<float> a;
+    a.rate = d; a.next = nullptr; a.hops = nullptr; a.phops = nullptr;
+    a.rows = n; a.n = n; a.row0 = 0; a.updates = nullptr;
+    int k = 0;
+    auto step = [&](long long mib, int mode) {
+        a.k = k % n; a.prow = d + (size_t)a.k * n; a.flip = (k & 1) * mode;
+        a.temporal_bytes = mib < 0 ? -1 : mib << 20;
+        CK(fwx::launch_relax<float>(a, 0));
+        ++k;
+    };
+    for (int i = 0; i < warm; ++i) step(-1, 1);
+    CK(hipDeviceSynchronize());
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    std::vector<float> best(nb * modes, 1e30f), sum(nb * modes, 0.f);
+    for (int r = 0; r < rounds; ++r)
+        for (int b = 0; b < nb; ++b)
+            for (int m = 0; m < modes; ++m) {
+                step(budgets[b], m);   // first launch after a switch: not timed
+                CK(hipEventRecord(e0, 0));
+                for (int i = 0; i < per; ++i) step(budgets[b], m);
+                CK(hipEventRecord(e1, 0));
+                CK(hipEventSynchronize(e1));
+                float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                const float us = 1e3f * ms / per;
+                best[b * modes + m] = std::min(best[b * modes + m], us);
+                sum[b * modes + m] += us;
+            }
+    printf("policy n=%d warm=%d per=%d rounds=%d  (us/launch min | mean over rounds; pivots %d..%d)\n", n, warm,
+           per, rounds, warm % n, k % n);
+    printf("%-12s  %-21s  %-21s  %-21s\n", "tail MiB", "plain (flip 0)", "serpentine (flip 1)", "serp XCD (flip 2)");
+    for (int b = 0; b < nb; ++b) {
+        char name[32];
+        if (budgets[b] < 0) snprintf(name, sizeof name, "all default"); else snprintf(name, sizeof name, "%lld", budgets[b]);
+        printf("%-12s", name);
+        for (int m = 0; m < modes; ++m)
+            printf("  %7.1f | %7.1f    ", best[b * modes + m], sum[b * modes + m] / rounds);
+        printf("\n");
+    }
+    return 0;
 }
 
 int main(int argc, char **argv)
@@ -69,6 +120,8 @@ int main(int argc, char **argv)
                (double)n * n * n / (ms * 1e-3));
         return 0;
     }
+
+    if (argc > 5 && !strcmp(argv[5], "policy")) return policy_sweep(d, n, warm, per, rounds);
 
     if (argc > 5 && !strcmp(argv[5], "fused")) {
         // PMC probe mode for the fused engine: `passes` passes of 64 pivots (panel, colpanel, main
