@@ -439,6 +439,18 @@ inline long long perk_temporal_bytes(size_t slab_bytes)
     return (long long)b;
 }
 
+// Store granularity of relax_k's rates-only path (fwx::RelaxArgs::store_bytes): FWX_PERK_STORE_BYTES=<16|32|64|128>
+// overrides FWX_PERK_STORE_BYTES_DEFAULT, read on every call; any other value: the default.  No result bit
+// depends on it.
+inline int perk_store_bytes()
+{
+    if (const char *e = getenv("FWX_PERK_STORE_BYTES")) {
+        const int b = atoi(e);
+        if (b == 16 || b == 32 || b == 64 || b == 128) return b;
+    }
+    return FWX_PERK_STORE_BYTES_DEFAULT;
+}
+
 // One launch per pivot over a slab; pivot rows from `prow0 + (k-k_begin)*stride`.
 template <typename T>
 inline int relax_range(T *rate, int32_t *next, int32_t *hops, int rows, int n, int row0, const T *prow0,
@@ -452,6 +464,7 @@ inline int relax_range(T *rate, int32_t *next, int32_t *hops, int rows, int n, i
     a.rows = rows; a.n = n; a.row0 = row0; a.updates = d_updates; a.plog = plog;
     a.skip_lo = skip_lo; a.skip_hi = skip_hi;
     a.temporal_bytes = perk_temporal_bytes((size_t)rows * n * sizeof(T));
+    a.store_bytes = perk_store_bytes();
     // serpentine: reversed in groups of 8 (tiles keep their XCD) where the split applies -- the regime
     // it was measured in (profiles/r05_tune_relax_policy.txt) -- tile by tile otherwise
     const int rev = FWX_XCD_SERPENTINE && a.temporal_bytes >= 0 ? 2 : 1;

@@ -27,6 +27,10 @@ struct PathLog {
     int32_t *at_row = nullptr;
 };
 
+// Default store granularity of relax_k's rates-only path (RelaxArgs::store_bytes, FWX_PERK_STORE_BYTES):
+// one full 64-byte sector per group of 4 lanes (profiles/r06_tune_relax_stores.txt, r06_bench_ab.txt).
+#define FWX_PERK_STORE_BYTES_DEFAULT 64
+
 template <typename T> struct RelaxArgs {
     T *rate;                       // slab: rows x n
     int32_t *next;                 // or nullptr
@@ -43,6 +47,8 @@ template <typename T> struct RelaxArgs {
     long long temporal_bytes = -1; // the slab's last rows, this many bytes, are streamed with default-policy
                                    // loads in every launch, all rows before them non-temporally; < 0: all
                                    // default policy
+    int store_bytes = 0;           // rates-only store granularity, 16 / 32 / 64 / 128 bytes (relax_k); 0:
+                                   // FWX_PERK_STORE_BYTES_DEFAULT
     int skip_lo = 0, skip_hi = 0;  // slab rows [skip_lo, skip_hi) are left alone (multiples of 4):
                                    //   a look-ahead launch has already relaxed them
     unsigned long long *updates;   // FWX_UPDATE_SHARDS_K counters or nullptr

@@ -79,8 +79,18 @@ template <typename T> struct Lanes<T, 1> {
 // reads 1 KiB of one row, UNROLL*NV such loads are in flight per thread.
 //
 // Stores happen only where r[i][j] < c (about 0.2 % of entries per launch at N = 16384, SURVEY.md
-// Appendix B), as one exec-masked 16-byte store of the updated vector plus scalar stores of
-// next/hops for the updated components.
+// Appendix B).  With next/hops: one exec-masked 16-byte store of the updated vector plus scalar
+// stores of next/hops for the updated components (`SV` = RELAX_SV_LEGACY).  Rates only: the store
+// granularity is GL aligned lanes (GL * 16 bytes, RelaxArgs::store_bytes): when any lane of a
+// group improved, every lane of the group stores its vector, the lanes that did not improve writing
+// back the exact bits they loaded in this launch, so a store covers whole 64-byte sectors / 128-byte
+// lines instead of scattered 16-byte pieces of them.  That write-back is
+// exact because within one launch every element belongs to exactly one lane and no one else writes
+// it: column k gets an identical rewrite under its readers (the pivot-column gathers), row k
+// (NaN pivot operand) never improves so its groups never store.  Clamped lanes (past the end of
+// the row, duplicating the owner of the last vector) are excluded from every group: their copy is
+// stale.  The new vector is built with selects and the group mask comes from a wave ballot
+// outside any divergent region; U counts improved components only.
 //
 // `flip` (visit_tile) reverses the block order: launches alternate direction so that the tiles
 // streamed last by pivot k are streamed first by pivot k+1; in groups of 8 (flip 2) they also run on
@@ -94,8 +104,18 @@ template <typename T> struct Lanes<T, 1> {
 // row, the pivot-column gather and all stores keep the default policy.  A cache hint only: no result
 // bit depends on it.
 // -------------------------------------------------------------------------------------------------
+// Store variants (SV).  The production rates-only path is RELAX_SV_SELECT; next/hops always take
+// RELAX_SV_LEGACY.  The others exist for tools/tune_relax.hip `stores` mode only (timing; their
+// results are wrong by design): SKIP = SELECT behind a wave-uniform skip of rows where no lane
+// compares true, NOSTORE = LEGACY with every store suppressed (its arithmetic and branch kept),
+// NORARE = the rare path compiled out (loads and compares kept), NTST = SELECT with non-temporal
+// stores everywhere.  NTST_NTROWS = SELECT with non-temporal stores in the rows that are streamed
+// with non-temporal loads (`nt_below`), default-policy stores in the temporal tail.
+enum { RELAX_SV_SELECT = 0, RELAX_SV_SKIP = 1, RELAX_SV_LEGACY = 2, RELAX_SV_NOSTORE = 3, RELAX_SV_NORARE = 4,
+       RELAX_SV_NTST = 5, RELAX_SV_NTST_NTROWS = 6 };
+
 template <typename T, int W, int NV, int RPB, int UNROLL, bool HAS_NEXT, bool HAS_HOPS, bool COUNT,
-          int MINW = 1>
+          int MINW = 1, int GL = 1, int SV = RELAX_SV_SELECT>
 __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int32_t *hops,
                                                const T *prow, const int32_t *phops,
                                                const int32_t *pnext, int rows,
@@ -151,11 +171,16 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
     // Pivot row segment -> registers.  Column k gets NaN: skip j == k.  Columns past the end
     // of the row are CLAMPED to the last in-range vector and their pivot set to NaN: the
     // streaming loads stay unconditional (valid addresses) and such lanes can never update.
+    static_assert(GL == 1 || GL == 2 || GL == 4 || GL == 8, "store group: 1, 2, 4 or 8 lanes");
+    constexpr bool SEL = !HAS_NEXT && !HAS_HOPS && (SV == RELAX_SV_SELECT || SV == RELAX_SV_SKIP ||
+                                                    SV == RELAX_SV_NTST || SV == RELAX_SV_NTST_NTROWS);
     V p[NV];
     int col[NV];
+    bool own[NV];             // false: a clamped lane (never stores)
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
         const int c0 = strip * SW + (v * 256 + t) * W;
+        own[v] = c0 < n;
         if (c0 < n) {
             col[v] = c0;
             p[v] = *reinterpret_cast<const V *>(prow + c0);
@@ -170,10 +195,12 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
     __syncthreads();
 
     unsigned int my_updates = 0;
+    bool sink = false;        // RELAX_SV_NORARE: keeps the compares alive
     T *const base = rate + (size_t)r_begin * n;
+    const int g0 = (int)(__lane_id() & ~(GL - 1));   // first lane of my store group
 
     // One row of one vector: compare, and in the rare case that something improves, store.
-    auto relax_vec = [&](const V &x, const V &pv, int r, int cv) {
+    auto relax_vec = [&](const V &x, const V &pv, int r, int cv, bool mine, auto nt) {
         const T rik = s_col[r];
         bool any = false;
         T cand[W];
@@ -181,6 +208,37 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
         for (int c = 0; c < W; ++c) {
             cand[c] = rik * L::get(pv, c);
             any |= (L::get(x, c) < cand[c]);
+        }
+        if constexpr (SV == RELAX_SV_NORARE) {
+            sink |= any;
+            return;
+        }
+        if constexpr (SEL) {
+            // All lanes of the wave are active here (r is workgroup-uniform).  Selects, not branches;
+            // the diagonal filter and the strict `<` as in the legacy path below.
+            if (SV == RELAX_SV_SKIP && !__any(any)) return;   // wave-uniform
+            const int i = row0 + r_begin + r;
+            V nx = x;
+            bool changed = false;
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                const bool up = L::get(x, c) < cand[c] && cv + c != i;
+                L::set(nx, c, up ? cand[c] : L::get(x, c));
+                changed |= up;
+                if (COUNT) my_updates += up;
+            }
+            bool st = changed;
+            if constexpr (GL > 1) {
+                const unsigned long long m = __ballot(changed);
+                st = mine && ((m >> g0) & ((1ull << GL) - 1)) != 0;
+            }
+            V *const dst = reinterpret_cast<V *>(rate + (size_t)(r_begin + r) * n + cv);
+            if (SV == RELAX_SV_NTST || (SV == RELAX_SV_NTST_NTROWS && decltype(nt)::value)) {
+                if (st) __builtin_nontemporal_store(nx, dst);
+            } else if (st) {
+                *dst = nx;
+            }
+            return;
         }
         if (any) {
             // Rare path: some component improves.  The diagonal (j == i) is filtered here.
@@ -202,7 +260,7 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
                     if (COUNT) ++my_updates;
                 }
             }
-            if (changed) *reinterpret_cast<V *>(rate + off) = nx;
+            if (changed && (SV != RELAX_SV_NOSTORE || k < 0)) *reinterpret_cast<V *>(rate + off) = nx;
         }
     };
 
@@ -221,7 +279,7 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
             for (int u = 0; u < UNROLL; ++u)
 #pragma unroll
                 for (int v = 0; v < NV; ++v)
-                    relax_vec(x[u][v], p[v], r + u, col[v]);
+                    relax_vec(x[u][v], p[v], r + u, col[v], own[v], nt);
         }
         // Row tail (slab height not a multiple of UNROLL).
         for (; r < r_cnt; ++r) {
@@ -231,12 +289,13 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
                 x[v] = load_vec<V, NT>(base + (size_t)r * n + col[v]);
 #pragma unroll
             for (int v = 0; v < NV; ++v)
-                relax_vec(x[v], p[v], r, col[v]);
+                relax_vec(x[v], p[v], r, col[v], own[v], nt);
         }
     };
     // workgroup-uniform: one of the two instantiations, never both
     if (bid < nt_below) stream(std::true_type());
     else stream(std::false_type());
+    if (SV == RELAX_SV_NORARE && sink && k < 0) rate[0] = T(0);   // never: k >= 0
 
     if (COUNT) {
         if (my_updates) atomicAdd(&s_cnt, my_updates);
@@ -439,7 +498,7 @@ __global__ __launch_bounds__(256) void snapshot_row(T *dst, const T *src, int32_
 // -------------------------------------------------------------------------------------------------
 // Host-side launchers
 // -------------------------------------------------------------------------------------------------
-template <typename T, int W, int NV, int RPB, int UNROLL, int MINW = 1>
+template <typename T, int W, int NV, int RPB, int UNROLL, int MINW = 1, int SV = RELAX_SV_SELECT>
 static hipError_t launch_relax_cfg(const RelaxArgs<T> &a, hipStream_t s)
 {
     constexpr int SW = 256 * NV * W;
@@ -457,18 +516,31 @@ static hipError_t launch_relax_cfg(const RelaxArgs<T> &a, hipStream_t s)
         const double tail = std::ceil((double)a.temporal_bytes / slab * grid.x);
         nt_below = (int)grid.x - (int)std::min(tail, (double)grid.x);
     }
-#define FWX_LAUNCH(HN, HH, CN)                                                                     \
-    hipLaunchKernelGGL((relax_k<T, W, NV, RPB, UNROLL, HN, HH, CN, MINW>), grid, block, 0, s, a.rate,  \
-                       a.next, a.hops, a.prow, a.phops, a.pnext, a.rows, a.n, a.row0, a.k, nstrips, \
-                       flip, a.updates, a.plog, a.skip_lo, a.skip_hi, nt_below)
+    // Store group of the rates-only path in lanes of 16 bytes (the scalar path stores per lane).
+    const int sb = a.store_bytes > 0 ? a.store_bytes : FWX_PERK_STORE_BYTES_DEFAULT;
+    const int gl = sb >= 128 ? 8 : sb >= 64 ? 4 : sb >= 32 ? 2 : 1;
+#define FWX_LAUNCH(HN, HH, CN, GL)                                                                 \
+    hipLaunchKernelGGL((relax_k<T, W, NV, RPB, UNROLL, HN, HH, CN, MINW, GL, SV>), grid, block, 0, s, \
+                       a.rate, a.next, a.hops, a.prow, a.phops, a.pnext, a.rows, a.n, a.row0, a.k,  \
+                       nstrips, flip, a.updates, a.plog, a.skip_lo, a.skip_hi, nt_below)
+#define FWX_LAUNCH_GL(CN)                                                                          \
+    do {                                                                                           \
+        if constexpr (W * sizeof(T) == 16) {                                                       \
+            if (gl == 8) { FWX_LAUNCH(false, false, CN, 8); break; }                               \
+            if (gl == 4) { FWX_LAUNCH(false, false, CN, 4); break; }                               \
+            if (gl == 2) { FWX_LAUNCH(false, false, CN, 2); break; }                               \
+        }                                                                                          \
+        FWX_LAUNCH(false, false, CN, 1);                                                           \
+    } while (0)
     const bool hn = a.next != nullptr, hh = a.hops != nullptr, cn = a.updates != nullptr;
     if (hh) {
-        if (cn) FWX_LAUNCH(true, true, true); else FWX_LAUNCH(true, true, false);
+        if (cn) FWX_LAUNCH(true, true, true, 1); else FWX_LAUNCH(true, true, false, 1);
     } else if (hn) {
-        if (cn) FWX_LAUNCH(true, false, true); else FWX_LAUNCH(true, false, false);
+        if (cn) FWX_LAUNCH(true, false, true, 1); else FWX_LAUNCH(true, false, false, 1);
     } else {
-        if (cn) FWX_LAUNCH(false, false, true); else FWX_LAUNCH(false, false, false);
+        if (cn) FWX_LAUNCH_GL(true); else FWX_LAUNCH_GL(false);
     }
+#undef FWX_LAUNCH_GL
 #undef FWX_LAUNCH
     return hipGetLastError();
 }

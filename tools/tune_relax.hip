@@ -84,6 +84,119 @@ static int policy_sweep(float *d, int n, int warm, int per, int rounds)
     return 0;
 }
 
+// `stores` mode: what relax_k's write path costs.  Every variant starts each pivot window from its own
+// copy of the matrix state at the window's first pivot (the uniform D1 distribution, states made by the
+// production path), runs the production geometry and sweep order with the temporal tail on (the
+// default budget) and off, and is timed per window: the first `per` pivots, from k = 4096 and from
+// k = 12000.  Variants (fwx::RELAX_SV_*): the legacy 16-byte store path (the parent's production), the
+// same with every store suppressed (arithmetic and branch kept), the rare path compiled out, and the
+// select path (wave ballot, one store per group) at G = 16 / 32 / 64 / 128 bytes, branch-free and behind
+// a wave-uniform skip, and with non-temporal stores (everywhere / in the non-temporal rows only).  Results of the suppressed variants are wrong by design; the per-window update
+// count U comes from a counting run of the production path.
+//   tune_relax 16384 0 256 3 stores
+template <int GL, int SV>
+static hipError_t run_sv(const fwx::RelaxArgs<float> &a0, hipStream_t s)
+{
+    fwx::RelaxArgs<float> a = a0;
+    a.store_bytes = GL * 16;
+    return fwx::launch_relax_cfg<float, 4, 1, 4, 4, 1, SV>(a, s);
+}
+
+static int stores_sweep(float *d, int n, int per, int rounds)
+{
+    const std::vector<Cfg> vars = {
+        {"legacy G16 (parent)", run_sv<1, fwx::RELAX_SV_LEGACY>},
+        {"legacy, no stores", run_sv<1, fwx::RELAX_SV_NOSTORE>},
+        {"rare path out", run_sv<1, fwx::RELAX_SV_NORARE>},
+        {"select G16", run_sv<1, fwx::RELAX_SV_SELECT>},
+        {"select G32", run_sv<2, fwx::RELAX_SV_SELECT>},
+        {"select G64", run_sv<4, fwx::RELAX_SV_SELECT>},
+        {"select G128", run_sv<8, fwx::RELAX_SV_SELECT>},
+        {"skip+select G16", run_sv<1, fwx::RELAX_SV_SKIP>},
+        {"skip+select G32", run_sv<2, fwx::RELAX_SV_SKIP>},
+        {"skip+select G64", run_sv<4, fwx::RELAX_SV_SKIP>},
+        {"skip+select G128", run_sv<8, fwx::RELAX_SV_SKIP>},
+        {"select G64 nt-st", run_sv<4, fwx::RELAX_SV_NTST>},
+        {"select G128 nt-st", run_sv<8, fwx::RELAX_SV_NTST>},
+        {"G64 nt-st nt rows", run_sv<4, fwx::RELAX_SV_NTST_NTROWS>},
+        {"G128 nt-st nt rows", run_sv<8, fwx::RELAX_SV_NTST_NTROWS>},
+    };
+    const int k0s[3] = {0, 4096, 12000}, nw = 3, nv = (int)vars.size();
+    const size_t bytes = (size_t)n * n * sizeof(float);
+    float *snap[3], *work;
+    for (int w = 0; w < nw; ++w) CK(hipMalloc(&snap[w], bytes));
+    CK(hipMalloc(&work, bytes));
+    unsigned long long *upd;
+    CK(hipMalloc(&upd, FWX_UPDATE_SHARDS_K * sizeof(unsigned long long)));
+    fwx::RelaxArgs<float> a;
+    a.rate = work; a.next = nullptr; a.hops = nullptr; a.phops = nullptr;
+    a.rows = n; a.n = n; a.row0 = 0; a.updates = nullptr;
+    const long long tb[2] = {256ll << 20, -1};   // tail on (the default 256 MiB) / off
+    auto launch = [&](const Cfg &c, int k, int t) {
+        a.k = k; a.prow = work + (size_t)k * n;
+        a.temporal_bytes = tb[t];
+        a.flip = (k & 1) * (t == 0 ? 2 : 1);   // relax_range's serpentine
+        CK(c.fn(a, 0));
+    };
+    // window states: the production path from the pristine matrix
+    const Cfg prod = {"production", fwx::launch_relax<float>};
+    CK(hipMemcpy(work, d, bytes, hipMemcpyDeviceToDevice));
+    for (int w = 0, k = 0; w < nw; ++w) {
+        for (; k < k0s[w] && k < n; ++k) launch(prod, k, 0);
+        CK(hipMemcpy(snap[w], work, bytes, hipMemcpyDeviceToDevice));
+    }
+    unsigned long long u[3];
+    for (int w = 0; w < nw; ++w) {
+        CK(hipMemcpy(work, snap[w], bytes, hipMemcpyDeviceToDevice));
+        CK(hipMemset(upd, 0, FWX_UPDATE_SHARDS_K * sizeof(unsigned long long)));
+        a.updates = upd;
+        for (int k = k0s[w]; k < std::min(n, k0s[w] + per); ++k) launch(prod, k, 0);
+        a.updates = nullptr;
+        std::vector<unsigned long long> h(FWX_UPDATE_SHARDS_K);
+        CK(hipMemcpy(h.data(), upd, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost));
+        u[w] = 0;
+        for (auto x : h) u[w] += x;
+    }
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    std::vector<float> best(nv * 2 * nw, 1e30f), sum(nv * 2 * nw, 0.f);
+    for (int r = 0; r < rounds; ++r)
+        for (int v = 0; v < nv; ++v)
+            for (int t = 0; t < 2; ++t)
+                for (int w = 0; w < nw; ++w) {
+                    const int kb = k0s[w], ke = std::min(n, k0s[w] + per);
+                    if (ke <= kb) continue;
+                    CK(hipMemcpyAsync(work, snap[w], bytes, hipMemcpyDeviceToDevice, 0));
+                    CK(hipEventRecord(e0, 0));
+                    for (int k = kb; k < ke; ++k) launch(vars[v], k, t);
+                    CK(hipEventRecord(e1, 0));
+                    CK(hipEventSynchronize(e1));
+                    float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                    const float us = 1e3f * ms / (ke - kb);
+                    const int i = (v * 2 + t) * nw + w;
+                    best[i] = std::min(best[i], us);
+                    sum[i] += us;
+                }
+    printf("stores n=%d per=%d rounds=%d  (us/launch min | mean over rounds; windows from k = %d, %d, %d)\n", n,
+           per, rounds, k0s[0], k0s[1], k0s[2]);
+    printf("updates per launch (production, U / launches): %.0f  %.0f  %.0f\n", (double)u[0] / per,
+           (double)u[1] / per, (double)u[2] / per);
+    for (int t = 0; t < 2; ++t) {
+        printf("\ntemporal tail %s\n%-20s", t == 0 ? "on (default budget)" : "off (all default policy)", "variant");
+        for (int w = 0; w < nw; ++w) printf("  k=%-5d min | mean   ", k0s[w]);
+        printf("\n");
+        for (int v = 0; v < nv; ++v) {
+            printf("%-20s", vars[v].name);
+            for (int w = 0; w < nw; ++w) {
+                const int i = (v * 2 + t) * nw + w;
+                printf("  %7.1f | %7.1f    ", best[i], sum[i] / rounds);
+            }
+            printf("\n");
+        }
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const int n = argc > 1 ? atoi(argv[1]) : 16384;
@@ -122,6 +235,7 @@ int main(int argc, char **argv)
     }
 
     if (argc > 5 && !strcmp(argv[5], "policy")) return policy_sweep(d, n, warm, per, rounds);
+    if (argc > 5 && !strcmp(argv[5], "stores")) return stores_sweep(d, n, per, rounds);
 
     if (argc > 5 && !strcmp(argv[5], "fused")) {
         // PMC probe mode for the fused engine: `passes` passes of 64 pivots (panel, colpanel, main
