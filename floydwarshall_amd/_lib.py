@@ -91,6 +91,8 @@ SIGNATURES = {
     "fwx_last_hip_error": (ctypes.c_int, []),
     "fwx_hip_versions": (ctypes.c_int, [ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
     "fwx_test_fail_after": (ctypes.c_int, [c_i32]),
+    "fwx_test_kernel_forms": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "fwx_test_kernel_form_name": (ctypes.c_char_p, [ctypes.c_int]),
     "fwx_solve_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
     "fwx_solve_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
     "fwx_follow_path": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i32, c_vp, c_i32]),

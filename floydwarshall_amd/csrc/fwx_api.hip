@@ -914,6 +914,24 @@ int fwx_test_fail_after(int32_t countdown)
     return FWX_OK;
 }
 
+int fwx_test_kernel_forms(uint64_t *seen, int reset)
+{
+    if (seen) *seen = reset ? fwx::g_kernel_forms.exchange(0, std::memory_order_relaxed)
+                            : fwx::g_kernel_forms.load(std::memory_order_relaxed);
+    else if (reset) fwx::g_kernel_forms.store(0, std::memory_order_relaxed);
+    return fwx::KF_COUNT;
+}
+
+const char *fwx_test_kernel_form_name(int form)
+{
+    static const char *const names[] = {
+#define FWX_KERNEL_FORM_NAME(name) #name,
+        FWX_KERNEL_FORM_LIST(FWX_KERNEL_FORM_NAME)
+#undef FWX_KERNEL_FORM_NAME
+    };
+    return form >= 0 && form < fwx::KF_COUNT ? names[form] : nullptr;
+}
+
 const char *fwx_strerror(int status)
 {
     switch (status) {

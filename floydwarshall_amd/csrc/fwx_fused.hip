@@ -2234,9 +2234,27 @@ template <> struct FusedCfg<double, true> { static constexpr int BS = 16, MINW =
 
 // Below ~512 full-size tiles the launch is bound by the latency of ONE tile (64 pivots folded into
 // 64 entries per thread); 64 x 64 tiles give 4x the workgroups and a quarter of the serial work.
-static bool small_tiles(int n, int rows, long long thresh = 512)
+static bool small_tiles(int n, int rows, long long thresh)
 {
     return (long long)((n + 127) / 128) * ((rows + 127) / 128) < thresh;
+}
+// Tile-count thresholds: read once per process.  FWX_SMALL_TILES_BELOW (default 512, the generic and
+// max-form kernels' 64 x 64 tiles) and FWX_MID_TILES_BELOW (default 3600, the f32 max form's 128 x 64
+// tiles) exist for the tests, which set them to 0 to run the large-tile forms at small orders.
+static long long env_tiles(const char *name, long long dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoll(e) : dflt;
+}
+static bool small_tiles(int n, int rows)
+{
+    static const long long thresh = env_tiles("FWX_SMALL_TILES_BELOW", 512);
+    return small_tiles(n, rows, thresh);
+}
+static bool mid_tiles(int n, int rows)
+{
+    static const long long thresh = env_tiles("FWX_MID_TILES_BELOW", 3600);
+    return small_tiles(n, rows, thresh);
 }
 // The arg kernel keeps a tile's workgroup busy for longer (fold + re-scan) and runs 3 workgroups per
 // CU: its 64 x 64 form pays off up to larger matrices (measured, rates + next: N = 4096 9.54 -> 8.8
@@ -2245,10 +2263,7 @@ static bool small_tiles(int n, int rows, long long thresh = 512)
 // 6144 18.56 / 18.88, 8192 39.17 / 38.96, 10240 70.56 / 72.02: level or ahead up to there.
 static bool small_tiles_arg(int n, int rows)
 {
-    static const long long thresh = [] {               // FWX_ARG_SMALL_TILES_BELOW: A/B switch
-        const char *e = getenv("FWX_ARG_SMALL_TILES_BELOW");
-        return e ? atoll(e) : 6500LL;
-    }();
+    static const long long thresh = env_tiles("FWX_ARG_SMALL_TILES_BELOW", 6500);   // A/B switch
     return small_tiles(n, rows, thresh);
 }
 
@@ -2313,27 +2328,32 @@ static bool launch_max_form(const FusedArgs<float> &a, dim3 grid, dim3 block, in
                            a.hops, a.cht, a.wh, cw)
         if (small || small_tiles_arg(a.n, a.rows)) {
             const dim3 g(small ? grid.x : (unsigned)((a.n + 63) / 64), (unsigned)((a.rows + 63) / 64));
-            if (a.bt > B) FWX_ARG_LAUNCH(4, 2, g); else FWX_ARG_LAUNCH(4, 1, g);
+            if (a.bt > B) { note_form(KF_ARG_RI4_NP2_F32); FWX_ARG_LAUNCH(4, 2, g); }
+            else { note_form(KF_ARG_RI4_NP1_F32); FWX_ARG_LAUNCH(4, 1, g); }
         } else {
             const dim3 g((unsigned)((a.n + 63) / 64), (unsigned)((a.rows + 127) / 128));
-            if (a.bt > B) FWX_ARG_LAUNCH(8, 2, g); else FWX_ARG_LAUNCH(8, 1, g);
+            if (a.bt > B) { note_form(KF_ARG_RI8_NP2_F32); FWX_ARG_LAUNCH(8, 2, g); }
+            else { note_form(KF_ARG_RI8_NP1_F32); FWX_ARG_LAUNCH(8, 1, g); }
         }
 #undef FWX_ARG_LAUNCH
         return true;
     }
     if (small) {
+        note_form(KF_MAX_SMALL_F32);
         hipLaunchKernelGGL((fused_main_max<4, 1, 4, 1>), grid, block, 0, s, a.rate, a.rows, a.n, a.row0,
                            a.k0, a.bt, a.w, a.ct, a.ct_ld, ct_vec, skip_lo, skip_hi, cw);
-    } else if (small_tiles(a.n, a.rows, 3600)) {
+    } else if (mid_tiles(a.n, a.rows)) {
         // mid sizes: 128 x 64 tiles.  The 768 workgroup slots of the chip quantise a launch of 128 x 128
         // tiles badly (N = 4096: 1024 tiles = 1.33 rounds), half-width tiles halve the step; their
         // extra LDS operand reads cost less than that up to N = 7168 (gpurun_out/r02_run58.log:
         // 3072: 2.65 -> 2.44 ms, 4096: 4.40 -> 4.26, 6144: 11.04 -> 10.61, 7168: 16.0 -> 15.7; from
         // 8192 on the full tile wins: 22.35 against 22.65 ms)
         const dim3 g((unsigned)((a.n + 63) / 64), (unsigned)((a.rows + 127) / 128));
+        note_form(KF_MAX_MID_F32);
         hipLaunchKernelGGL((fused_main_max<3, 1, 8, 1>), g, block, 0, s, a.rate, a.rows, a.n,
                            a.row0, a.k0, a.bt, a.w, a.ct, a.ct_ld, ct_vec, skip_lo, skip_hi, cw);
     } else {
+        note_form(KF_MAX_LARGE_F32);
         hipLaunchKernelGGL((fused_main_max<3, 1, 8, 2>), grid, block, 0, s, a.rate, a.rows, a.n,
                            a.row0, a.k0, a.bt, a.w, a.ct, a.ct_ld, ct_vec, skip_lo, skip_hi, cw);
     }
@@ -2364,9 +2384,11 @@ static bool launch_max_form(const FusedArgs<double> &a, dim3 grid, dim3 block, i
                            a.next, a.rows, a.n, a.row0, a.k0, a.bt, a.w, a.ct, a.cnt, a.ct_ld, ct_vec,      \
                            skip_lo, skip_hi, last, a.hops, a.cht, a.wh, c2)
         if (tall) {
-            if (a.bt > B) FWX_ARG64_LAUNCH(2, 4, 2); else FWX_ARG64_LAUNCH(2, 4, 1);
+            if (a.bt > B) { note_form(KF_ARG_F64_RI4_NP2); FWX_ARG64_LAUNCH(2, 4, 2); }
+            else { note_form(KF_ARG_F64_RI4_NP1); FWX_ARG64_LAUNCH(2, 4, 1); }
         } else {
-            if (a.bt > B) FWX_ARG64_LAUNCH(3, 2, 2); else FWX_ARG64_LAUNCH(3, 2, 1);
+            if (a.bt > B) { note_form(KF_ARG_F64_RI2_NP2); FWX_ARG64_LAUNCH(3, 2, 2); }
+            else { note_form(KF_ARG_F64_RI2_NP1); FWX_ARG64_LAUNCH(3, 2, 1); }
         }
 #undef FWX_ARG64_LAUNCH
         return true;
@@ -2374,10 +2396,12 @@ static bool launch_max_form(const FusedArgs<double> &a, dim3 grid, dim3 block, i
     if (!small) {
         const int ct_vec = ((uintptr_t)a.ct % 16 == 0 && a.ct_ld % 2 == 0) ? 1 : 0;
         const dim3 g((unsigned)((a.n + 127) / 128), (unsigned)((a.rows + 127) / 128));
+        note_form(KF_MAX_LARGE_F64);
         hipLaunchKernelGGL((fused_main_max_f64<2>), g, block, 0, s, a.rate, a.rows, a.n, a.row0, a.k0,
                            a.bt, a.w, a.ct, a.ct_ld, ct_vec, skip_lo, skip_hi, cw);
         return true;
     }
+    note_form(KF_MAX_SMALL_F64);
     hipLaunchKernelGGL((fused_main<double, false, false, 16, 2, 1, 4, true>), grid, block, 0, s,
                        a.rate, a.next, a.rows, a.n, a.row0, a.k0, a.bt, a.w, a.ct, a.cnt,
                        a.ct_ld, skip_lo, skip_hi, a.updates, nullptr, nullptr, nullptr, nullptr, cw);
@@ -2440,6 +2464,7 @@ template <typename T> hipError_t launch_fused_colpanel(const FusedArgs<T> &a, hi
     // (the trace matrices of a slab are indexed by LOCAL row, like its rate / next)
     if (a.plog.last && !a.next) return hipErrorInvalidValue;
     if (a.hops && (!a.next || !a.wh || !a.cht)) return hipErrorInvalidValue;
+    note_form(sizeof(T) == 4 ? KF_COLPANEL_F32 : KF_COLPANEL_F64);
 #define FWX_COLPANEL(HN, HL, HH)                                                                   \
     hipLaunchKernelGGL((fused_colpanel<T, HN, HL, HH>), cgrid, block, 0, s, a.rate, a.next, a.rows, a.n, \
                        a.row0, a.k0, a.bt, a.w, a.ct, a.cnt, a.ct_ld, a.plog.last, a.plog.at_col,  \
@@ -2504,6 +2529,8 @@ hipError_t launch_fused_main(const FusedArgs<T> &full, int r_lo, int r_hi, hipSt
         grid.x = (unsigned)((cols.c_hi - cols.c_lo) / tj);
     }
     if (launch_max_form(a, grid, block, skip_lo, skip_hi, s, last, small, cw, window)) return hipGetLastError();
+    note_form(sizeof(T) == 4 ? (small ? KF_MAIN_SMALL_F32 : KF_MAIN_LARGE_F32)
+                             : (small ? KF_MAIN_SMALL_F64 : KF_MAIN_LARGE_F64));
 #define FWX_FUSED_LAUNCH(HN, CN, HL)                                                               \
     do {                                                                                           \
         if (small)                                                                                 \
@@ -2546,6 +2573,7 @@ hipError_t launch_fused_panel(const T *rows_base, int n, int k0, int bt, T *w, h
     if (n <= 0 || bt <= 0) return hipSuccess;
     if (bt > B || (hops_rows && !wh)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + 63) / 64)), block(PANEL_THREADS);
+    note_form(sizeof(T) == 4 ? KF_ROWPANEL_F32 : KF_ROWPANEL_F64);
     // plog / hops_rows point at the SAME rows as rows_base (pivot row k0 of those matrices)
 #define FWX_ROWPANEL(HL, HH)                                                                       \
     hipLaunchKernelGGL((fused_rowpanel<T, HL, HH>), grid, block, 0, s, rows_base, n, k0, bt, w, plog.last, \
@@ -2583,11 +2611,13 @@ hipError_t launch_fused_panels(const FusedArgs<T> &a, T *w_out, int32_t *wh_out,
         // registers, 4 x 40 > the 128 a retiring main workgroup frees: no point, the 64-row form stays
         if (a.side && fused_panels_fit_beside(a)) {
             const dim3 g32((unsigned)(row_wgs + (a.n + 31) / 32));
+            note_form(KF_PANELS_NEXT_F32_R32);
             hipLaunchKernelGGL((fused_panels_next_f32<false, 32>), g32, block, 0, s, row_wgs, a.rate, a.next, a.n, a.k0,
                                a.bt, w_out, a.ct, a.cnt, a.ct_ld, nullptr, nullptr, nullptr);
             return hipGetLastError();
         }
         if (tight && a.next && !a.hops) {
+            note_form(a.plog.last ? KF_PANELS_NEXT_TRACE_F32 : KF_PANELS_NEXT_F32);
             if (a.plog.last)
                 hipLaunchKernelGGL(fused_panels_next_f32<true>, grid, block, 0, s, row_wgs, a.rate, a.next, a.n, a.k0,
                                    a.bt, w_out, a.ct, a.cnt, a.ct_ld, a.plog.last, a.plog.at_row, a.plog.at_col);
@@ -2597,6 +2627,9 @@ hipError_t launch_fused_panels(const FusedArgs<T> &a, T *w_out, int32_t *wh_out,
             return hipGetLastError();
         }
     }
+    const bool max_form = !a.plog.last && !a.next && a.nonneg;
+    note_form(sizeof(T) == 4 ? (max_form ? KF_PANELS_MAX_F32 : KF_PANELS_F32)
+                             : (max_form ? KF_PANELS_MAX_F64 : KF_PANELS_F64));
     if (a.plog.last) {
         if (a.hops) FWX_PANELS(true, true, true); else FWX_PANELS(true, true, false);
     } else if (a.next) {

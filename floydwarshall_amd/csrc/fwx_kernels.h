@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 // Must equal FWX_UPDATE_SHARDS of include/fwx.h (power of two).
 #define FWX_UPDATE_SHARDS_K 256
 
@@ -26,6 +28,54 @@ struct PathLog {
     int32_t *at_col = nullptr;
     int32_t *at_row = nullptr;
 };
+
+// Record of the launch forms a process has used (test hook fwx_test_kernel_forms, fwx.h): one bit per
+// form, and within a form one per instantiation that a threshold picks (tile size, passes per launch).
+// Every launch site ORs its bit into one process-global word -- one relaxed host atomic per launch,
+// nothing on the device; global because the partition sweeps launch from worker threads.  The names
+// (fwx_test_kernel_form_name) are what floydwarshall_amd.engine.KERNEL_FORMS must list, in this order.
+#define FWX_KERNEL_FORM_LIST(X)                                                                    \
+    X(SMALL_SOLVE)          /* small_solve, n <= FWX_SMALL_N */                                    \
+    X(RELAX_K)              /* relax_k, the per-k engine */                                        \
+    X(ROWPANEL_F32)         /* launch_fused_panel */                                               \
+    X(ROWPANEL_F64)                                                                                \
+    X(COLPANEL_F32)         /* launch_fused_colpanel */                                            \
+    X(COLPANEL_F64)                                                                                \
+    X(PANELS_F32)           /* launch_fused_panels: fused_panels, compare form */                  \
+    X(PANELS_F64)                                                                                  \
+    X(PANELS_MAX_F32)       /* fused_panels, max form (rates only, in the domain) */               \
+    X(PANELS_MAX_F64)                                                                              \
+    X(PANELS_NEXT_F32)      /* fused_panels_next_f32<false> */                                     \
+    X(PANELS_NEXT_TRACE_F32) /* fused_panels_next_f32<true> */                                     \
+    X(PANELS_NEXT_F32_R32)  /* fused_panels_next_f32<false, 32>, beside a main launch */           \
+    X(MAIN_SMALL_F32)       /* launch_fused_main: generic fused_main, 64 x 64 tiles */             \
+    X(MAIN_LARGE_F32)       /* ... 128-row tiles */                                                \
+    X(MAIN_SMALL_F64)                                                                              \
+    X(MAIN_LARGE_F64)                                                                              \
+    X(MAX_SMALL_F32)        /* fused_main_max<4, 1, 4, 1> */                                       \
+    X(MAX_MID_F32)          /* fused_main_max<3, 1, 8, 1> */                                       \
+    X(MAX_LARGE_F32)        /* fused_main_max<3, 1, 8, 2> */                                       \
+    X(ARG_RI4_NP1_F32)      /* fused_main_arg<3, RI, NP> */                                        \
+    X(ARG_RI4_NP2_F32)                                                                             \
+    X(ARG_RI8_NP1_F32)                                                                             \
+    X(ARG_RI8_NP2_F32)                                                                             \
+    X(MAX_SMALL_F64)        /* fused_main<double, ..., MAXF = true> */                             \
+    X(MAX_LARGE_F64)        /* fused_main_max_f64<2> */                                            \
+    X(ARG_F64_RI4_NP1)      /* fused_main_arg_f64<2, 4, NP> (64 x 64 tiles) */                     \
+    X(ARG_F64_RI4_NP2)                                                                             \
+    X(ARG_F64_RI2_NP1)      /* fused_main_arg_f64<3, 2, NP> (FWX_ARG_F64_SHORT_TILES=1) */         \
+    X(ARG_F64_RI2_NP2)
+
+enum KernelForm {
+#define FWX_KERNEL_FORM_ENUM(name) KF_##name,
+    FWX_KERNEL_FORM_LIST(FWX_KERNEL_FORM_ENUM)
+#undef FWX_KERNEL_FORM_ENUM
+    KF_COUNT
+};
+static_assert(KF_COUNT <= 64, "one bit per form in a 64-bit word");
+
+inline std::atomic<uint64_t> g_kernel_forms{0};
+inline void note_form(KernelForm f) { g_kernel_forms.fetch_or(1ull << f, std::memory_order_relaxed); }
 
 // Default store granularity of relax_k's rates-only path (RelaxArgs::store_bytes, FWX_PERK_STORE_BYTES):
 // one full 64-byte sector per group of 4 lanes (profiles/r06_tune_relax_stores.txt, r06_bench_ab.txt).

@@ -462,6 +462,7 @@ hipError_t launch_small_solve(T *rate, int32_t *next, int32_t *hops, int n, int 
 {
     if (n <= 0 || k_end <= k_begin) return hipSuccess;
     if (n > FWX_SMALL_N || (hops && !next) || k_begin < 0 || k_end > n) return hipErrorInvalidValue;
+    note_form(KF_SMALL_SOLVE);
 #define FWX_SMALL(M, RG, HN, HH, LG)                                                               \
     hipLaunchKernelGGL((small_solve<T, M, RG, HN, HH, LG>), dim3(1), dim3(M * RG), 0, s, rate,     \
                        next, hops, n, k_begin, k_end, updates, plog)
@@ -533,6 +534,7 @@ static hipError_t launch_relax_cfg(const RelaxArgs<T> &a, hipStream_t s)
         FWX_LAUNCH(false, false, CN, 1);                                                           \
     } while (0)
     const bool hn = a.next != nullptr, hh = a.hops != nullptr, cn = a.updates != nullptr;
+    note_form(KF_RELAX_K);
     if (hh) {
         if (cn) FWX_LAUNCH(true, true, true, 1); else FWX_LAUNCH(true, true, false, 1);
     } else if (hn) {

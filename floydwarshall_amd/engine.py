@@ -28,6 +28,29 @@ def device_count():
     return lib().fwx_device_count()
 
 
+# Launch forms the test hook fwx_test_kernel_forms records, in bit order (FWX_KERNEL_FORM_LIST in
+# csrc/fwx_kernels.h): bit i of the mask is KERNEL_FORMS[i].
+KERNEL_FORMS = (
+    "SMALL_SOLVE", "RELAX_K",
+    "ROWPANEL_F32", "ROWPANEL_F64", "COLPANEL_F32", "COLPANEL_F64",
+    "PANELS_F32", "PANELS_F64", "PANELS_MAX_F32", "PANELS_MAX_F64",
+    "PANELS_NEXT_F32", "PANELS_NEXT_TRACE_F32", "PANELS_NEXT_F32_R32",
+    "MAIN_SMALL_F32", "MAIN_LARGE_F32", "MAIN_SMALL_F64", "MAIN_LARGE_F64",
+    "MAX_SMALL_F32", "MAX_MID_F32", "MAX_LARGE_F32",
+    "ARG_RI4_NP1_F32", "ARG_RI4_NP2_F32", "ARG_RI8_NP1_F32", "ARG_RI8_NP2_F32",
+    "MAX_SMALL_F64", "MAX_LARGE_F64",
+    "ARG_F64_RI4_NP1", "ARG_F64_RI4_NP2", "ARG_F64_RI2_NP1", "ARG_F64_RI2_NP2",
+)
+
+
+def kernel_forms_seen(reset=False):
+    """Names of the launch forms this process has used since the last reset (test hook)."""
+    seen = ctypes.c_uint64(0)
+    count = lib().fwx_test_kernel_forms(ctypes.byref(seen), 1 if reset else 0)
+    assert count == len(KERNEL_FORMS), (count, len(KERNEL_FORMS))
+    return {name for i, name in enumerate(KERNEL_FORMS) if seen.value >> i & 1}
+
+
 def _np_ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 

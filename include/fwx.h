@@ -123,6 +123,12 @@ int fwx_hip_versions(int32_t *built_against, int32_t *runtime);
  * internal allocation point reached by later calls on this thread throws std::bad_alloc, which the
  * boundary must turn into FWX_ERR_OOM with nothing leaked.  0 disarms.  Not for production use.     */
 int fwx_test_fail_after(int32_t countdown);
+/* TEST HOOK for dispatch coverage: every kernel launch of the solvers ORs a bit for its form (kernel and
+ * the instantiation a size threshold picks) into one process-wide word.  Stores that word into *seen
+ * (if not NULL) and clears it if reset; returns the number of forms.  fwx_test_kernel_form_name gives
+ * the name of bit `form`, NULL past the last.  Not for production use.                                */
+int fwx_test_kernel_forms(uint64_t *seen, int reset);
+const char *fwx_test_kernel_form_name(int form);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).

@@ -145,45 +145,53 @@ def config5_solve_with_oracle_slices(dm, n, threads=None):
     """Solves the matrix uploaded into the handle `dm` (rate + next + hops) over all n pivots, and pins
     three 256-pivot stretches to the oracle: the first pivots (from the input itself), a stretch across the
     middle of the matrix (pivot 16384 = a partition boundary at P = 8; the stretch starts 128 before it, so
-    a 128-pivot launch ends exactly there) and the last 256 pivots (ending at the solved matrix).  Every
-    stretch is a pivot range of its own on the GPU -- four full blocks: two 128-pivot launches of the double
-    pass, panels across a launch boundary -- and is continued on the oracle (rate + next + hops; the loop tiled
-    over 16 pivots, oracle.relax_mt_tiled, which tests/test_oracle_golden.py pins to the plain loop: the plain
-    loop streams 12 GiB through host memory per pivot) from the state the GPU held before it.  Returns the solved (rate, next, hops).
+    a 128-pivot launch ends exactly there) and the last 256 pivots (ending at the solved matrix).  See
+    solve_with_oracle_stretches.  Two tests (the plain handle, P = 8 partitions) walk the same input through
+    the same stretches: the second only has to reach the states the first verified (their digests)."""
+    return solve_with_oracle_stretches(dm, n, CONFIG5_SLICES, threads, cache=_CONFIG5_ORACLE)
 
-    Two tests (the plain handle, P = 8 partitions) walk the same input through the same stretches.  The
-    first to run does the above and records the digests of the oracle's state after each stretch; the
-    second only has to reach THOSE states: equal digests after a stretch mean its matrix equals one the
-    oracle produced from a verified predecessor -- no second oracle run, no download before the stretch.
-    The oracle runs on a thread of its own (ctypes releases the GIL) while the GPU solves the stretch and the
-    result comes back over PCIe."""
+
+def solve_with_oracle_stretches(dm, n, stretches, threads=None, cache=None):
+    """Solves the matrix uploaded into the handle `dm` over all n pivots and pins the pivot `stretches`
+    ((a, b) pairs, ascending, the last ending at n) to the oracle.  Every stretch is a pivot range of its own
+    on the GPU and is continued on the oracle (the fields the handle carries: rate, + next, + hops; the loop
+    tiled over 16 pivots, oracle.relax_mt_tiled, which tests/test_oracle_golden.py pins to the plain loop)
+    from the state the GPU held before it.  Returns the solved (rate, next, hops), None for a field the
+    handle does not carry.
+
+    cache: a dict shared by tests that walk the same input through the same stretches.  The first to run
+    records the digests of the oracle's state after each stretch; a later one only has to reach THOSE states:
+    equal digests after a stretch mean its matrix equals one the oracle produced from a verified predecessor
+    -- no second oracle run, no download before the stretch.  The oracle runs on a thread of its own (ctypes
+    releases the GIL) while the GPU solves the stretch and the result comes back over PCIe."""
     import threading
     import oracle
     pos = 0
-    for a, b in CONFIG5_SLICES:
+    for a, b in stretches:
         if a > pos:
             dm.solve(k_begin=pos, k_end=a)
-        cached = _CONFIG5_ORACLE.get((n, a, b))
+        cached = cache.get((n, a, b)) if cache is not None else None
         if cached is None:
             er, en, eh = dm.download()
             t = threading.Thread(target=oracle.relax_mt_tiled, args=(er, en, a, b),
                                  kwargs={"threads": threads, "hops": eh, "tile": 16})
             t.start()                                # the oracle continues from the GPU state, beside the GPU
         dm.solve(k_begin=a, k_end=b)
-        gr, gn, gh = dm.download()
+        got = dm.download()
         if cached is None:
             t.join()
-            assert_bits_equal(gr, er, "rate after pivots [%d, %d)" % (a, b))
-            assert_bits_equal(gn, en, "next after pivots [%d, %d)" % (a, b))
-            assert_bits_equal(gh, eh, "hops after pivots [%d, %d)" % (a, b))
-            _CONFIG5_ORACLE[(n, a, b)] = (digest(er), digest(en), digest(eh))
+            for g, e, what in zip(got, (er, en, eh), ("rate", "next", "hops")):
+                if e is not None:
+                    assert_bits_equal(g, e, "%s after pivots [%d, %d)" % (what, a, b))
+            if cache is not None:
+                cache[(n, a, b)] = tuple(digest(e) for e in (er, en, eh) if e is not None)
             del er, en, eh
         else:
-            assert (digest(gr), digest(gn), digest(gh)) == cached, \
+            assert tuple(digest(g) for g in got if g is not None) == cached, \
                 "state after pivots [%d, %d) differs from the oracle's continuation" % (a, b)
         pos = b
     assert pos == n
-    return gr, gn, gh
+    return got
 
 
 _CONFIG5_ORACLE = {}     # (n, a, b) -> digests (rate, next, hops) of the oracle's state after the stretch

@@ -83,6 +83,25 @@ def test_exception_barrier_without_a_device():
         s.close()
 
 
+def test_kernel_form_table_matches_the_library():
+    """engine.KERNEL_FORMS names the bits of fwx_test_kernel_forms in the library's order, all of them."""
+    L = _lib.lib()
+    count = L.fwx_test_kernel_forms(None, 0)
+    assert 0 < count <= 64
+    names = tuple(L.fwx_test_kernel_form_name(i).decode() for i in range(count))
+    assert names == engine.KERNEL_FORMS
+    assert L.fwx_test_kernel_form_name(count) is None and L.fwx_test_kernel_form_name(-1) is None
+
+
+def test_kernel_form_hook_reads_and_resets_without_a_device():
+    """No launch is made here, so whatever the record holds, a reset empties it."""
+    engine.kernel_forms_seen(reset=True)
+    assert engine.kernel_forms_seen() == set()
+    seen = ctypes.c_uint64(1)
+    assert _lib.lib().fwx_test_kernel_forms(ctypes.byref(seen), 1) == len(engine.KERNEL_FORMS)
+    assert seen.value == 0
+
+
 def test_follow_path_host_side():
     nxt = np.array([[-1, 1, 1], [2, -1, 2], [0, 0, -1]], dtype=np.int32)
     assert engine.follow_path(nxt, 0, 2) == [1, 2]
