@@ -502,10 +502,12 @@ int solve_host(int32_t n, T *rate, int32_t *next, int32_t *hops, const fwx_opts 
         if (rc) return rc;
     } else {
         // per-k engine; pitch nd (a matrix padded for the fused engine but found outside its domain)
+        void *ws = nullptr;      // snapshot panels of the multi-pivot schedule (rates only): the context's
+        if (!dn && !dh && (rc = cx.reserve(CallCtx::WS, perk_kt_ws_bytes<T>(nd), &ws))) return rc;
         rc = relax_range<T>(dr, dn, dh, nd, nd, 0, dr + (size_t)op.k_begin * nd,
                             dh ? dh + (size_t)op.k_begin * nd : nullptr, nd, op.k_begin, op.k_end,
                             op.serpentine, upd, s, fwx::PathLog(), 0, 0,
-                            dn ? dn + (size_t)op.k_begin * nd : nullptr);
+                            dn ? dn + (size_t)op.k_begin * nd : nullptr, ws);
         if (rc) return rc;
     }
 
@@ -920,6 +922,16 @@ int fwx_test_kernel_forms(uint64_t *seen, int reset)
                             : fwx::g_kernel_forms.load(std::memory_order_relaxed);
     else if (reset) fwx::g_kernel_forms.store(0, std::memory_order_relaxed);
     return fwx::KF_COUNT;
+}
+
+int fwx_test_perk_pivots(uint64_t *launches, int reset)
+{
+    for (int i = 0; i < 5; ++i) {
+        const uint64_t v = reset ? g_perk_launches[i].exchange(0, std::memory_order_relaxed)
+                                 : g_perk_launches[i].load(std::memory_order_relaxed);
+        if (launches) launches[i] = v;
+    }
+    return perk_pivots();
 }
 
 const char *fwx_test_kernel_form_name(int form)

@@ -451,13 +451,160 @@ inline int perk_store_bytes()
     return FWX_PERK_STORE_BYTES_DEFAULT;
 }
 
-// One launch per pivot over a slab; pivot rows from `prow0 + (k-k_begin)*stride`.
+// Pivots per streaming pass of the per-k engine's rates-only whole-matrix solves (relax_kt):
+// FWX_PERK_PIVOTS=<1|2|4|8> overrides FWX_PERK_PIVOTS_DEFAULT, read on every call; any other value: the
+// default.  1 = one relax_k launch per pivot, launch for launch the engine before relax_kt existed.  No
+// result bit depends on it.
+#define FWX_PERK_PIVOTS_DEFAULT 8
+inline int perk_pivots()
+{
+    if (const char *e = getenv("FWX_PERK_PIVOTS")) {
+        char *end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end != e && *end == '\0' && (v == 1 || v == 2 || v == 4 || v == 8)) return (int)v;
+    }
+    return FWX_PERK_PIVOTS_DEFAULT;
+}
+
+// Launches of the multi-pivot schedule by pivots per launch: [0] relax_k (ragged single pivots), [1] / [2] /
+// [3] relax_kt with 2 / 4 / 8, [4] panel launches.  Test hook fwx_test_perk_pivots (fwx.h); relaxed host atomics.
+inline std::atomic<uint64_t> g_perk_launches[5];
+
+// Snapshot panels (W and Ct of one 64-pivot block) of the multi-pivot schedule: perk_kt_ws_bytes.  A blocking
+// entry point that holds a per-call context passes that context's workspace.  fwx_dev_relax* has no workspace
+// argument and returns with its launches queued, so there the panels live in a process-wide pool keyed by the
+// stream (whose device is taken from the stream, not from the caller's current device): launches that read a
+// buffer and the panel launch that next rewrites it are then always on ONE stream, in order, and two
+// streams never share a buffer.  A buffer is allocated by the first call on its stream and kept; only a call
+// that needs a larger one than its stream has waits for that stream, frees and allocates again.  The pool
+// keeps at most kMax buffers: one more evicts the least recently used with hipFree, which waits for the
+// device and so for any launch that may still read it, whether or not its stream still exists.  The pool
+// mutex is held across those (rare) allocations.  Nothing is synchronised on the way out.
+template <typename T> inline size_t perk_kt_ws_bytes(int n)
+{
+    const size_t ld = ((size_t)n + 3) & ~(size_t)3;
+    return (size_t)FWX_FUSED_B * ((size_t)n + ld) * sizeof(T);
+}
+class PerkScratch {
+public:
+    static int get(hipStream_t s, size_t bytes, void **out)
+    {
+        int dev = 0, cur = 0;
+        FWX_HIP(hipGetDevice(&cur));
+        dev = cur;
+        if (s) FWX_HIP(hipStreamGetDevice(s, &dev));
+        Pool &p = pool();
+        std::lock_guard<std::mutex> lk(p.mu);
+        Entry *e = nullptr;
+        for (Entry &x : p.all)
+            if (x.s == s && x.dev == dev) { e = &x; break; }
+        if (!e) {
+            if (p.all.size() >= kMax) {            // evict the least recently used
+                size_t lru = 0;
+                for (size_t i = 1; i < p.all.size(); ++i)
+                    if (p.all[i].used < p.all[lru].used) lru = i;
+                if (p.all[lru].p) (void)hipFree(p.all[lru].p);
+                p.all.erase(p.all.begin() + (long)lru);
+            }
+            p.all.push_back(Entry{dev, s, nullptr, 0, 0});
+            e = &p.all.back();
+        }
+        e->used = ++p.clock;
+        if (e->cap < bytes) {
+            if (e->p) {
+                if (s) (void)hipStreamSynchronize(s);   // its readers are queued on this stream and nowhere else
+                (void)hipFree(e->p);
+                e->p = nullptr; e->cap = 0;
+            }
+            if (dev != cur) FWX_HIP(hipSetDevice(dev));
+            const hipError_t err = hipMalloc(&e->p, bytes);
+            if (dev != cur) (void)hipSetDevice(cur);
+            FWX_HIP(err);
+            e->cap = bytes;
+        }
+        *out = e->p;
+        return FWX_OK;
+    }
+
+private:
+    static constexpr size_t kMax = 16;
+    struct Entry { int dev; hipStream_t s; void *p; size_t cap; uint64_t used; };
+    struct Pool { std::mutex mu; std::vector<Entry> all; uint64_t clock = 0; };
+    static Pool &pool() { static Pool *p = new Pool(); return *p; }   // leaked on purpose
+};
+
+// The multi-pivot schedule of relax_range (below) for a rates-only solve of the whole matrix in place.  Per
+// block of <= 64 pivots: ONE panel launch (fused_panels, compare form: W and Ct of the block from the
+// time-k0 matrix, which it does not modify), then the block's pivots `np` at a time, one relax_kt launch
+// each, all on `s`.  A ragged end of a block goes down the powers of two; a last single pivot is a relax_k
+// launch on the live row -- exact, because between launches the matrix is a consistent time-k state.
+template <typename T>
+inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine, int np,
+                          unsigned long long *d_updates, hipStream_t s, void *ws)
+{
+    const size_t ld = ((size_t)n + 3) & ~(size_t)3;
+    if (!ws) {
+        const int rc0 = PerkScratch::get(s, perk_kt_ws_bytes<T>(n), &ws);
+        if (rc0) return rc0;
+    }
+    T *const w = (T *)ws, *const ct = w + (size_t)FWX_FUSED_B * n;
+
+    fwx::FusedArgs<T> pa;
+    pa.rate = rate; pa.next = nullptr; pa.rows = n; pa.n = n; pa.row0 = 0; pa.w = nullptr; pa.ct = ct;
+    pa.cnt = nullptr; pa.ct_ld = (int)ld; pa.updates = nullptr; pa.nonneg = false;
+    fwx::RelaxKtArgs<T> a;
+    a.rate = rate; a.ct_ld = (int)ld; a.n = n; a.updates = d_updates;
+    a.temporal_bytes = perk_temporal_bytes((size_t)n * n * sizeof(T));
+    a.store_bytes = perk_store_bytes();
+    fwx::RelaxArgs<T> a1;
+    a1.rate = rate; a1.next = nullptr; a1.hops = nullptr; a1.phops = nullptr; a1.rows = n; a1.n = n; a1.row0 = 0;
+    a1.updates = d_updates; a1.temporal_bytes = a.temporal_bytes; a1.store_bytes = a.store_bytes;
+    const int rev = FWX_XCD_SERPENTINE && a.temporal_bytes >= 0 ? 2 : 1;
+    Throttle thr;
+    int sweeps = 0;                                // launches alternate direction, whatever their width
+    auto after = [&](hipError_t e, int slot) -> int {
+        if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
+        FWX_HIP(e);
+        g_perk_launches[slot].fetch_add(1, std::memory_order_relaxed);
+        return thr.tick(s);
+    };
+    for (int k0 = k_begin; k0 < k_end; k0 += FWX_FUSED_B) {
+        const int bt = std::min(FWX_FUSED_B, k_end - k0);
+        int t = 0;
+        if (bt >= 2) {
+            pa.k0 = k0; pa.bt = bt;
+            if (const int rc = after(fwx::launch_fused_panels<T>(pa, w, nullptr, s), 4)) return rc;
+            for (int g = np; g >= 2; g >>= 1)
+                for (; bt - t >= g; t += g) {
+                    a.k = k0 + t; a.np = g; a.w = w + (size_t)t * n; a.ct = ct + (size_t)t * ld;
+                    a.flip = serpentine ? rev * (sweeps++ & 1) : 0;
+                    if (const int rc = after(fwx::launch_relax_kt<T>(a, s), g == 8 ? 3 : g == 4 ? 2 : 1)) return rc;
+                }
+        }
+        for (; t < bt; ++t) {
+            a1.k = k0 + t; a1.prow = rate + (size_t)a1.k * n;
+            a1.flip = serpentine ? rev * (sweeps++ & 1) : 0;
+            if (const int rc = after(fwx::launch_relax<T>(a1, s), 0)) return rc;
+        }
+    }
+    return FWX_OK;
+}
+
+// One launch per pivot over a slab; pivot rows from `prow0 + (k-k_begin)*stride`.  A rates-only call on
+// the whole matrix in place with the pivots its own rows takes relax_range_kt instead: FWX_PERK_PIVOTS
+// pivots per launch; kt_ws: perk_kt_ws_bytes of device scratch for it that the caller keeps until the launches
+// have run, or null: the stream's buffer of PerkScratch.
 template <typename T>
 inline int relax_range(T *rate, int32_t *next, int32_t *hops, int rows, int n, int row0, const T *prow0,
                 const int32_t *phops0, int64_t stride, int k_begin, int k_end, int serpentine,
                 unsigned long long *d_updates, hipStream_t s, fwx::PathLog plog = fwx::PathLog(),
-                int skip_lo = 0, int skip_hi = 0, const int32_t *pnext0 = nullptr)
+                int skip_lo = 0, int skip_hi = 0, const int32_t *pnext0 = nullptr, void *kt_ws = nullptr)
 {
+    const int np = perk_pivots();
+    if (np > 1 && !next && !hops && !plog.last && row0 == 0 && rows == n && skip_hi <= skip_lo &&
+        n % (16 / (int)sizeof(T)) == 0 && (uintptr_t)rate % 16 == 0 && stride == n &&
+        prow0 == rate + (size_t)k_begin * n && k_end - k_begin >= 2)
+        return relax_range_kt<T>(rate, n, k_begin, k_end, serpentine, np, d_updates, s, kt_ws);
     fwx::RelaxArgs<T> a;
     Throttle thr;
     a.rate = rate; a.next = next; a.hops = hops;

@@ -109,6 +109,23 @@ template <typename T> struct RelaxArgs {
 
 template <typename T> hipError_t launch_relax(const RelaxArgs<T> &a, hipStream_t s);
 
+// relax_kt: pivots [k, k+np) on the whole n x n matrix in one streaming pass, rates only, operands from
+// the snapshot panels of launch_fused_panels (compare form).  n must be a multiple of 16 bytes of
+// elements, rate and w 16-byte aligned.
+#define FWX_PERK_KT_RPB 8          // rows per workgroup and loads in flight per thread: 8 x 8 is 8-10 % faster per
+#define FWX_PERK_KT_UNROLL 8       //   pivot than relax_k's 4 x 4 at NP = 8 (profiles/r07_tune_relax_pivots.txt)
+template <typename T> struct RelaxKtArgs {
+    T *rate;                       // n x n
+    const T *w;                    // w[t*n + j]      = row k+t at time k+t          (t < np)
+    const T *ct;                   // ct[t*ct_ld + i] = column k+t at time k+t, NaN at i == k+t
+    int ct_ld, n, k, np;           // np: 2, 4 or 8
+    int flip;                      // as RelaxArgs
+    long long temporal_bytes = -1;
+    int store_bytes = 0;
+    unsigned long long *updates = nullptr;   // FWX_UPDATE_SHARDS_K counters or nullptr
+};
+template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s);
+
 // Whole solve (pivots [k_begin,k_end)) of an n <= FWX_SMALL_N matrix in one single-workgroup launch.
 #define FWX_SMALL_N 128
 template <typename T>

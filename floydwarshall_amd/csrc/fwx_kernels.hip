@@ -6,6 +6,8 @@
 // predicated stores.  No MFMA: (max, x) with a strict compare is not a dense contraction.
 //
 // Kernel 1  relax_k      one launch per pivot k over a slab of rows (HBM-bound streaming read)
+//           relax_kt     2, 4 or 8 neighbouring pivots per launch from time-k snapshots (rates only, whole
+//                        matrix in place): the same stream, read once per launch instead of once per pivot
 // Kernel 2  snapshot_row copies pivot row k into the snapshot panel (panel phase, multi-GPU)
 //
 // Exactness rules shared by every kernel:
@@ -306,6 +308,126 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
 }
 
 // -------------------------------------------------------------------------------------------------
+// relax_kt: steps k .. k+NP-1 of runAlgo on the whole matrix in ONE streaming pass (rates only).
+//
+// An entry may take several pivots in one visit if each pivot's operands are the snapshots of its row
+// and column taken at its own time.  Those come from the panel kernels of the
+// fused engine (fwx_fused.hip): w[t][j] = row k+t at time k+t, ct[t][i] = column k+t at time k+t with
+// NaN at i == k+t.  The launch reads NOTHING of the live matrix but r[i][j] itself -- rows and columns
+// k .. k+NP-1 are rewritten by their owners during the launch and are no operands here (DESIGN.md
+// section 3, consequence (2)) -- so it is race-free, and the exact write-back of unchanged lanes holds
+// as in relax_k: every element belongs to exactly one lane and nobody else reads or writes it.
+//
+// Shaped like relax_k: 256 threads with one 16-byte vector each, RPB rows per workgroup, UNROLL rows of
+// unconditional loads in flight, the same visit_tile mapping, `nt_below` split and GL-lane group store.
+// A thread keeps its slice of the NP pivot rows in registers (NaN at column k+t: skip j == k; NaN in
+// clamped lanes), the workgroup stages ct[t][rows] in LDS (contiguous reads of the panel: no strided
+// gather).  Each loaded vector is folded through t = 0 .. NP-1 in ascending order with
+//   x = (x < c && j != i) ? c : x,   c = ct[t][i] * w[t][j]
+// -- one IEEE multiply, the strict ordered compare, never `max`: no domain assumption enters the per-k
+// engine -- and a group stores once if any of its lanes ended different from what it loaded.  U counts
+// every improvement of every fold step, which is what NP launches of relax_k count.
+// -------------------------------------------------------------------------------------------------
+template <typename T, int W, int RPB, int UNROLL, bool COUNT, int GL, int NP>
+__global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct, int ct_ld, int n, int k,
+                                                int nstrips, int flip, unsigned long long *updates,
+                                                int nt_below)
+{
+    using L = Lanes<T, W>;
+    using V = typename L::V;
+    constexpr int SW = 256 * W;
+    static_assert(GL == 1 || GL == 2 || GL == 4 || GL == 8, "store group: 1, 2, 4 or 8 lanes");
+    static_assert(NP * RPB <= 256, "one thread per staged pivot-column value");
+
+    __shared__ T s_ct[NP][RPB];
+    __shared__ unsigned int s_cnt;
+
+    const int t = threadIdx.x;
+    const int bid = visit_tile(flip);
+    const int strip = bid % nstrips;
+    const int chunk = bid / nstrips;
+    const int r_begin = chunk * RPB;
+    const int r_cnt = min(RPB, n - r_begin);
+
+    // Pivot columns -> LDS from the panel (row k+t of it already holds NaN: skip i == k).
+    if (t < NP * RPB) {
+        const int tt = t / RPB, r = t % RPB;
+        if (r < r_cnt) s_ct[tt][r] = ct[(size_t)tt * ct_ld + r_begin + r];
+    }
+    if (COUNT && t == 0) s_cnt = 0;
+
+    // Pivot row segments -> registers, clamped past the end of the row as in relax_k.
+    const int c0 = strip * SW + t * W;
+    const bool own = c0 < n;                  // false: a clamped lane (never stores)
+    const int col = own ? c0 : n - W;
+    V p[NP];
+#pragma unroll
+    for (int tt = 0; tt < NP; ++tt) {
+        if (own) {
+            p[tt] = *reinterpret_cast<const V *>(w + (size_t)tt * n + c0);
+#pragma unroll
+            for (int c = 0; c < W; ++c)
+                if (c0 + c == k + tt) L::set(p[tt], c, quiet_nan<T>());
+        } else {
+            p[tt] = L::splat(quiet_nan<T>());
+        }
+    }
+    __syncthreads();
+
+    unsigned int my_updates = 0;
+    T *const base = rate + (size_t)r_begin * n + col;
+    const int g0 = (int)(__lane_id() & ~(GL - 1));   // first lane of my store group
+
+    // One row of one vector through the NP pivots; all lanes of the wave are active (r is uniform).
+    auto relax_vec = [&](const V &x, int r) {
+        const int i = r_begin + r;
+        V nx = x;
+        bool changed = false;
+#pragma unroll
+        for (int tt = 0; tt < NP; ++tt) {
+            const T cik = s_ct[tt][r];
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                const T cand = cik * L::get(p[tt], c);
+                const bool up = L::get(nx, c) < cand && col + c != i;
+                L::set(nx, c, up ? cand : L::get(nx, c));
+                changed |= up;
+                if (COUNT) my_updates += up;
+            }
+        }
+        bool st = changed;
+        if constexpr (GL > 1) {
+            const unsigned long long m = __ballot(changed);
+            st = own && ((m >> g0) & ((1ull << GL) - 1)) != 0;
+        }
+        if (st) *reinterpret_cast<V *>(base + (size_t)r * n) = nx;
+    };
+
+    auto stream = [&](auto nt) {
+        constexpr bool NT = decltype(nt)::value;
+        int r = 0;
+        for (; r + UNROLL <= r_cnt; r += UNROLL) {
+            V x[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) x[u] = load_vec<V, NT>(base + (size_t)(r + u) * n);
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) relax_vec(x[u], r + u);
+        }
+        for (; r < r_cnt; ++r) relax_vec(load_vec<V, NT>(base + (size_t)r * n), r);
+    };
+    // workgroup-uniform: one of the two instantiations, never both
+    if (bid < nt_below) stream(std::true_type());
+    else stream(std::false_type());
+
+    if (COUNT) {
+        if (my_updates) atomicAdd(&s_cnt, my_updates);
+        __syncthreads();
+        if (t == 0 && s_cnt)
+            atomicAdd(&updates[bid & (FWX_UPDATE_SHARDS_K - 1)], (unsigned long long)s_cnt);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // small_solve: the whole of runAlgo for n <= 128 in ONE launch of one workgroup -- the reference's
 // own regime (its tests stop at 4 x 4, src/test/AlgorithmsTest.hs:66-77; the README session has 4
 // vertices; a market of 10 exchanges x 12 currencies has 120).  The matrix is padded with NaN to
@@ -564,6 +686,62 @@ template <typename T> hipError_t launch_relax(const RelaxArgs<T> &a, hipStream_t
 
 template hipError_t launch_relax<float>(const RelaxArgs<float> &, hipStream_t);
 template hipError_t launch_relax<double>(const RelaxArgs<double> &, hipStream_t);
+
+// relax_kt with the geometry (RPB, UNROLL); the tile order, the cache-policy split and the store group
+// are chosen exactly as launch_relax_cfg chooses them for relax_k.
+template <typename T, int RPB, int UNROLL>
+static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
+{
+    constexpr int W = 16 / (int)sizeof(T), SW = 256 * W;
+    if (a.n <= 0) return hipSuccess;
+    if (a.n % W || (uintptr_t)a.rate % 16 || (uintptr_t)a.w % 16 || a.ct_ld < a.n || a.k < 0 ||
+        a.k + a.np > a.n || (a.np != 2 && a.np != 4 && a.np != 8))
+        return hipErrorInvalidValue;
+    const int nstrips = (a.n + SW - 1) / SW;
+    const int nchunks = (a.n + RPB - 1) / RPB;
+    const dim3 grid((unsigned)(nstrips * nchunks)), block(256);
+    const int flip = a.flip == 2 && grid.x % 8 ? 1 : a.flip;
+    int nt_below = 0;
+    const double slab = (double)a.n * a.n * sizeof(T);
+    if (a.temporal_bytes >= 0 && slab > (double)a.temporal_bytes) {
+        const double tail = std::ceil((double)a.temporal_bytes / slab * grid.x);
+        nt_below = (int)grid.x - (int)std::min(tail, (double)grid.x);
+    }
+    const int sb = a.store_bytes > 0 ? a.store_bytes : FWX_PERK_STORE_BYTES_DEFAULT;
+    const int gl = sb >= 128 ? 8 : sb >= 64 ? 4 : sb >= 32 ? 2 : 1;
+#define FWX_LAUNCH_KT(CN, GL, NP)                                                                  \
+    hipLaunchKernelGGL((relax_kt<T, W, RPB, UNROLL, CN, GL, NP>), grid, block, 0, s, a.rate, a.w, a.ct, \
+                       a.ct_ld, a.n, a.k, nstrips, flip, a.updates, nt_below)
+#define FWX_LAUNCH_KT_NP(CN, GL)                                                                   \
+    do {                                                                                           \
+        if (a.np == 8) FWX_LAUNCH_KT(CN, GL, 8);                                                   \
+        else if (a.np == 4) FWX_LAUNCH_KT(CN, GL, 4);                                              \
+        else FWX_LAUNCH_KT(CN, GL, 2);                                                             \
+    } while (0)
+#define FWX_LAUNCH_KT_GL(CN)                                                                       \
+    do {                                                                                           \
+        if (gl == 8) FWX_LAUNCH_KT_NP(CN, 8);                                                      \
+        else if (gl == 4) FWX_LAUNCH_KT_NP(CN, 4);                                                 \
+        else if (gl == 2) FWX_LAUNCH_KT_NP(CN, 2);                                                 \
+        else FWX_LAUNCH_KT_NP(CN, 1);                                                              \
+    } while (0)
+    // The form RELAX_K stands for the per-k engine, whichever of its two kernels sweeps: relax_kt has no
+    // bit of its own, its launches are counted by width instead (fwx_test_perk_pivots).
+    note_form(KF_RELAX_K);
+    if (a.updates) FWX_LAUNCH_KT_GL(true); else FWX_LAUNCH_KT_GL(false);
+#undef FWX_LAUNCH_KT_GL
+#undef FWX_LAUNCH_KT_NP
+#undef FWX_LAUNCH_KT
+    return hipGetLastError();
+}
+
+template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s)
+{
+    return launch_relax_kt_cfg<T, FWX_PERK_KT_RPB, FWX_PERK_KT_UNROLL>(a, s);
+}
+
+template hipError_t launch_relax_kt<float>(const RelaxKtArgs<float> &, hipStream_t);
+template hipError_t launch_relax_kt<double>(const RelaxKtArgs<double> &, hipStream_t);
 
 template <typename T>
 hipError_t launch_snapshot_row(T *dst, const T *src, int32_t *hdst, const int32_t *hsrc, int n,

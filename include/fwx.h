@@ -129,6 +129,11 @@ int fwx_test_fail_after(int32_t countdown);
  * the name of bit `form`, NULL past the last.  Not for production use.                                */
 int fwx_test_kernel_forms(uint64_t *seen, int reset);
 const char *fwx_test_kernel_form_name(int form);
+/* TEST HOOK for the per-k engine's multi-pivot schedule: returns what FWX_PERK_PIVOTS parses to right now
+ * (1, 2, 4 or 8; the default on anything else).  launches (if not NULL) receives five counters of the
+ * launches that schedule has made in this process -- single-pivot, 2-, 4- and 8-pivot sweeps, panel
+ * launches -- which are cleared if reset.  Needs no device.  Not for production use.                  */
+int fwx_test_perk_pivots(uint64_t *launches, int reset);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).
@@ -392,7 +397,20 @@ typedef struct fwx_pivots {
                          /* domain (see "Domain"), where that case cannot arise                        */
 } fwx_pivots;
 
-/* Apply pivots [k_begin,k_end) in order to every row of the slab (one launch per pivot).
+/* Apply pivots [k_begin,k_end) in order to every row of the slab, asynchronously on `stream`.
+ * In general one launch per pivot, each reading the slab once.  A rates-only call (no next, no hops) on
+ * the WHOLE matrix in place -- row0 = 0, rows = n, the pivots its own rows (piv->rate = rate +
+ * k_begin*n, stride n), n a multiple of 16 bytes of elements, rate 16-byte aligned, no skip range --
+ * applies FWX_PERK_PIVOTS pivots per launch instead (environment, 1 | 2 | 4 | 8, read per call, default
+ * 8; 1 = one launch per pivot): per block of 64 pivots one panel launch takes the time-k snapshots of
+ * the block's rows and columns, then every launch folds 2, 4 or 8 neighbouring pivots from those
+ * snapshots into each entry it streams, so the matrix is read once per launch, not once per pivot.
+ * The result is bit for bit the same.  The snapshots live in library-owned device scratch on the stream's
+ * device, one buffer of 128 * n elements per stream (at most 16 are kept, the least recently used goes):
+ * the FIRST such call on a stream calls hipMalloc, and a call with a larger n than the stream has seen
+ * waits for the stream before it frees and allocates again -- so such a call cannot be captured into a
+ * graph; set FWX_PERK_PIVOTS=1 for that.  Every later call allocates nothing, synchronises nothing and
+ * returns with its launches queued.
  * d_updates: optional device array of FWX_UPDATE_SHARDS uint64 counters, incremented by U.      */
 #define FWX_UPDATE_SHARDS 256
 int fwx_dev_relax(const fwx_slab *slab, const fwx_pivots *piv, int32_t serpentine,

@@ -197,6 +197,133 @@ static int stores_sweep(float *d, int n, int per, int rounds)
     return 0;
 }
 
+// `pivots` mode: the multi-pivot schedule of the per-k engine (relax_range_kt in fwx_internal.h).  For NP = 1
+// (relax_k, one launch per pivot) and NP = 2, 4, 8 (relax_kt, geometries RPB x UNROLL) a window of `per`
+// pivots -- from k = 0, 4096 and 12000, each started from a copy of the matrix state at its first pivot -- is
+// issued as production issues it: per 64 pivots one fused_panels launch, then 64 / NP sweeps, serpentine in
+// groups of 8, the default temporal tail.  Reported per window: us per pivot over the whole window (panel
+// launches included) and us per sweep launch (the window minus its panel launches, which are timed on
+// their own, back to back on an otherwise idle chip, and reported separately).
+//   tune_relax 16384 0 256 3 pivots
+struct KtCfg { const char *name; int np; hipError_t (*fn)(const fwx::RelaxKtArgs<float> &, hipStream_t); };
+template <int RPB, int UNROLL>
+static hipError_t run_kt(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
+{
+    return fwx::launch_relax_kt_cfg<float, RPB, UNROLL>(a, s);
+}
+
+static int pivots_sweep(float *d, int n, int per, int rounds)
+{
+    std::vector<KtCfg> vars = {{"NP1 relax_k", 1, nullptr}};
+    for (int np : {2, 4, 8}) {
+        vars.push_back({"RPB4 U4", np, run_kt<4, 4>});
+        vars.push_back({"RPB8 U4", np, run_kt<8, 4>});
+        vars.push_back({"RPB8 U8", np, run_kt<8, 8>});
+        vars.push_back({"RPB16 U8", np, run_kt<16, 8>});
+    }
+    const int k0s[3] = {0, 4096, 12000}, nw = 3, nv = (int)vars.size();
+    if (n % 64 || per % 8) { printf("pivots mode: n must be a multiple of 64 and per of 8\n"); return 1; }
+    const size_t bytes = (size_t)n * n * sizeof(float);
+    float *snap[3], *work, *w, *ct;
+    for (int i = 0; i < nw; ++i) CK(hipMalloc(&snap[i], bytes));
+    CK(hipMalloc(&work, bytes));
+    CK(hipMalloc(&w, (size_t)64 * n * sizeof(float)));
+    CK(hipMalloc(&ct, (size_t)64 * n * sizeof(float)));
+    const long long tail = 256ll << 20;
+    fwx::FusedArgs<float> pa;
+    pa.rate = work; pa.next = nullptr; pa.rows = n; pa.n = n; pa.row0 = 0; pa.w = nullptr; pa.ct = ct;
+    pa.cnt = nullptr; pa.ct_ld = n; pa.updates = nullptr; pa.nonneg = false;
+    fwx::RelaxKtArgs<float> a;
+    a.rate = work; a.ct_ld = n; a.n = n; a.temporal_bytes = tail;
+    fwx::RelaxArgs<float> a1;
+    a1.rate = work; a1.next = nullptr; a1.hops = nullptr; a1.phops = nullptr;
+    a1.rows = n; a1.n = n; a1.row0 = 0; a1.updates = nullptr; a1.temporal_bytes = tail;
+    int sweeps = 0;
+    // pivots [kb, ke) with variant v; returns the number of sweep launches.  Timing only: a 64-block is
+    // rounded DOWN to whole groups of np pivots (production sends a ragged end down the powers of two), so
+    // the window starts and `per` must be multiples of 8 for the states to be the per-k states
+    auto run = [&](const KtCfg &v, int kb, int ke) {
+        int launches = 0;
+        if (v.np == 1) {
+            for (int k = kb; k < ke; ++k, ++launches) {
+                a1.k = k; a1.prow = work + (size_t)k * n; a1.flip = 2 * (k & 1);
+                CK(fwx::launch_relax<float>(a1, 0));
+            }
+            return launches;
+        }
+        for (int k0 = kb; k0 + v.np <= ke; k0 += 64) {
+            const int bt = std::min(64, ke - k0) / v.np * v.np;
+            pa.k0 = k0; pa.bt = bt;
+            CK(fwx::launch_fused_panels<float>(pa, w, nullptr, 0));
+            for (int t = 0; t < bt; t += v.np, ++launches) {
+                a.k = k0 + t; a.np = v.np; a.w = w + (size_t)t * n; a.ct = ct + (size_t)t * n;
+                a.flip = 2 * (sweeps++ & 1);
+                CK(v.fn(a, 0));
+            }
+        }
+        return launches;
+    };
+    // window states: the NP = 8 path from the pristine matrix (bit for bit the per-k states)
+    CK(hipMemcpy(work, d, bytes, hipMemcpyDeviceToDevice));
+    for (int i = 0, k = 0; i < nw; ++i) {
+        if (k0s[i] > k) run(vars[nv - 4], k, std::min(n, k0s[i]));
+        k = std::min(n, k0s[i]);
+        CK(hipMemcpy(snap[i], work, bytes, hipMemcpyDeviceToDevice));
+    }
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    // the panel launch alone, per window state
+    float panel_us[3] = {0, 0, 0};
+    for (int i = 0; i < nw; ++i) {
+        if (k0s[i] + 64 > n) continue;
+        CK(hipMemcpy(work, snap[i], bytes, hipMemcpyDeviceToDevice));
+        pa.k0 = k0s[i]; pa.bt = 64;
+        CK(fwx::launch_fused_panels<float>(pa, w, nullptr, 0));
+        CK(hipEventRecord(e0, 0));
+        for (int r = 0; r < 16; ++r) CK(fwx::launch_fused_panels<float>(pa, w, nullptr, 0));
+        CK(hipEventRecord(e1, 0));
+        CK(hipEventSynchronize(e1));
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+        panel_us[i] = 1e3f * ms / 16;
+    }
+    std::vector<float> best(nv * nw, 1e30f), sum(nv * nw, 0.f);
+    std::vector<int> nl(nv * nw, 0), npv(nv * nw, 0);
+    for (int r = 0; r < rounds; ++r)
+        for (int v = 0; v < nv; ++v)
+            for (int i = 0; i < nw; ++i) {
+                const int kb = k0s[i], ke = std::min(n, k0s[i] + per);
+                if (ke - kb < 8) continue;
+                CK(hipMemcpyAsync(work, snap[i], bytes, hipMemcpyDeviceToDevice, 0));
+                CK(hipEventRecord(e0, 0));
+                nl[v * nw + i] = run(vars[v], kb, ke);
+                CK(hipEventRecord(e1, 0));
+                CK(hipEventSynchronize(e1));
+                float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                npv[v * nw + i] = nl[v * nw + i] * vars[v].np;
+                best[v * nw + i] = std::min(best[v * nw + i], 1e3f * ms);
+                sum[v * nw + i] += 1e3f * ms;
+            }
+    printf("pivots n=%d per=%d rounds=%d  (windows from k = %d, %d, %d; min over rounds, mean in brackets)\n", n, per,
+           rounds, k0s[0], k0s[1], k0s[2]);
+    printf("panel launch alone (fused_panels, compare form, 64 pivots), us: %.1f  %.1f  %.1f\n", panel_us[0],
+           panel_us[1], panel_us[2]);
+    printf("%-4s %-12s", "NP", "geometry");
+    for (int i = 0; i < nw; ++i) printf("  k=%-5d us/pivot  us/sweep launch ", k0s[i]);
+    printf("\n");
+    for (int v = 0; v < nv; ++v) {
+        printf("%-4d %-12s", vars[v].np, vars[v].name);
+        for (int i = 0; i < nw; ++i) {
+            const int x = v * nw + i;
+            if (!nl[x]) { printf("  %-34s", "-"); continue; }
+            const float panels = vars[v].np == 1 ? 0.f : panel_us[i] * ((npv[x] + 63) / 64);
+            printf("  %7.2f (%7.2f)  %7.1f         ", best[x] / npv[x], sum[x] / rounds / npv[x],
+                   (best[x] - panels) / nl[x]);
+        }
+        printf("\n");
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const int n = argc > 1 ? atoi(argv[1]) : 16384;
@@ -221,10 +348,33 @@ int main(int argc, char **argv)
         CK(hipEventRecord(e0, 0));
         const int kmax = argc > 6 ? atoi(argv[6]) : n;      // optional: only the first kmax pivots
         const int sync_every = argc > 7 ? atoi(argv[7]) : 0; // optional: drain the queue regularly
-        for (int k = 0; k < kmax; ++k) {
-            a.k = k; a.prow = d + (size_t)k * n; a.flip = k & 1;
-            CK(fwx::launch_relax<float>(a, 0));
-            if (sync_every && (k + 1) % sync_every == 0) CK(hipDeviceSynchronize());
+        // optional: 2 | 4 | 8 = the multi-pivot schedule.  Timing / traffic only: kmax is rounded down to whole
+        // groups of np pivots per 64-block (production sends a ragged end down the powers of two instead)
+        const int np = argc > 8 ? atoi(argv[8]) : 1;
+        if (np == 2 || np == 4 || np == 8) {
+            float *w, *ct;
+            CK(hipMalloc(&w, (size_t)64 * n * sizeof(float)));
+            CK(hipMalloc(&ct, (size_t)64 * n * sizeof(float)));
+            fwx::FusedArgs<float> pa;
+            pa.rate = d; pa.next = nullptr; pa.rows = n; pa.n = n; pa.row0 = 0; pa.w = nullptr; pa.ct = ct;
+            pa.cnt = nullptr; pa.ct_ld = n; pa.updates = nullptr; pa.nonneg = false;
+            fwx::RelaxKtArgs<float> b;
+            b.rate = d; b.ct_ld = n; b.n = n; b.np = np;
+            for (int k0 = 0, sweeps = 0; k0 + np <= kmax; k0 += 64) {
+                pa.k0 = k0; pa.bt = std::min(64, kmax - k0) / np * np;
+                CK(fwx::launch_fused_panels<float>(pa, w, nullptr, 0));
+                for (int t = 0; t < pa.bt; t += np) {
+                    b.k = k0 + t; b.w = w + (size_t)t * n; b.ct = ct + (size_t)t * n; b.flip = sweeps++ & 1;
+                    CK(fwx::launch_relax_kt<float>(b, 0));
+                    if (sync_every && (k0 + t + np) % sync_every == 0) CK(hipDeviceSynchronize());
+                }
+            }
+        } else {
+            for (int k = 0; k < kmax; ++k) {
+                a.k = k; a.prow = d + (size_t)k * n; a.flip = k & 1;
+                CK(fwx::launch_relax<float>(a, 0));
+                if (sync_every && (k + 1) % sync_every == 0) CK(hipDeviceSynchronize());
+            }
         }
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
@@ -236,6 +386,7 @@ int main(int argc, char **argv)
 
     if (argc > 5 && !strcmp(argv[5], "policy")) return policy_sweep(d, n, warm, per, rounds);
     if (argc > 5 && !strcmp(argv[5], "stores")) return stores_sweep(d, n, per, rounds);
+    if (argc > 5 && !strcmp(argv[5], "pivots")) return pivots_sweep(d, n, per, rounds);
 
     if (argc > 5 && !strcmp(argv[5], "fused")) {
         // PMC probe mode for the fused engine: `passes` passes of 64 pivots (panel, colpanel, main
