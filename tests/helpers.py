@@ -233,3 +233,72 @@ def check_walks_and_exact_lists(rate0, rate, nxt, hops, src, dst, walk_len, walk
         r = float(rate[s_, d_])
         assert abs(p - r) <= (len(path) - 1) * u * 1.001 * r, (s_, d_, p, r, len(path))
     return len(differ)
+
+
+# ---- the per-k engine's multi-pivot schedule (tests/test_gpu_perk_pivots*.py) --------------------------------------
+MIB = float(1 << 20)
+PERK_PIVOTS = [1, 2, 4, 8]
+
+
+def perk_launches(reset=True):
+    """(single-pivot, 2-, 4-, 8-pivot sweeps, panel launches) of the multi-pivot schedule since the last reset."""
+    import ctypes
+    from floydwarshall_amd import _lib
+    c = (ctypes.c_uint64 * 5)()
+    _lib.lib().fwx_test_perk_pivots(c, 1 if reset else 0)
+    return [int(v) for v in c]
+
+
+def perk_expected_launches(kb, ke, np_):
+    """What relax_range_kt issues for pivots [kb, ke): per block of <= 64 pivots from kb one panel launch, the
+    block's pivots np_ at a time, a ragged end down the powers of two, a last single pivot on relax_k."""
+    want = [0, 0, 0, 0, 0]
+    if np_ == 1 or ke - kb < 2:
+        return want
+    for k0 in range(kb, ke, 64):
+        bt = min(64, ke - k0)
+        if bt >= 2:
+            want[4] += 1
+            g = np_
+            while g >= 2:
+                want[{2: 1, 4: 2, 8: 3}[g]] += bt // g
+                bt %= g
+                g //= 2
+        want[0] += bt
+    return want
+
+
+def perk_oracle(rate, kb, ke):
+    """(rates, U) of the C oracle over pivots [kb, ke); the input is left alone."""
+    import oracle
+    er = rate.copy()
+    u = oracle.relax_mt(er, None, kb, ke, threads=16, fast=True)
+    return er, u
+
+
+def perk_relax(rate, kb, ke, serp=True, stream=None):
+    """fwx_dev_relax on the whole matrix in place, counting: (rates, U)."""
+    from floydwarshall_amd import engine
+    n = rate.shape[0]
+    r_t = dev(rate)
+    upd = dev_zeros((engine.FWX_UPDATE_SHARDS,), np.int64)
+    engine.dev_relax(r_t, n, 0, kb, ke, serpentine=serp, updates_t=upd, stream=stream)
+    return host(r_t), int(host(upd).sum())
+
+
+def perk_check(rate, kb, ke, monkeypatch, what, budgets=None, serps=(True, False), pivots=PERK_PIVOTS, want=None):
+    """Rates, U and the launch counters of fwx_dev_relax over pivots [kb, ke) for every width in `pivots`, every
+    temporal budget (default: one that splits the matrix, one that does not) and sweep order.  want: the oracle's
+    (rates, U) where the caller shares them between cases."""
+    want_r, want_u = want if want is not None else perk_oracle(rate, kb, ke)
+    for np_ in pivots:
+        monkeypatch.setenv("FWX_PERK_PIVOTS", str(np_))
+        for budget in budgets or [repr(rate.nbytes / 2 / MIB), "1e12"]:
+            monkeypatch.setenv("FWX_PERK_TEMPORAL_MIB", budget)
+            for serp in serps:
+                perk_launches()
+                got_r, got_u = perk_relax(rate, kb, ke, serp)
+                tag = "%s NP=%d budget=%s serp=%s pivots [%d, %d)" % (what, np_, budget, serp, kb, ke)
+                assert_bits_equal(got_r, want_r, tag)
+                assert got_u == want_u, tag
+                assert perk_launches() == perk_expected_launches(kb, ke, np_), tag

@@ -13,78 +13,19 @@ counts, must equal the C oracle's bit for bit:
   * two solves interleaved on two streams of one process (the snapshot scratch is keyed by stream).
 
 The launch counters of the test hook show that the sweeps really were NP wide."""
-import ctypes
-
 import numpy as np
 import pytest
 
-import oracle
 from floydwarshall_amd import _lib, engine, hip, synth
 
-from helpers import assert_bits_equal, dev, dev_zeros, digest, host, load_golden
+from helpers import (MIB, PERK_PIVOTS as PIVOTS, assert_bits_equal, dev, digest, host, load_golden,
+                     perk_check as _check, perk_expected_launches as _expected_launches, perk_launches as _launches,
+                     perk_oracle as _oracle)
 from hostile_inputs import hostile_matrix
 
 pytestmark = pytest.mark.gpu
 
-MIB = float(1 << 20)
-PIVOTS = [1, 2, 4, 8]
 ORDERS = [260, 324, 452, 1036]
-
-
-def _launches(reset=True):
-    """(single-pivot, 2-, 4-, 8-pivot sweeps, panel launches) of the multi-pivot schedule since the last reset."""
-    c = (ctypes.c_uint64 * 5)()
-    _lib.lib().fwx_test_perk_pivots(c, 1 if reset else 0)
-    return [int(v) for v in c]
-
-
-def _expected_launches(kb, ke, np_):
-    """What relax_range_kt issues for pivots [kb, ke): per block of <= 64 pivots from kb one panel launch, the
-    block's pivots np_ at a time, a ragged end down the powers of two, a last single pivot on relax_k."""
-    want = [0, 0, 0, 0, 0]
-    if np_ == 1 or ke - kb < 2:
-        return want
-    for k0 in range(kb, ke, 64):
-        bt = min(64, ke - k0)
-        if bt >= 2:
-            want[4] += 1
-            g = np_
-            while g >= 2:
-                want[{2: 1, 4: 2, 8: 3}[g]] += bt // g
-                bt %= g
-                g //= 2
-        want[0] += bt
-    return want
-
-
-def _oracle(rate, kb, ke):
-    er = rate.copy()
-    u = oracle.relax_mt(er, None, kb, ke, threads=16, fast=True)
-    return er, u
-
-
-def _relax(rate, kb, ke, serp=True, stream=None):
-    """fwx_dev_relax on the whole matrix in place, counting: (rates, U)."""
-    n = rate.shape[0]
-    r_t = dev(rate)
-    upd = dev_zeros((engine.FWX_UPDATE_SHARDS,), np.int64)
-    engine.dev_relax(r_t, n, 0, kb, ke, serpentine=serp, updates_t=upd, stream=stream)
-    return host(r_t), int(host(upd).sum())
-
-
-def _check(rate, kb, ke, monkeypatch, what, budgets=None, serps=(True, False), pivots=PIVOTS):
-    want_r, want_u = _oracle(rate, kb, ke)
-    for np_ in pivots:
-        monkeypatch.setenv("FWX_PERK_PIVOTS", str(np_))
-        for budget in budgets or [repr(rate.nbytes / 2 / MIB), "1e12"]:
-            monkeypatch.setenv("FWX_PERK_TEMPORAL_MIB", budget)
-            for serp in serps:
-                _launches()
-                got_r, got_u = _relax(rate, kb, ke, serp)
-                tag = "%s NP=%d budget=%s serp=%s pivots [%d, %d)" % (what, np_, budget, serp, kb, ke)
-                assert_bits_equal(got_r, want_r, tag)
-                assert got_u == want_u, tag
-                assert _launches() == _expected_launches(kb, ke, np_), tag
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
