@@ -29,6 +29,7 @@ FWX_F32, FWX_F64 = 0, 1
 FWX_ENGINE_AUTO, FWX_ENGINE_PERK, FWX_ENGINE_FUSED = 0, 1, 2
 FWX_UPDATE_SHARDS = 256
 FWX_FUSED_BLOCK = 64
+FWX_BATCH_MAX_N = 128
 FWX_FLAG_NONNEG = 1
 FWX_XCHG_AUTO, FWX_XCHG_PEER, FWX_XCHG_RCCL = 0, 1, 2
 FWX_XCHG_CALLBACK = 3
@@ -96,6 +97,11 @@ SIGNATURES = {
     "fwx_test_perk_pivots": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "fwx_solve_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
     "fwx_solve_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_batch_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_batch_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_dev_solve_batch": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32,
+                                           c_vp, c_vp]),
+    "fwx_test_batch_wave_max_n": (ctypes.c_int, []),
     "fwx_follow_path": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i32, c_vp, c_i32]),
     "fwx_matrix_create": (ctypes.c_int, [ctypes.POINTER(c_vp), c_i32, c_i32, c_i32, c_i32, c_i32]),
     "fwx_matrix_upload": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),

@@ -526,6 +526,111 @@ int solve_host(int32_t n, T *rate, int32_t *next, int32_t *hops, const fwx_opts 
     return FWX_OK;
 }
 
+// What the batch entry points decide before any device call (fwx.h): the pivot range against n, then the
+// order against FWX_BATCH_MAX_N.  k_end <= 0 means n.
+int batch_range(int32_t n, int32_t k_begin, int32_t &k_end)
+{
+    if (k_end <= 0) k_end = n;
+    if (k_begin < 0 || k_begin > k_end || k_end > n) return FWX_ERR_INVALID;
+    return n > FWX_BATCH_MAX_N ? FWX_ERR_UNSUPPORTED : FWX_OK;
+}
+
+template <typename T>
+int dev_solve_batch(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, int64_t stride,
+                    int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, hipStream_t s)
+{
+    const hipError_t e = fwx::launch_batch_solve<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
+                                                    d_updates_each, batch_wave_max_n(), s);
+    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
+    FWX_HIP(e);
+    return FWX_OK;
+}
+
+// fwx_solve_batch_f64 / _f32: count matrices of order n from / to host arrays, one launch.  Pitch n, no
+// padding (the batch kernels load scalars), the arrays of the batch back to back on the device.
+template <typename T>
+int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
+                     const fwx_opts *o)
+{
+    if (count < 0 || n < 0) return FWX_ERR_INVALID;
+    if (count == 0 || n == 0) return FWX_OK;
+    if (!rate || (hops && !next)) return FWX_ERR_INVALID;
+    Opts op;
+    int rc = read_opts(o, n, op);
+    if (rc) return rc;
+    if ((rc = batch_range(n, op.k_begin, op.k_end))) return rc;
+    if (op.engine != FWX_ENGINE_AUTO) return FWX_ERR_UNSUPPORTED;
+    DeviceGuard g;
+    if ((rc = g.enter(op.device))) return rc;
+
+    const size_t cells = (size_t)count * (size_t)n * (size_t)n;
+    const bool counting = updates_each || op.updates_out;
+    CtxLease lease;
+    if ((rc = lease.open())) return rc;
+    CallCtx &cx = *lease.c;
+    if (op.has_stream) cx.uses_stream(op.stream);
+    hipStream_t s = op.has_stream ? op.stream : cx.s;
+    void *d_rate = nullptr, *d_next = nullptr, *d_hops = nullptr, *d_upd = nullptr;
+    fail_point();
+    if ((rc = cx.reserve(CallCtx::RATE, cells * sizeof(T), &d_rate))) return rc;
+    fail_point();
+    if (next && (rc = cx.reserve(CallCtx::NEXT, cells * sizeof(int32_t), &d_next))) return rc;
+    fail_point();
+    if (hops && (rc = cx.reserve(CallCtx::HOPS, cells * sizeof(int32_t), &d_hops))) return rc;
+    std::vector<unsigned long long> h_upd;
+    if (counting) {                              // one counter per matrix: the context's workspace
+        fail_point();
+        h_upd.resize((size_t)count);
+        if ((rc = cx.reserve(CallCtx::WS, (size_t)count * sizeof(unsigned long long), &d_upd))) return rc;
+        FWX_HIP(hipMemsetAsync(d_upd, 0, (size_t)count * sizeof(unsigned long long), s));
+    }
+
+    // pinned staging while the whole batch fits (see solve_host), straight copies above
+    const size_t b_rate = cells * sizeof(T), b_idx = cells * sizeof(int32_t);
+    const size_t b_total = b_rate + (next ? b_idx : 0) + (hops ? b_idx : 0);
+    const bool staged = b_total <= CallCtx::kStageBytes;
+    char *st_rate = nullptr, *st_next = nullptr, *st_hops = nullptr;
+    if (staged) {
+        void *pinned = nullptr;
+        fail_point();
+        if ((rc = cx.reserve_pinned(b_total, &pinned))) return rc;
+        st_rate = (char *)pinned;
+        st_next = st_rate + b_rate;
+        st_hops = st_next + (next ? b_idx : 0);
+        memcpy(st_rate, rate, b_rate);
+        if (next) memcpy(st_next, next, b_idx);
+        if (hops) memcpy(st_hops, hops, b_idx);
+    }
+    FWX_HIP(hipMemcpyAsync(d_rate, staged ? (const void *)st_rate : (const void *)rate, b_rate, hipMemcpyHostToDevice, s));
+    if (next) FWX_HIP(hipMemcpyAsync(d_next, staged ? (const void *)st_next : (const void *)next, b_idx, hipMemcpyHostToDevice, s));
+    if (hops) FWX_HIP(hipMemcpyAsync(d_hops, staged ? (const void *)st_hops : (const void *)hops, b_idx, hipMemcpyHostToDevice, s));
+
+    if ((rc = dev_solve_batch<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
+                                 op.k_begin, op.k_end, (unsigned long long *)d_upd, s)))
+        return rc;
+
+    FWX_HIP(hipMemcpyAsync(staged ? (void *)st_rate : (void *)rate, d_rate, b_rate, hipMemcpyDeviceToHost, s));
+    if (next) FWX_HIP(hipMemcpyAsync(staged ? (void *)st_next : (void *)next, d_next, b_idx, hipMemcpyDeviceToHost, s));
+    if (hops) FWX_HIP(hipMemcpyAsync(staged ? (void *)st_hops : (void *)hops, d_hops, b_idx, hipMemcpyDeviceToHost, s));
+    if (counting)
+        FWX_HIP(hipMemcpyAsync(h_upd.data(), d_upd, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    FWX_HIP(hipStreamSynchronize(s));
+    if (staged) {
+        memcpy(rate, st_rate, b_rate);
+        if (next) memcpy(next, st_next, b_idx);
+        if (hops) memcpy(hops, st_hops, b_idx);
+    }
+    if (counting) {
+        uint64_t sum = 0;
+        for (int32_t b = 0; b < count; ++b) {
+            sum += h_upd[(size_t)b];
+            if (updates_each) updates_each[b] = h_upd[(size_t)b];
+        }
+        if (op.updates_out) *op.updates_out = sum;
+    }
+    return FWX_OK;
+}
+
 // Single-thread device walk of the next-hop matrix (fwx_matrix_query).
 __global__ void follow_path_kernel(const int32_t *next, int n, int ld, int src, int dst, int32_t *out,
                                    int cap, int32_t *len_out)
@@ -970,6 +1075,44 @@ int fwx_solve_f32(int32_t n, float *rate, int32_t *next, int32_t *hops, const fw
 {
     return fwxi::guarded([&]() -> int { return solve_host<float>(n, rate, next, hops, opts); });
 }
+
+int fwx_solve_batch_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                        uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts);
+    });
+}
+
+int fwx_solve_batch_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                        uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts);
+    });
+}
+
+int fwx_dev_solve_batch(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                        int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
+                        void *stream)
+{
+    return fwxi::guarded([&]() -> int {
+        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
+        if (count == 0 || n == 0) return FWX_OK;
+        if (!rate || (hops && !next) || stride < (int64_t)n * n) return FWX_ERR_INVALID;
+        const int rc = batch_range(n, k_begin, k_end);
+        if (rc) return rc;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        hipStream_t s = (hipStream_t)stream;
+        if (dtype == FWX_F64)
+            return dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, k_begin, k_end,
+                                           d_updates_each, s);
+        return dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, k_begin, k_end,
+                                      d_updates_each, s);
+    });
+}
+
+int fwx_test_batch_wave_max_n(void) { return batch_wave_max_n(); }
 
 int fwx_follow_path(int32_t n, const int32_t *next, int32_t src, int32_t dst, int32_t *out,
                     int32_t cap)

@@ -466,6 +466,22 @@ inline int perk_pivots()
     return FWX_PERK_PIVOTS_DEFAULT;
 }
 
+// Tier choice of the batched small solves (fwx_solve_batch_*, fwx_dev_solve_batch): matrices of order n <=
+// FWX_BATCH_WAVE_MAX_N take the wave tier (one wave per matrix, registers only), larger ones the workgroup
+// tier (small_solve's body, one workgroup per matrix).  An integer 0 ... FWX_BATCH_WAVE_N, read on every
+// call; 0 turns the wave tier off; any other value: the default.  No result bit depends on it.
+#define FWX_BATCH_WAVE_MAX_N_DEFAULT FWX_BATCH_WAVE_N
+inline int batch_wave_max_n()
+{
+    if (const char *e = getenv("FWX_BATCH_WAVE_MAX_N")) {
+        char *end = nullptr;
+        const long v = strtol(e, &end, 10);
+        // digits only: no sign, no blank
+        if (*e >= '0' && *e <= '9' && *end == '\0' && v >= 0 && v <= FWX_BATCH_WAVE_N) return (int)v;
+    }
+    return FWX_BATCH_WAVE_MAX_N_DEFAULT;
+}
+
 // Launches of the multi-pivot schedule by pivots per launch: [0] relax_k (ragged single pivots), [1] / [2] /
 // [3] relax_kt with 2 / 4 / 8, [4] panel launches.  Test hook fwx_test_perk_pivots (fwx.h); relaxed host atomics.
 inline std::atomic<uint64_t> g_perk_launches[5];

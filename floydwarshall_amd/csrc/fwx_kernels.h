@@ -132,6 +132,17 @@ template <typename T>
 hipError_t launch_small_solve(T *rate, int32_t *next, int32_t *hops, int n, int k_begin, int k_end,
                               unsigned long long *updates, PathLog plog, hipStream_t s);
 
+// Batched small solves: `count` matrices of order n <= FWX_SMALL_N, matrix b at rate + b*stride (next / hops
+// alike; stride >= n*n elements, the gap is never touched), pivots [k_begin,k_end) of each, in one launch (one per
+// 2^21 matrices).  n <= wave_max_n (at most FWX_BATCH_WAVE_N): one wave per matrix, the matrix in registers,
+// no LDS; otherwise small_solve's body with one workgroup per matrix.  updates_each: count counters or
+// nullptr, counter b is incremented by U of matrix b.  No kernel-form bit is recorded.
+#define FWX_BATCH_WAVE_N 16
+template <typename T>
+hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride,
+                              int k_begin, int k_end, unsigned long long *updates_each, int wave_max_n,
+                              hipStream_t s);
+
 template <typename T>
 hipError_t launch_snapshot_row(T *dst, const T *src, int32_t *hdst, const int32_t *hsrc, int n,
                                hipStream_t s);

@@ -437,11 +437,14 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
 // post-step values (= the time-(k+1) operands) into the other buffer, so one barrier per pivot is
 // enough.  Row k and column k are fixed points of step k, so what step k reads are exactly the
 // step-start operands (Algorithms.hs:58-60).
+//
+// The body is shared by two kernels: small_solve (one matrix, one workgroup) and small_solve_batch (the
+// workgroup tier of the batched solve: workgroup b solves matrix b of a batch).
 // -------------------------------------------------------------------------------------------------
 template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
-__global__ __launch_bounds__(M * RG) void small_solve(T *rate, int32_t *next, int32_t *hops, int n,
-                                                      int k_begin, int k_end,
-                                                      unsigned long long *updates, PathLog plog)
+__device__ __forceinline__ void small_solve_body(T *rate, int32_t *next, int32_t *hops, int n,
+                                                 int k_begin, int k_end,
+                                                 unsigned long long *updates, PathLog plog)
 {
     constexpr int E = M / RG;                 // entries per thread; rows r = r0 + RG*m
     constexpr int G = 4;                      // entries per branch-free group
@@ -577,6 +580,176 @@ __global__ __launch_bounds__(M * RG) void small_solve(T *rate, int32_t *next, in
         if (tid == 0 && s_cnt) atomicAdd(&updates[0], (unsigned long long)s_cnt);
     }
 }
+
+template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
+__global__ __launch_bounds__(M * RG) void small_solve(T *rate, int32_t *next, int32_t *hops, int n,
+                                                      int k_begin, int k_end,
+                                                      unsigned long long *updates, PathLog plog)
+{
+    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(rate, next, hops, n, k_begin, k_end, updates, plog);
+}
+
+// -------------------------------------------------------------------------------------------------
+// Batched small solves: `count` independent matrices of one order n <= 128 in one launch, matrix b at
+// rate + b*stride (next / hops alike), U of matrix b added to updates[b].  No path trace.
+//
+// Workgroup tier (any n <= 128): small_solve's body, workgroup b on matrix b.
+// -------------------------------------------------------------------------------------------------
+template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS>
+__global__ __launch_bounds__(M * RG) void small_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
+                                                            long long stride, int k_begin, int k_end,
+                                                            unsigned long long *updates)
+{
+    const size_t off = (size_t)blockIdx.x * (size_t)stride;
+    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, false>(rate + off, HAS_NEXT ? next + off : nullptr,
+                                                          HAS_HOPS ? hops + off : nullptr, n, k_begin, k_end,
+                                                          updates ? updates + blockIdx.x : nullptr, PathLog());
+}
+
+// -------------------------------------------------------------------------------------------------
+// Wave tier (n <= 16): one WAVE per matrix, four matrices per 256-thread workgroup; no LDS, no barrier.
+// The matrix is a NaN-padded 16 x 16 tile in registers: lane l holds column c = l & 15 of the rows
+// q + 4m (q = l >> 4, m = 0..3), next and hops alike.  Row k = 4*mk + kq is register mk of the 16 lanes
+// with q == kq; column k is lane (q*16 + k) of every row group.  Step k reads its operands -- r[k][c],
+// next[k][c], hops[k][c] from lane kq*16 + c, and r[i][k], next[i][k], hops[i][k] from lane (l & 48) | k
+// for each of the lane's rows -- with cross-lane reads (ds_bpermute_b32: the sources differ per lane),
+// ALL of them before any register of the step is updated, so every operand is the step-start value
+// (Algorithms.hs:58-60).  The pivot loop is fully unrolled: which register holds row k is then a
+// compile-time fact and no register array is indexed dynamically (no scratch).  Skips as everywhere:
+// NaN in place of r[k][k]-column / row operands (i == k, j == k), +inf in the register of a diagonal
+// entry (never a target; never an operand, because the only steps that would read it skip it), whose
+// value in memory is left alone.  Row groups and pivots that are padding only are skipped by
+// wave-uniform tests.  A wave past `count` leaves at once: there is no barrier it could be missed at.
+// -------------------------------------------------------------------------------------------------
+template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+__global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
+                                                        long long stride, int count, int k_begin,
+                                                        int k_end, unsigned long long *updates)
+{
+    constexpr int E = 4;                      // rows per lane: q, q + 4, q + 8, q + 12
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const long long b = (long long)blockIdx.x * 4 + wave;
+    if (b >= count) return;                   // wave-uniform
+    const int c = lane & 15, q = lane >> 4;
+    const size_t base = (size_t)b * (size_t)stride;
+
+    T x[E];
+    int32_t nx[E], hp[E];
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int r = q + 4 * m;
+        const bool in = r < n && c < n;
+        const size_t off = base + (size_t)(r * n + c);
+        x[m] = in ? rate[off] : quiet_nan<T>();
+        if (r == c) x[m] = (T)__builtin_huge_val();           // skip j == i (see small_solve)
+        nx[m] = -1;
+        hp[m] = 0;
+        if constexpr (HAS_NEXT) { if (in) nx[m] = next[off]; }
+        if constexpr (HAS_HOPS) { if (in) hp[m] = hops[off]; }
+    }
+
+    unsigned int mine = 0;
+#pragma unroll
+    for (int mk = 0; mk < E; ++mk) {
+#pragma unroll
+        for (int kq = 0; kq < 4; ++kq) {
+            const int k = 4 * mk + kq;
+            if (k < k_begin || k >= k_end) continue;          // scalar (k_end <= n)
+            // every operand of step k, before any register changes
+            const int rsrc = kq * 16 + c;
+            T rkc = __shfl(x[mk], rsrc, 64);
+            int32_t nkc = -1, hkc = 0;
+            if constexpr (HAS_NEXT) nkc = __shfl(nx[mk], rsrc, 64);
+            if constexpr (HAS_HOPS) hkc = __shfl(hp[mk], rsrc, 64);
+            if (c == k) rkc = quiet_nan<T>();                 // skip j == k
+            const int csrc = (lane & 48) | k;
+            T cr[E];
+            int32_t cn[E], ch[E];
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                cr[m] = quiet_nan<T>();
+                cn[m] = -1;
+                ch[m] = 0;
+                if (4 * m >= n) continue;                     // scalar: padding rows only
+                cr[m] = __shfl(x[m], csrc, 64);
+                if (q + 4 * m == k) cr[m] = quiet_nan<T>();   // skip i == k
+                if constexpr (HAS_NEXT) cn[m] = __shfl(nx[m], csrc, 64);
+                if constexpr (HAS_HOPS) ch[m] = __shfl(hp[m], csrc, 64);
+            }
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                if (4 * m >= n) continue;
+                const T cand = cr[m] * rkc;                   // Algorithms.hs:61
+                const bool p = x[m] < cand;                   // :55 (false on NaN)
+                x[m] = p ? cand : x[m];
+                // head (ikPath ++ kjPath): next[i][k] unless ikPath is empty, then next[k][j]
+                if constexpr (HAS_NEXT) nx[m] = p ? (cn[m] < 0 ? nkc : cn[m]) : nx[m];
+                if constexpr (HAS_HOPS) hp[m] = p ? ch[m] + hkc : hp[m];
+                mine += (unsigned int)__builtin_popcountll(__ballot(p));   // scalar; wave total
+            }
+        }
+    }
+
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int r = q + 4 * m;
+        if (r < n && c < n) {
+            const size_t off = base + (size_t)(r * n + c);
+            if (r != c) rate[off] = x[m];
+            if constexpr (HAS_NEXT) next[off] = nx[m];
+            if constexpr (HAS_HOPS) hops[off] = hp[m];
+        }
+    }
+    if (updates && mine && lane == 0) atomicAdd(&updates[b], (unsigned long long)mine);
+}
+
+template <typename T>
+hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride,
+                              int k_begin, int k_end, unsigned long long *updates_each, int wave_max_n,
+                              hipStream_t s)
+{
+    if (count <= 0 || n <= 0 || k_end <= k_begin) return hipSuccess;
+    if (n > FWX_SMALL_N || (hops && !next) || k_begin < 0 || k_end > n || stride < (long long)n * n)
+        return hipErrorInvalidValue;
+    const bool wave = n <= wave_max_n && n <= FWX_BATCH_WAVE_N;
+    // One launch; a launch is limited to 2^32 - 1 threads, so a batch of more than kChunk matrices
+    // (2^21 workgroups of 1024 threads) takes one launch per kChunk.
+    constexpr int kChunk = 1 << 21;
+    for (long long b0 = 0; b0 < count; b0 += kChunk) {
+        const int cnt = (int)std::min<long long>(kChunk, count - b0);
+        const size_t off = (size_t)b0 * (size_t)stride;
+        T *r = rate + off;
+        int32_t *nx = next ? next + off : nullptr, *hp = hops ? hops + off : nullptr;
+        unsigned long long *u = updates_each ? updates_each + b0 : nullptr;
+#define FWX_BATCH_WAVE(HN, HH)                                                                     \
+    hipLaunchKernelGGL((wave_solve_batch<T, HN, HH>), dim3((cnt + 3) / 4), dim3(256), 0, s, r, nx, hp, n, \
+                       stride, cnt, k_begin, k_end, u)
+#define FWX_BATCH_WG(M, RG, HN, HH)                                                                \
+    hipLaunchKernelGGL((small_solve_batch<T, M, RG, HN, HH>), dim3(cnt), dim3(M * RG), 0, s, r, nx, hp, n, \
+                       stride, k_begin, k_end, u)
+#define FWX_BATCH_FIELDS(LAUNCH, ...)                                                              \
+    do {                                                                                           \
+        if (hops) LAUNCH(__VA_ARGS__ true, true);                                                  \
+        else if (next) LAUNCH(__VA_ARGS__ true, false);                                            \
+        else LAUNCH(__VA_ARGS__ false, false);                                                     \
+    } while (0)
+        if (wave) FWX_BATCH_FIELDS(FWX_BATCH_WAVE);
+        else if (n <= 64) FWX_BATCH_FIELDS(FWX_BATCH_WG, 64, 16,);
+        else FWX_BATCH_FIELDS(FWX_BATCH_WG, 128, 8,);
+#undef FWX_BATCH_FIELDS
+#undef FWX_BATCH_WG
+#undef FWX_BATCH_WAVE
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template hipError_t launch_batch_solve<float>(float *, int32_t *, int32_t *, int, int, long long, int, int,
+                                              unsigned long long *, int, hipStream_t);
+template hipError_t launch_batch_solve<double>(double *, int32_t *, int32_t *, int, int, long long, int, int,
+                                               unsigned long long *, int, hipStream_t);
 
 template <typename T>
 hipError_t launch_small_solve(T *rate, int32_t *next, int32_t *hops, int n, int k_begin, int k_end,

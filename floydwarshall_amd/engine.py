@@ -17,7 +17,7 @@ from ._lib import (FWX_ENGINE_AUTO, FWX_ENGINE_FUSED, FWX_ENGINE_PERK, FWX_F32, 
                    FWX_FUSED_BLOCK, FWX_UPDATE_SHARDS, FWX_XCHG_AUTO, FWX_XCHG_PEER, FWX_XCHG_RCCL,
                    FWX_ERR_RCCL, FwxError, FwxOpts, FwxPivots, FwxSlab, check, lib)
 
-__all__ = ["solve", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
+__all__ = ["solve", "solve_batch", "dev_solve_batch", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
            "dev_solve", "DeviceMatrix", "dev_relax", "dev_panel", "dev_panel_snap",
            "dev_relax_fused", "FusedWorkspace", "Trace", "FWX_FUSED_BLOCK", "device_count",
            "FwxError", "FWX_ENGINE_AUTO", "FWX_ENGINE_PERK", "FWX_ENGINE_FUSED",
@@ -96,6 +96,53 @@ def solve(rate, nxt=None, hops=None, *, device=-1, engine=FWX_ENGINE_AUTO, k_beg
     check(fn(rate.shape[0], _np_ptr(rate), _np_ptr(nxt), _np_ptr(hops), ctypes.byref(o)),
           "fwx_solve")
     return int(u.value) if count_updates else None
+
+
+def solve_batch(rate, nxt=None, hops=None, *, device=-1, k_begin=0, k_end=0, count_updates=False):
+    """runAlgo on every matrix of a batch in ONE launch (fwx_solve_batch_f64 / _f32): rate.shape ==
+    (count, n, n) with n <= FWX_BATCH_MAX_N, C-contiguous host numpy arrays, solved in place; nxt / hops
+    shaped alike.  Every matrix comes back as `solve` of that matrix alone would leave it.
+
+    Returns the per-matrix U as a uint64 array of `count` entries if count_updates else None."""
+    if not (isinstance(rate, np.ndarray) and rate.ndim == 3 and rate.shape[1] == rate.shape[2]):
+        raise ValueError("rate must be a numpy array of shape (count, n, n)")
+    if rate.dtype not in (np.float32, np.float64) or not rate.flags.c_contiguous:
+        raise ValueError("rate must be C-contiguous float32 or float64")
+    for name, a in (("next", nxt), ("hops", hops)):
+        if a is not None and not (isinstance(a, np.ndarray) and a.shape == rate.shape
+                                  and a.dtype == np.int32 and a.flags.c_contiguous):
+            raise ValueError("%s must be a C-contiguous int32 array shaped like rate" % name)
+    if hops is not None and nxt is None:
+        raise ValueError("hops requires next")
+    count, n = rate.shape[0], rate.shape[1]
+    o, _ = _opts(device, FWX_ENGINE_AUTO, k_begin, k_end)
+    each = np.zeros(count, dtype=np.uint64) if count_updates else None
+    fn = lib().fwx_solve_batch_f64 if rate.dtype == np.float64 else lib().fwx_solve_batch_f32
+    check(fn(count, n, _np_ptr(rate), _np_ptr(nxt), _np_ptr(hops), _np_ptr(each), ctypes.byref(o)),
+          "fwx_solve_batch")
+    return each
+
+
+def dev_solve_batch(rate_t, count, n, *, next_t=None, hops_t=None, stride=None, k_begin=0, k_end=0,
+                    updates_t=None, stream=None):
+    """fwx_dev_solve_batch: `count` matrices of order n <= FWX_BATCH_MAX_N held in the device array rate_t,
+    matrix b at element b * stride (default n * n; the gap is never touched), next_t / hops_t alike, solved
+    in place by one launch, asynchronously on `stream` (default: as dev_relax).  updates_t: device array
+    of `count` 64-bit counters, counter b is incremented by U of matrix b."""
+    stride = n * n if stride is None else int(stride)
+    need = (count - 1) * stride + n * n if count > 0 else 0
+    assert rate_t.is_cuda and rate_t.is_contiguous() and rate_t.numel() >= need
+    for t in (next_t, hops_t):
+        assert t is None or (t.is_cuda and t.is_contiguous() and _dtype_name(t) == "int32"
+                             and t.numel() >= need)
+    assert updates_t is None or (updates_t.element_size() == 8 and updates_t.numel() >= count)
+    vp = ctypes.c_void_p
+    check(lib().fwx_dev_solve_batch(
+        count, n, _tensor_dtype_code(rate_t), vp(rate_t.data_ptr()),
+        vp(next_t.data_ptr()) if next_t is not None else None,
+        vp(hops_t.data_ptr()) if hops_t is not None else None, stride, k_begin, k_end,
+        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)),
+        "fwx_dev_solve_batch")
 
 
 def solve_multi(rate, nxt=None, hops=None, *, devices=(0,), exchange=FWX_XCHG_AUTO,

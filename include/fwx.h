@@ -142,6 +142,42 @@ int fwx_test_perk_pivots(uint64_t *launches, int reset);
 int fwx_solve_f64(int32_t n, double *rate, int32_t *next, int32_t *hops, const fwx_opts *opts);
 int fwx_solve_f32(int32_t n, float *rate, int32_t *next, int32_t *hops, const fwx_opts *opts);
 
+/* ---- batched small solves: many matrices of one order n <= FWX_BATCH_MAX_N in ONE launch ---------
+ * The reference's own regime is small (its tests stop at 4 x 4); a host with many independent small
+ * matrices -- one per timestamp of a price history, one per venue group, a what-if sweep over quotes --
+ * solves them all in one call instead of looping over fwx_solve_*: one workgroup (n <= 16: one wave) per
+ * matrix, so the batch spreads over the whole chip where the loop keeps one CU busy.  Every matrix gets
+ * the full semantics above, the list rule included (head = next[i][k] if that is >= 0, else next[k][j]);
+ * there is no domain check and no routing: a batch may mix matrices inside and outside the domain, and
+ * each comes back bit-identical to the reference loop on that matrix alone.
+ *
+ * count matrices of order n, matrix b at rate + b*n*n (next / hops alike, both optional, hops needs next);
+ * HOST arrays, solved in place.  updates_each: optional, count entries, U of each matrix.
+ * count == 0 or n == 0: FWX_OK, nothing is touched.  FWX_ERR_INVALID: count < 0, n < 0, rate NULL, hops
+ * without next, a bad struct_size or pivot range.  FWX_ERR_UNSUPPORTED: n > FWX_BATCH_MAX_N, or
+ * opts->engine other than FWX_ENGINE_AUTO (the batch kernels are the only engine here).  All of these are
+ * decided before any device call; then FWX_ERR_NO_DEVICE without a device, the arrays untouched.
+ * opts: device, k_begin / k_end (one range for every matrix), stream / use_stream and updates_out (the SUM of
+ * U over the batch) are honoured; serpentine is ignored.
+ * Tier choice: FWX_BATCH_WAVE_MAX_N (environment, read per call; an integer 0 ... 16, default 16, anything
+ * else means the default): n at or below it runs one wave per matrix with the matrix in registers, larger n
+ * one workgroup per matrix; 0 turns the wave tier off.  No result bit depends on it.                   */
+#define FWX_BATCH_MAX_N 128
+int fwx_solve_batch_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                        uint64_t *updates_each, const fwx_opts *opts);
+int fwx_solve_batch_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                        uint64_t *updates_each, const fwx_opts *opts);
+/* The same on caller-owned DEVICE memory, asynchronous on `stream`, nothing allocated or synchronised;
+ * stride = elements between consecutive matrices (>= n*n, else FWX_ERR_INVALID; the gap is never read or
+ * written); pivots [k_begin, k_end) of every matrix, k_end <= 0 means n; dtype: fwx_dtype;
+ * d_updates_each: optional device array of count uint64, INCREMENTED by each matrix's U.  Statuses as above
+ * (n > FWX_BATCH_MAX_N: FWX_ERR_UNSUPPORTED).                                                          */
+int fwx_dev_solve_batch(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                        int64_t stride, int32_t k_begin, int32_t k_end,
+                        unsigned long long *d_updates_each, void *stream);
+/* TEST HOOK: what FWX_BATCH_WAVE_MAX_N parses to right now.  Needs no device.  Not for production use. */
+int fwx_test_batch_wave_max_n(void);
+
 /* Index form of the `_path` list that optimum returns (Algorithms.hs:74-75): follow next-hops
  * from src until dst.  Returns the number of vertices written to out (dst included, src not), 0 if
  * next[src][dst] == -1 (empty path, "no exchange"), or a negative fwx_status.  Host arrays.      */
