@@ -15,7 +15,7 @@
 #include "fwx_guard.h"
 #include "fwx_internal.h"
 #include "fwx_kernels.h"
-#include "fwx_replay.h"
+#include "fwx_resume.h"
 
 using namespace fwxi;
 
@@ -85,29 +85,7 @@ template <typename T> bool fused_ok(int n, const void *rate, const int32_t *)
 //     count it either -- and an entry that does not move is no item of the arg re-scan: its next-hop,
 //     path length and trace stay), so main(P+1) simply covers everything but the cross after it.
 constexpr int kLookaheadMinN = INT32_MAX, kLookaheadMinNWithNext = 16384, kLookaheadMinNWithTrace = 8192;
-// crossover (single / double pass, ms; profiles/r03_double_pass_crossover.txt): f32 4096: 4.10 / 4.74,
-// 6144: 10.47 / 10.18, 8192: 21.2 / 20.0, 12288: 68.1 / 61.0, 16384: 152.0 / 135.3; f64 6144: 23.1 / 22.1,
-// 16384: 355 / 324 -- below ~6000 the side chain (five launches per 128 pivots) is the critical path
-constexpr int kDoublePassMinN = 6144;    // FWX_DOUBLE_PASS_MIN_N overrides
-// ... and with next-hops (the arg kernels; + trace, + hops), f32 only: FWX_DOUBLE_PASS_NEXT_MIN_N overrides.
-// (f64: the two-pass fused_main_arg_f64 is SLOWER than two launches, N = 16384 + next 486 -> 499 ms on
-// one box -- tools/runs/r03_run33.sh --, so f64 stays on the single pass unless the variable asks)
-// (round 4, after the panel flags and the 32-row column panels: tools/runs/r04_run42.sh, single / double pass, ms:
-//  + next 4096 5.8 / 6.0, 5120 9.9 / 9.7, 6144 16.2 / 16.0, 7168 24.3 / 23.8; + trace 4096 6.3 / 6.8, 6144 21.0 /
-//  17.9, 7168 32.0 / 26.1 -- the threshold was 8192)
-constexpr int kDoublePassNextMinN = 5120;
-// FWX_LOOKAHEAD_MIN_N / FWX_SYMMETRIC_MIN_N override the thresholds (tests force each schedule at
-// small sizes, tuning runs switch one off with a huge value); read on every solve.
-static int env_threshold(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    if (e && *e) {
-        char *end = nullptr;
-        const long v = strtol(e, &end, 10);
-        if (end != e && v >= 0 && v <= INT32_MAX) return (int)v;
-    }
-    return dflt;
-}
+// The double-pass crossovers (kDoublePassMinN, kDoublePassNextMinN) and env_threshold: fwx_internal.h.
 
 template <typename T>
 int fused_range(T *rate, int32_t *next, int32_t *hops, int n, int k_begin, int k_end, void *ws,
@@ -130,29 +108,17 @@ int fused_range(T *rate, int32_t *next, int32_t *hops, int n, int k_begin, int k
     // Resumable handle: every pass writes its panels to their place in the all-pivot arrays (row k of
     // each = pivot k) instead of a ping-pong buffer, and the state is copied at the checkpoint pivots.
     if (rec && k_begin % FWX_FUSED_B) rec = nullptr;      // passes must start on multiples of 64
+    Slab whole;                                           // the matrix as one slab (fwx_resume.h)
+    whole.live = {rate, next, hops, plog.last, plog.at_col, plog.at_row};
+    whole.rows = whole.nd = n; whole.ct_ld = ld; whole.es = sizeof(T); whole.s = s;
     auto panel_set = [&](int k0, int b) {
         if (!rec) return;
-        wbuf[b] = (T *)rec->w + (size_t)k0 * n;
-        ctbuf[b] = (T *)rec->ct + (size_t)k0 * ld;
-        cntbuf[b] = rec->cnt ? rec->cnt + (size_t)k0 * ld : nullptr;
-        whbuf[b] = rec->wh ? rec->wh + (size_t)k0 * n : nullptr;
-        chtbuf[b] = rec->cht ? rec->cht + (size_t)k0 * ld : nullptr;
+        const PanelRows pr = store_panels(rec->store, whole, k0);
+        wbuf[b] = (T *)pr.w; ctbuf[b] = (T *)pr.ct; cntbuf[b] = pr.cnt; whbuf[b] = pr.wh; chtbuf[b] = pr.cht;
     };
     auto checkpoint = [&](int k0) -> int {        // the state at the START of step k0, if it is one
-        if (!rec) return FWX_OK;
-        for (size_t c = 0; c < rec->pivot.size(); ++c) {
-            if (rec->pivot[c] != k0) continue;
-            const size_t nn = (size_t)n * n;
-            FWX_HIP(hipMemcpyAsync(rec->rate[c], rate, nn * sizeof(T), hipMemcpyDeviceToDevice, s));
-            if (next) FWX_HIP(hipMemcpyAsync(rec->next[c], next, nn * 4, hipMemcpyDeviceToDevice, s));
-            if (hops) FWX_HIP(hipMemcpyAsync(rec->hops[c], hops, nn * 4, hipMemcpyDeviceToDevice, s));
-            if (plog.last) {
-                FWX_HIP(hipMemcpyAsync(rec->last[c], plog.last, nn * 4, hipMemcpyDeviceToDevice, s));
-                FWX_HIP(hipMemcpyAsync(rec->at_col[c], plog.at_col, nn * 4, hipMemcpyDeviceToDevice, s));
-                FWX_HIP(hipMemcpyAsync(rec->at_row[c], plog.at_row, nn * 4, hipMemcpyDeviceToDevice, s));
-            }
-        }
-        return FWX_OK;
+        const int c = rec ? rec->checkpoint_at(k0) : -1;
+        return c < 0 ? FWX_OK : save_checkpoint(rec->store, whole, c);
     };
     SideStream local_side;
     SideStream &side = kept_side ? *kept_side : local_side;
@@ -923,72 +889,37 @@ inline size_t dev_offset(const fwx_matrix *m, int64_t index)
     return (size_t)(index / m->n) * (size_t)m->nd + (size_t)(index % m->n);
 }
 
-// Element counts behind the memory a resumable handle keeps: `cells` per n x n array and `col_cells`
-// per all-pivot column-panel array, summed over the partitions of a partitioned handle.
-struct MultiDims { uint64_t cells, col_cells, w_cells; };
-MultiDims resume_dims(const fwx_matrix *m)
+// The handle as one slab of all its rows (fwx_resume.h), work on its own stream.
+Slab slab_of(const fwx_matrix *m)
 {
-    MultiDims d;
-    if (m->multi) {
-        multi_resume_dims(m, &d.cells, &d.col_cells, &d.w_cells);
-        return d;
-    }
-    const uint64_t nd = (uint64_t)m->nd;
-    d.cells = d.w_cells = nd * nd;
-    d.col_cells = nd * ((nd + 3) & ~(uint64_t)3);
-    return d;
+    Slab v;
+    v.live = {m->rate, m->next, m->hops, m->plog.last, m->plog.at_col, m->plog.at_row};
+    v.kept.rate = m->rate0; v.kept.next = m->next0; v.kept.hops = m->hops0;
+    v.rows = v.nd = m->nd;
+    v.ct_ld = (m->nd + 3) & ~3;
+    v.es = m->dtype == FWX_F64 ? 8 : 4;
+    v.s = m->stream;
+    return v;
 }
 
 void resume_free(Resume *r)
 {
     if (!r) return;
-    auto drop = [](void *p) { if (p) (void)hipFree(p); };
-    for (void *p : r->rate) drop(p);
-    for (auto *v : {&r->next, &r->hops, &r->last, &r->at_col, &r->at_row})
-        for (int32_t *p : *v) drop(p);
-    drop(r->w); drop(r->ct); drop(r->cnt); drop(r->wh); drop(r->cht); drop(r->idx);
+    store_free(r->store);
     delete r;
 }
 
-// index: entry offsets in the DEVICE arrays (row * nd + column)
-template <typename T>
-int resolve_typed(fwx_matrix *m, int32_t count, const int64_t *index, int c_idx, hipStream_t s)
+// The patched entries (indices of the caller's n x n view) into the kept input; offs, if given: their offsets
+// in the device arrays.
+int patch_kept_input(const fwx_matrix *m, const Slab &v, int32_t count, const int64_t *index, const void *rate_vals,
+                     const int32_t *next_vals, const int32_t *hops_vals, std::vector<int64_t> *offs = nullptr)
 {
-    Resume &R = *m->resume;
-    const int n = m->nd, c = R.pivot[(size_t)c_idx];
-    const size_t nn = (size_t)n * n;
-    // the state at the start of step c ...
-    FWX_HIP(hipMemcpyAsync(m->rate, R.rate[(size_t)c_idx], nn * sizeof(T), hipMemcpyDeviceToDevice, s));
-    if (m->next) FWX_HIP(hipMemcpyAsync(m->next, R.next[(size_t)c_idx], nn * 4, hipMemcpyDeviceToDevice, s));
-    if (m->hops) FWX_HIP(hipMemcpyAsync(m->hops, R.hops[(size_t)c_idx], nn * 4, hipMemcpyDeviceToDevice, s));
-    if (m->plog.last) {
-        FWX_HIP(hipMemcpyAsync(m->plog.last, R.last[(size_t)c_idx], nn * 4, hipMemcpyDeviceToDevice, s));
-        FWX_HIP(hipMemcpyAsync(m->plog.at_col, R.at_col[(size_t)c_idx], nn * 4, hipMemcpyDeviceToDevice, s));
-        FWX_HIP(hipMemcpyAsync(m->plog.at_row, R.at_row[(size_t)c_idx], nn * 4, hipMemcpyDeviceToDevice, s));
+    for (int32_t q = 0; q < count; ++q) {
+        const size_t off = dev_offset(m, index[q]);
+        if (offs) offs->push_back((int64_t)off);
+        const int rc = patch_kept(v, off, q, rate_vals, next_vals, hops_vals);
+        if (rc) return rc;
     }
-    // ... except the patched entries, replayed from the patched input through the stored panels into
-    // the live arrays and into every checkpoint up to c (which thereby stay valid for the new input)
-    ReplayTargets tg;
-    memset(&tg, 0, sizeof(tg));
-    for (int q = 0; q <= c_idx; ++q) {
-        const int t = tg.count++;
-        tg.pivot[t] = R.pivot[(size_t)q];
-        tg.rate[t] = R.rate[(size_t)q];
-        tg.next[t] = m->next ? R.next[(size_t)q] : nullptr;
-        tg.hops[t] = m->hops ? R.hops[(size_t)q] : nullptr;
-        tg.last[t] = m->plog.last ? R.last[(size_t)q] : nullptr;
-    }
-    {
-        const int t = tg.count++;
-        tg.pivot[t] = c;
-        tg.rate[t] = m->rate; tg.next[t] = m->next; tg.hops[t] = m->hops; tg.last[t] = m->plog.last;
-    }
-    int64_t *d_index = R.idx;
-    FWX_HIP(hipMemcpyAsync(d_index, index, (size_t)count * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(replay_entries_kernel<T>, dim3((unsigned)count), dim3(64), 0, s, d_index, n, R.ld, 0, c,
-                       (const T *)m->rate0, m->next ? m->next0 : nullptr, m->hops ? m->hops0 : nullptr,
-                       (const T *)R.w, (const T *)R.ct, m->next ? R.cnt : nullptr, R.wh, R.cht, tg);
-    FWX_HIP(hipGetLastError());
     return FWX_OK;
 }
 
@@ -1231,7 +1162,7 @@ int fwx_matrix_upload(fwx_matrix *m, const void *rate, const int32_t *next, cons
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        const size_t nn = (size_t)m->nd * (size_t)m->nd, es = m->dtype == FWX_F64 ? 8 : 4;
+        const size_t es = m->dtype == FWX_F64 ? 8 : 4;
         // hipMemcpyDefault: the sources may be host arrays (what an FFI hands over) or device arrays
         // (a caller that keeps its pristine input in HBM, e.g. the benchmark)
         hipStream_t s = m->stream;
@@ -1240,16 +1171,10 @@ int fwx_matrix_upload(fwx_matrix *m, const void *rate, const int32_t *next, cons
         if ((rc = copy_in(m, m->rate, rate, es, s))) return rc;
         if (m->next && (rc = copy_in(m, m->next, next, 4, s))) return rc;
         if (m->hops && (rc = copy_in(m, m->hops, hops, 4, s))) return rc;
-        if (m->plog.last || (m->keep && m->next)) {
-            // traced matrix: keep the uploaded next-hops (paths of entries never improved); kept input
-            FWX_HIP(hipMemcpyAsync(m->next0, m->next, nn * 4, hipMemcpyDeviceToDevice, s));
-            m->rec_ready = 0;   // the trace of an earlier input is stale
-        }
-        if (m->keep) {
-            FWX_HIP(hipMemcpyAsync(m->rate0, m->rate, nn * es, hipMemcpyDeviceToDevice, s));
-            if (m->hops) FWX_HIP(hipMemcpyAsync(m->hops0, m->hops, nn * 4, hipMemcpyDeviceToDevice, s));
-            m->kept_valid = 1;
-        }
+        // traced matrix: keep the uploaded next-hops (paths of entries never improved); kept input: all of it
+        if ((rc = keep_live(slab_of(m)))) return rc;
+        if (m->next0) m->rec_ready = 0;   // the trace of an earlier input is stale
+        if (m->keep) m->kept_valid = 1;
         FWX_HIP(hipStreamSynchronize(s));
         m->fresh = 1;
         if (m->resume) m->resume->state_at = m->keep ? 0 : -1;
@@ -1299,11 +1224,8 @@ int fwx_matrix_keep_input(fwx_matrix *m)
         if (m->hops) FWX_HIP(hipMalloc((void **)&m->hops0, nn * 4));
         m->keep = 1;
         if (m->fresh) {          // an unsolved upload is in the arrays: that is the input to keep
-            hipStream_t s = m->stream;
-            FWX_HIP(hipMemcpyAsync(m->rate0, m->rate, nn * es, hipMemcpyDeviceToDevice, s));
-            if (m->next) FWX_HIP(hipMemcpyAsync(m->next0, m->next, nn * 4, hipMemcpyDeviceToDevice, s));
-            if (m->hops) FWX_HIP(hipMemcpyAsync(m->hops0, m->hops, nn * 4, hipMemcpyDeviceToDevice, s));
-            FWX_HIP(hipStreamSynchronize(s));
+            if ((rc = keep_live(slab_of(m)))) return rc;
+            FWX_HIP(hipStreamSynchronize(m->stream));
             m->kept_valid = 1;
         }
         return FWX_OK;
@@ -1325,24 +1247,15 @@ int fwx_matrix_patch_input(fwx_matrix *m, int32_t count, const int64_t *index, c
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        const size_t nn = (size_t)m->nd * (size_t)m->nd, es = m->dtype == FWX_F64 ? 8 : 4;
-        hipStream_t s = m->stream;
+        const Slab v = slab_of(m);
         if (m->resume) m->resume->valid_upto = 0;   // the kept input changes without a replay
         // the remembered domain answer survives a patch whose values are themselves inside the domain
         // (rate >= +0 and not NaN; a non-zero rate comes with a next-hop >= 0); anything else, or a
         // non-zero rate patched in without its next-hop, sends the next solve through the check again
         if (m->dom_known && !patch_keeps_domain(m, count, rate_vals, next_vals)) m->dom_known = 0;
-        for (int32_t q = 0; q < count; ++q) {        // a handful of entries: plain small copies
-            const size_t off = dev_offset(m, index[q]);
-            FWX_HIP(hipMemcpyAsync((char *)m->rate0 + off * es, (const char *)rate_vals + (size_t)q * es, es,
-                                   hipMemcpyHostToDevice, s));
-            if (next_vals) FWX_HIP(hipMemcpyAsync(m->next0 + off, next_vals + q, 4, hipMemcpyHostToDevice, s));
-            if (hops_vals) FWX_HIP(hipMemcpyAsync(m->hops0 + off, hops_vals + q, 4, hipMemcpyHostToDevice, s));
-        }
-        FWX_HIP(hipMemcpyAsync(m->rate, m->rate0, nn * es, hipMemcpyDeviceToDevice, s));
-        if (m->next) FWX_HIP(hipMemcpyAsync(m->next, m->next0, nn * 4, hipMemcpyDeviceToDevice, s));
-        if (m->hops) FWX_HIP(hipMemcpyAsync(m->hops, m->hops0, nn * 4, hipMemcpyDeviceToDevice, s));
-        FWX_HIP(hipStreamSynchronize(s));
+        if ((rc = patch_kept_input(m, v, count, index, rate_vals, next_vals, hops_vals))) return rc;
+        if ((rc = restore_kept(v))) return rc;
+        FWX_HIP(hipStreamSynchronize(v.s));
         m->fresh = 1;
         m->rec_ready = 0;
         if (m->resume) m->resume->state_at = 0;      // the patched kept input, unsolved
@@ -1368,13 +1281,15 @@ int fwx_matrix_resume_bytes(const fwx_matrix *m, int32_t checkpoints, uint64_t *
 {
     return fwxi::guarded([&]() -> int {
         if (!m || !bytes_out || checkpoints < 0 || checkpoints > FWX_MAX_CHECKPOINTS) return FWX_ERR_INVALID;
-        const MultiDims d = resume_dims(m);
+        const SlabCells d = m->multi ? multi_resume_cells(m) : slab_cells(m->nd, m->nd, (m->nd + 3) & ~3);
         const uint64_t es = m->dtype == FWX_F64 ? 8 : 4;
         // per checkpoint: one copy of every array; panels: w + ct (+ cnt) (+ wh + cht) for all pivots
         // (a partitioned handle: every partition keeps all pivot ROWS, its own part of the columns)
         const uint64_t per_cp = d.cells * (es + (m->next ? 4 : 0) + (m->hops ? 4 : 0) + (m->plog.last ? 12 : 0));
         const uint64_t panels = d.w_cells * es + d.col_cells * es + (m->next ? d.col_cells * 4 : 0) +
                                 (m->hops ? d.w_cells * 4 + d.col_cells * 4 : 0);
+        // ONE index buffer, although every partition of a partitioned handle allocates its own: the session's
+        // memory budget (host/session.cpp) was tuned against this figure, so it stays as it is
         *bytes_out = (uint64_t)checkpoints * per_cp + panels + (uint64_t)FWX_MAX_PATCH * 8;
         return FWX_OK;
     });
@@ -1387,50 +1302,21 @@ int fwx_matrix_enable_resume(fwx_matrix *m, int32_t checkpoints)
         if (m->resume) return FWX_ERR_INVALID;
         if (!m->keep) return FWX_ERR_INVALID;                // replays start from the kept input
         if (m->multi) return m->n <= kSmallSolveAutoMax ? FWX_ERR_UNSUPPORTED : multi_enable_resume(m, checkpoints);
-        const int n = m->nd;                                 // everything below is sized like the device arrays
-        const bool f64 = m->dtype == FWX_F64;
         // resumable = AUTO takes the fused engine for this order (fwx.h fwx_engine)
         if (m->n <= kSmallSolveAutoMax) return FWX_ERR_UNSUPPORTED;
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
         fail_point();
-        // a partial set (an allocation failed, or threw) is released again: the handle stays usable
+        // a failure (an allocation, or the throw above) leaves nothing behind: the handle stays usable
         struct Holder {
             Resume *r = new Resume();
             ~Holder() { resume_free(r); }
         } hold;
         Resume *R = hold.r;
-        for (auto *v : {&R->next, &R->hops, &R->last, &R->at_col, &R->at_row}) v->reserve((size_t)checkpoints);
-        R->rate.reserve((size_t)checkpoints);
-        R->pivot.reserve((size_t)checkpoints);
-        const size_t es = f64 ? 8 : 4, nn = (size_t)n * n;
-        R->ld = (n + 3) & ~3;
-        // checkpoints at the multiples of 64 closest to q * n / (checkpoints + 1)
-        for (int q = 1; q <= checkpoints; ++q) {
-            int p = (int)(((int64_t)m->n * q / (checkpoints + 1) + 32) / 64 * 64);
-            if (p <= 0 || p >= m->n || (!R->pivot.empty() && p <= R->pivot.back())) continue;
-            R->pivot.push_back(p);
-        }
+        R->pivot = checkpoint_pivots(m->n, checkpoints);
         R->count = (int)R->pivot.size();
-        auto alloc = [&](void **p, size_t bytes) -> int { FWX_HIP(hipMalloc(p, bytes)); return FWX_OK; };
-        for (int q = 0; q < R->count; ++q) {
-            void *p = nullptr;
-            if ((rc = alloc(&p, nn * es))) return rc;
-            R->rate.push_back(p);
-            if (m->next) { if ((rc = alloc(&p, nn * 4))) return rc; R->next.push_back((int32_t *)p); }
-            if (m->hops) { if ((rc = alloc(&p, nn * 4))) return rc; R->hops.push_back((int32_t *)p); }
-            if (m->plog.last)
-                for (auto *v : {&R->last, &R->at_col, &R->at_row}) {
-                    if ((rc = alloc(&p, nn * 4))) return rc;
-                    v->push_back((int32_t *)p);
-                }
-        }
-        const size_t pan = (size_t)n * R->ld;
-        if ((rc = alloc(&R->w, nn * es)) || (rc = alloc(&R->ct, pan * es))) return rc;
-        if (m->next && (rc = alloc((void **)&R->cnt, pan * 4))) return rc;
-        if (m->hops && ((rc = alloc((void **)&R->wh, nn * 4)) || (rc = alloc((void **)&R->cht, pan * 4)))) return rc;
-        if ((rc = alloc((void **)&R->idx, (size_t)FWX_MAX_PATCH * 8))) return rc;
+        if ((rc = store_alloc(R->store, slab_of(m), R->count))) return rc;
         R->state_at = (m->fresh && m->kept_valid) ? 0 : -1;
         m->resume = R;            // complete: owned by the handle from here on
         hold.r = nullptr;
@@ -1484,8 +1370,8 @@ int fwx_matrix_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const
         }
         DeviceGuard g;
         if ((rc = g.enter(m->device))) return rc;
-        hipStream_t s = m->stream;
-        const size_t es = m->dtype == FWX_F64 ? 8 : 4;
+        const Slab v = slab_of(m);
+        hipStream_t s = v.s;
         const int c = R->pivot[(size_t)c_idx];
         R->valid_upto = 0;                           // until the resumed solve has finished
         // Any error return below leaves the handle in a state the next call can start from: nothing of this
@@ -1503,17 +1389,15 @@ int fwx_matrix_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const
                 m->rec_ready = 0;
             }
         } unwind{m, s};
-        std::vector<int64_t> dindex((size_t)count);  // offsets in the device arrays (pitch nd)
-        for (int32_t q = 0; q < count; ++q) dindex[(size_t)q] = (int64_t)dev_offset(m, index[q]);
-        for (int32_t q = 0; q < count; ++q) {        // the kept input first: the replay reads it
-            const size_t off = (size_t)dindex[(size_t)q];
-            FWX_HIP(hipMemcpyAsync((char *)m->rate0 + off * es, (const char *)rate_vals + (size_t)q * es, es,
-                                   hipMemcpyHostToDevice, s));
-            if (next_vals) FWX_HIP(hipMemcpyAsync(m->next0 + off, next_vals + q, 4, hipMemcpyHostToDevice, s));
-            if (hops_vals) FWX_HIP(hipMemcpyAsync(m->hops0 + off, hops_vals + q, 4, hipMemcpyHostToDevice, s));
-        }
-        rc = m->dtype == FWX_F64 ? resolve_typed<double>(m, count, dindex.data(), c_idx, s)
-                                 : resolve_typed<float>(m, count, dindex.data(), c_idx, s);
+        // the kept input first (the replay reads it), then the state at the start of step c, except the patched
+        // entries: replayed.  dindex: their offsets in the device arrays (pitch nd), alive until the solve
+        // below has synchronised the stream
+        std::vector<int64_t> dindex;
+        dindex.reserve((size_t)count);
+        if ((rc = patch_kept_input(m, v, count, index, rate_vals, next_vals, hops_vals, &dindex))) return rc;
+        if ((rc = restore_checkpoint(R->store, v, c_idx))) return rc;
+        rc = m->dtype == FWX_F64 ? replay_entries<double>(R->store, v, *R, c_idx, dindex.data(), dindex.size())
+                                 : replay_entries<float>(R->store, v, *R, c_idx, dindex.data(), dindex.size());
         if (rc) return rc;
         m->fresh = 0;
         m->rec_ready = 0;

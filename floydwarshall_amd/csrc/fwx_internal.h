@@ -654,31 +654,35 @@ inline fwx::PathLog plog_rows(fwx::PathLog p, size_t off)
 }
 
 struct MultiState;   // fwx_multi.hip: the partitions of a multi-device handle
+struct Resume;       // fwx_resume.h: what a resumable handle keeps
+struct SlabCells;
 
-// Resumable solves (fwx_matrix_enable_resume): what a handle keeps so
-// that a solve of a PATCHED input can start at a stored state instead of at pivot 0.
-//   panels      the time-k snapshots the fused engine produces anyway, for ALL pivots instead of two
-//               ping-pong buffers: w[k][j] = row k at time k, ct[k][i] = column k at time k (NaN at
-//               i == k), cnt / wh / cht likewise for next-hops and hops
-//   checkpoint  a copy of the state (rate, next, hops, the three trace arrays) at the START of step
-//               pivot[c], a multiple of 64
-// An input entry (i,j) is an OPERAND only in steps i and j, so patched entries cannot influence any
-// other entry before step m = min over their indices: the state at a checkpoint <= m is the stored
-// one except for the patched entries themselves, and those are replayed through the pivots before
-// the checkpoint from the stored panels (their operands (i,k), (k,j), k < m, are not patched).
-struct Resume {
-    int count = 0, ld = 0;
-    std::vector<int> pivot;                        // ascending, each a multiple of 64 in (0, n)
-    std::vector<void *> rate;
-    std::vector<int32_t *> next, hops, last, at_col, at_row;
-    void *w = nullptr, *ct = nullptr;              // n x n, n x ld elements of the handle's dtype
-    int32_t *cnt = nullptr, *wh = nullptr, *cht = nullptr;
-    int64_t *idx = nullptr;                        // FWX_MAX_PATCH entry indices of a resolve, on the device
-    int valid_upto = 0;    // panels of pivots [0, valid_upto) and checkpoints with pivot <= valid_upto
-                           // belong to the solve of the CURRENT kept input (0: nothing to resume from)
-    int state_at = -1;     // the live arrays hold the kept input brought to the start of step state_at
-                           // (0 right after an upload / patch; -1: unknown, e.g. solved twice over)
-};
+// crossover (single / double pass, ms; profiles/r03_double_pass_crossover.txt): f32 4096: 4.10 / 4.74,
+// 6144: 10.47 / 10.18, 8192: 21.2 / 20.0, 12288: 68.1 / 61.0, 16384: 152.0 / 135.3; f64 6144: 23.1 / 22.1,
+// 16384: 355 / 324 -- below ~6000 the side chain (five launches per 128 pivots) is the critical path
+constexpr int kDoublePassMinN = 6144;    // FWX_DOUBLE_PASS_MIN_N overrides
+// ... and with next-hops (the arg kernels; + trace, + hops), f32 only: FWX_DOUBLE_PASS_NEXT_MIN_N overrides.
+// (f64: the two-pass fused_main_arg_f64 is SLOWER than two launches, N = 16384 + next 486 -> 499 ms on
+// one box -- tools/runs/r03_run33.sh --, so f64 stays on the single pass unless the variable asks)
+// (round 4, after the panel flags and the 32-row column panels: tools/runs/r04_run42.sh, single / double pass, ms:
+//  + next 4096 5.8 / 6.0, 5120 9.9 / 9.7, 6144 16.2 / 16.0, 7168 24.3 / 23.8; + trace 4096 6.3 / 6.8, 6144 21.0 /
+//  17.9, 7168 32.0 / 26.1 -- the threshold was 8192)
+constexpr int kDoublePassNextMinN = 5120;
+// The partitioned handle's crossover with next-hops lags the single-device value on purpose: round 4 measured
+// one device only, and nobody has measured partitions in [5120, 8192) yet.
+constexpr int kMultiDoublePassNextMinN = 8192;
+// FWX_LOOKAHEAD_MIN_N / FWX_SYMMETRIC_MIN_N / FWX_DOUBLE_PASS_* override the thresholds (tests force each
+// schedule at small sizes, tuning runs switch one off with a huge value); read on every solve.
+inline int env_threshold(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    if (e && *e) {
+        char *end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end != e && v >= 0 && v <= INT32_MAX) return (int)v;
+    }
+    return dflt;
+}
 
 }  // namespace fwxi
 
@@ -718,7 +722,7 @@ struct fwx_matrix {
                            // values are themselves inside the domain keeps a "3".
     fwxi::MultiState *multi;   // non-null: a row-partitioned handle (fwx_matrix_create_multi); the
                            // single-device arrays above are then unused
-    fwxi::Resume *resume;  // non-null: panels of all pivots + state checkpoints are kept (f3)
+    fwxi::Resume *resume;  // non-null: panels of all pivots + state checkpoints are kept (f3, fwx_resume.h)
 };
 
 
@@ -729,7 +733,7 @@ int multi_upload(fwx_matrix *m, const void *rate, const int32_t *next, const int
 int multi_download(fwx_matrix *m, void *rate, int32_t *next, int32_t *hops);
 int multi_solve(fwx_matrix *m, const Opts &op, bool resumed = false);
 int multi_enable_resume(fwx_matrix *m, int32_t checkpoints);
-void multi_resume_dims(const fwx_matrix *m, uint64_t *cells, uint64_t *col_cells, uint64_t *w_cells);
+SlabCells multi_resume_cells(const fwx_matrix *m);    // summed over the partitions
 int multi_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const void *rate_vals,
                   const int32_t *next_vals, const int32_t *hops_vals, int c_idx, Opts op);
 // Does a patch with these values keep a matrix inside the domain (fwx.h) inside it?  rate >= +0 and not

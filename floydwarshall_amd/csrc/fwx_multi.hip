@@ -32,7 +32,7 @@
 #include "fwx_guard.h"
 #include "fwx_internal.h"
 #include "fwx_kernels.h"
-#include "fwx_replay.h"
+#include "fwx_resume.h"
 
 namespace fwxi {
 
@@ -167,19 +167,7 @@ struct Part {
     // solves -- the block's own rows of the all-pivot arrays below (bind_slot)
     void *wp[4] = {nullptr, nullptr, nullptr, nullptr};
     int32_t *whp[4] = {nullptr, nullptr, nullptr, nullptr};
-    // Resumable solves (fwx_matrix_enable_resume on a partitioned handle; Resume in fwx_internal.h holds
-    // the pivots and the validity marks): checkpoints = copies of this slab's arrays at the start of a
-    // checkpoint pivot; all-pivot panels = what the passes produce anyway, kept for every pivot --
-    // rw[k][j] = pivot row k at time k (EVERY partition keeps all of them: it receives them anyway, and the
-    // replay of a changed entry (i, j) needs rw[k][j] for all k beside its own rct[k][i]), rct[k][i] = pivot
-    // column k at time k for the local rows (NaN at i == k), rcnt / rwh / rcht likewise
-    struct {
-        std::vector<void *> rate;
-        std::vector<int32_t *> next, hops, last, at_col, at_row;
-        void *rw = nullptr, *rct = nullptr;
-        int32_t *rcnt = nullptr, *rwh = nullptr, *rcht = nullptr;
-        int64_t *idx = nullptr;
-    } R;
+    ResumeStore R;                          // this slab's checkpoints and all-pivot panels (fwx_resume.h)
     hipStream_t main = nullptr, side = nullptr;
     hipEvent_t rows_done = nullptr, main_done = nullptr, panel_done = nullptr;
     hipEvent_t w_ready[4] = {nullptr, nullptr, nullptr, nullptr}, main_free[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -346,20 +334,24 @@ struct DevRestore {
     ~DevRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-// (the partition's device must be current)
-static void part_resume_free(Part &q)
+// The partition that holds `row`.
+static int owner_of(const MultiState &M, int row)
 {
-    auto drop = [](void *p) { if (p) (void)hipFree(p); };
-    for (void *p : q.R.rate) drop(p);
-    for (auto *v : {&q.R.next, &q.R.hops, &q.R.last, &q.R.at_col, &q.R.at_row}) {
-        for (int32_t *p : *v) drop(p);
-        v->clear();
-    }
-    q.R.rate.clear();
-    drop(q.R.rw); drop(q.R.rct); drop(q.R.rcnt); drop(q.R.rwh); drop(q.R.rcht); drop(q.R.idx);
-    q.R.rw = q.R.rct = nullptr;
-    q.R.rcnt = q.R.rwh = q.R.rcht = nullptr;
-    q.R.idx = nullptr;
+    int p = 0;
+    while (p + 1 < M.parts && row >= M.part[p + 1].row0) ++p;
+    return p;
+}
+
+// Partition q as a slab (fwx_resume.h), work on its main stream.
+static Slab slab_of(const MultiState &M, const Part &q, size_t es)
+{
+    Slab v;
+    v.live = {q.rate, q.next, q.hops, q.plog.last, q.plog.at_col, q.plog.at_row};
+    v.kept.rate = q.rate0; v.kept.next = q.next0; v.kept.hops = q.hops0;
+    v.rows = q.rows; v.row0 = q.row0; v.nd = M.nd; v.ct_ld = q.ct_ld;
+    v.es = es;
+    v.s = q.main;
+    return v;
 }
 
 static void multi_free(MultiState *M)
@@ -390,7 +382,7 @@ static void multi_free(MultiState *M)
                         q.hops0, q.w[0], q.wh[0], q.ct, q.cnt, q.cht, q.upd, q.flag};
         for (void *b : bufs)
             if (b) (void)hipFree(b);
-        part_resume_free(q);
+        store_free(q.R);
         if (p == 0 && M->qscratch) (void)hipFree(M->qscratch);
     }
     delete M;
@@ -519,13 +511,7 @@ static int multi_copy(fwx_matrix *m, void *host_rate, int32_t *host_next, int32_
         if ((rc = copy(q.rate, (char *)host_rate, es))) return rc;
         if (q.next && (rc = copy(q.next, (char *)host_next, 4))) return rc;
         if (q.hops && (rc = copy(q.hops, (char *)host_hops, 4))) return rc;
-        if (to_device && q.next0)
-            FWX_HIP(hipMemcpyAsync(q.next0, q.next, (size_t)q.rows * nd * 4, hipMemcpyDeviceToDevice, q.main));
-        if (to_device && q.rate0) {
-            FWX_HIP(hipMemcpyAsync(q.rate0, q.rate, (size_t)q.rows * nd * es, hipMemcpyDeviceToDevice, q.main));
-            if (q.hops0)
-                FWX_HIP(hipMemcpyAsync(q.hops0, q.hops, (size_t)q.rows * nd * 4, hipMemcpyDeviceToDevice, q.main));
-        }
+        if (to_device && (rc = keep_live(slab_of(M, q, es)))) return rc;     // next0 of a traced handle; the kept input
     }
     for (int p = 0; p < M.parts; ++p) {
         if (!M.here(p)) continue;
@@ -787,19 +773,6 @@ static int finish_multi_solve(fwx_matrix *m, bool counting, const Opts &op)
     return FWX_OK;
 }
 
-// crossover thresholds of the double pass: those of the single-device engine (fwx_api.hip fused_range),
-// same environment overrides
-static int env_threshold_multi(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    if (e && *e) {
-        char *end = nullptr;
-        const long v = strtol(e, &end, 10);
-        if (end != e && v >= 0 && v <= INT32_MAX) return (int)v;
-    }
-    return dflt;
-}
-
 // The double pass on partitions: fused_range's schedule (fwx_api.hip) with owners and an exchange.
 // Blocks q = 0, 1, ... of 64 pivots; block q lives in panel set q & 3 on EVERY partition, so a pair
 // (2P, 2P + 1) is one contiguous 128-pivot panel and every partition's main kernel applies a pair per
@@ -828,8 +801,9 @@ static int multi_double_pass(fwx_matrix *m, const std::vector<Block> &blocks, Th
     while ((size_t)nb < blocks.size() && blocks[(size_t)nb].bt == Bq && blocks[(size_t)nb].k0 % Bq == 0) ++nb;
     for (int p = 0; p < P; ++p)
         if (M.part[p].rows <= 0 || M.part[p].row0 % Bq != 0) return FWX_OK;
-    const int min_n = with_next ? env_threshold_multi("FWX_DOUBLE_PASS_NEXT_MIN_N", sizeof(T) == 4 ? 8192 : INT32_MAX)
-                                : env_threshold_multi("FWX_DOUBLE_PASS_MIN_N", 6144);
+    // crossovers and their environment overrides: fwx_internal.h (with next-hops not the single-device value)
+    const int min_n = with_next ? env_threshold("FWX_DOUBLE_PASS_NEXT_MIN_N", sizeof(T) == 4 ? kMultiDoublePassNextMinN : INT32_MAX)
+                                : env_threshold("FWX_DOUBLE_PASS_MIN_N", kDoublePassMinN);
     if (m->n < min_n || nb < 4) return FWX_OK;
     int rc;
     MultiTimer &tm = M.timer;
@@ -1022,15 +996,14 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
         for (int p = 0; p < P; ++p) {
             Part &q = M.part[p];
             if (!here(p)) continue;
-            q.wp[slot] = (char *)q.R.rw + (size_t)blk.k0 * nd * sizeof(T);
-            q.whp[slot] = q.R.rwh ? q.R.rwh + (size_t)blk.k0 * nd : nullptr;
+            const PanelRows pr = store_panels(q.R, slab_of(M, q, sizeof(T)), blk.k0);
+            q.wp[slot] = pr.w; q.whp[slot] = pr.wh;
         }
     };
     auto bind_cols = [&](fwx::FusedArgs<T> &a, const Part &q, const Block &blk) {
         if (!rec) return;
-        a.ct = (T *)q.R.rct + (size_t)blk.k0 * q.ct_ld;
-        a.cnt = q.R.rcnt ? q.R.rcnt + (size_t)blk.k0 * q.ct_ld : nullptr;
-        a.cht = q.R.rcht ? q.R.rcht + (size_t)blk.k0 * q.ct_ld : nullptr;
+        const PanelRows pr = store_panels(q.R, slab_of(M, q, sizeof(T)), blk.k0);
+        a.ct = (T *)pr.ct; a.cnt = pr.cnt; a.cht = pr.cht;
     };
     for (int p = 0; p < P; ++p) {
         Part &q = M.part[p];
@@ -1073,24 +1046,12 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
     }
     // the state of every slab at the START of a checkpoint pivot (a block start), on a recording handle
     auto checkpoint = [&](int k0) -> int {
-        if (!rec) return FWX_OK;
-        for (size_t c = 0; c < rec->pivot.size(); ++c) {
-            if (rec->pivot[c] != k0) continue;
-            for (int p = 0; p < P; ++p) {
-                Part &q = M.part[p];
-                if (q.rows == 0 || !here(p)) continue;
-                int rc2 = set_dev(q.device);
-                if (rc2) return rc2;
-                const size_t cells = (size_t)q.rows * nd;
-                FWX_HIP(hipMemcpyAsync(q.R.rate[c], q.rate, cells * sizeof(T), hipMemcpyDeviceToDevice, q.main));
-                if (q.next) FWX_HIP(hipMemcpyAsync(q.R.next[c], q.next, cells * 4, hipMemcpyDeviceToDevice, q.main));
-                if (q.hops) FWX_HIP(hipMemcpyAsync(q.R.hops[c], q.hops, cells * 4, hipMemcpyDeviceToDevice, q.main));
-                if (q.plog.last) {
-                    FWX_HIP(hipMemcpyAsync(q.R.last[c], q.plog.last, cells * 4, hipMemcpyDeviceToDevice, q.main));
-                    FWX_HIP(hipMemcpyAsync(q.R.at_col[c], q.plog.at_col, cells * 4, hipMemcpyDeviceToDevice, q.main));
-                    FWX_HIP(hipMemcpyAsync(q.R.at_row[c], q.plog.at_row, cells * 4, hipMemcpyDeviceToDevice, q.main));
-                }
-            }
+        const int c = rec ? rec->checkpoint_at(k0) : -1;
+        for (int p = 0; p < P && c >= 0; ++p) {
+            Part &q = M.part[p];
+            if (q.rows == 0 || !here(p)) continue;
+            int rc2 = set_dev(q.device);
+            if (rc2 || (rc2 = save_checkpoint(q.R, slab_of(M, q, sizeof(T)), c))) return rc2;
         }
         return FWX_OK;
     };
@@ -1274,26 +1235,27 @@ int multi_solve(fwx_matrix *m, const Opts &op, bool resumed)
 }
 
 // ---- resumable solves on a partitioned handle (fwx_matrix_enable_resume / fwx_matrix_resolve) -------
-void multi_resume_dims(const fwx_matrix *m, uint64_t *cells, uint64_t *col_cells, uint64_t *w_cells)
+SlabCells multi_resume_cells(const fwx_matrix *m)
 {
     const MultiState &M = *m->multi;
-    *cells = *col_cells = *w_cells = 0;
+    SlabCells sum = {0, 0, 0};
     for (int p = 0; p < M.parts; ++p) {
-        const Part &q = M.part[p];
         if (!M.here(p)) continue;
-        *cells += (uint64_t)q.rows * M.nd;
-        *col_cells += (uint64_t)M.nd * (q.ct_ld ? q.ct_ld : 4);
-        *w_cells += (uint64_t)M.nd * M.nd;                   // every partition keeps all pivot rows
+        const SlabCells d = slab_cells(M.part[p].rows, M.nd, M.part[p].ct_ld);
+        sum.cells += d.cells;
+        sum.col_cells += d.col_cells;
+        sum.w_cells += d.w_cells;                            // every partition keeps all pivot rows
     }
+    return sum;
 }
 
 int multi_enable_resume(fwx_matrix *m, int32_t checkpoints)
 {
     MultiState &M = *m->multi;
     DevRestore keep;
-    const int n = m->n, nd = M.nd;
     const size_t es = m->dtype == FWX_F64 ? 8 : 4;
     fail_point();
+    // a failure (an allocation, or the throw above) leaves nothing behind: the handle stays usable
     struct Holder {
         Resume *r = new Resume();
         MultiState *M;
@@ -1301,48 +1263,22 @@ int multi_enable_resume(fwx_matrix *m, int32_t checkpoints)
         {
             if (!r) return;
             for (int p = 0; p < M->parts; ++p)
-                if (M->here(p) && hipSetDevice(M->part[p].device) == hipSuccess) part_resume_free(M->part[p]);
+                if (M->here(p) && hipSetDevice(M->part[p].device) == hipSuccess) store_free(M->part[p].R);
             delete r;
         }
     } hold;
     hold.M = &M;
     Resume *R = hold.r;
-    R->ld = 0;
-    // checkpoints at the multiples of 64 closest to q * n / (checkpoints + 1) that are block starts: a
-    // block never straddles two partitions, so inside partition p blocks start at row0 + 64 t
-    for (int q = 1; q <= checkpoints; ++q) {
-        const int c = (int)(((int64_t)n * q / (checkpoints + 1) + 32) / 64 * 64);
-        if (c <= 0 || c >= n || (!R->pivot.empty() && c <= R->pivot.back())) continue;
-        int p = 0;
-        while (p + 1 < M.parts && c >= M.part[p + 1].row0) ++p;
-        if ((c - M.part[p].row0) % FWX_FUSED_BLOCK != 0) continue;
-        R->pivot.push_back(c);
-    }
+    // only block starts: a block never straddles two partitions, so inside partition p blocks start at row0 + 64 t
+    R->pivot = checkpoint_pivots(m->n, checkpoints, [&](int c) {
+        return (c - M.part[owner_of(M, c)].row0) % FWX_FUSED_BLOCK == 0;
+    });
     R->count = (int)R->pivot.size();
-    auto alloc = [&](void **ptr, size_t bytes) -> int { FWX_HIP(hipMalloc(ptr, bytes ? bytes : 16)); return FWX_OK; };
     for (int p = 0; p < M.parts; ++p) {
         Part &q = M.part[p];
         if (!M.here(p)) continue;
         int rc = set_dev(q.device);
-        if (rc) return rc;
-        const size_t cells = (size_t)q.rows * nd, pan = (size_t)nd * (q.ct_ld ? q.ct_ld : 4);
-        for (int c = 0; c < R->count; ++c) {
-            void *ptr = nullptr;
-            if ((rc = alloc(&ptr, cells * es))) return rc;
-            q.R.rate.push_back(ptr);
-            if (q.next) { if ((rc = alloc(&ptr, cells * 4))) return rc; q.R.next.push_back((int32_t *)ptr); }
-            if (q.hops) { if ((rc = alloc(&ptr, cells * 4))) return rc; q.R.hops.push_back((int32_t *)ptr); }
-            if (q.plog.last)
-                for (auto *v : {&q.R.last, &q.R.at_col, &q.R.at_row}) {
-                    if ((rc = alloc(&ptr, cells * 4))) return rc;
-                    v->push_back((int32_t *)ptr);
-                }
-        }
-        if ((rc = alloc(&q.R.rw, (size_t)nd * nd * es)) || (rc = alloc(&q.R.rct, pan * es))) return rc;
-        if (q.next && (rc = alloc((void **)&q.R.rcnt, pan * 4))) return rc;
-        if (q.hops && ((rc = alloc((void **)&q.R.rwh, (size_t)nd * nd * 4)) || (rc = alloc((void **)&q.R.rcht, pan * 4))))
-            return rc;
-        if ((rc = alloc((void **)&q.R.idx, (size_t)FWX_MAX_PATCH * 8))) return rc;
+        if (rc || (rc = store_alloc(q.R, slab_of(M, q, es), R->count))) return rc;
     }
     R->state_at = (m->fresh && m->kept_valid) ? 0 : -1;
     m->resume = R;
@@ -1350,11 +1286,26 @@ int multi_enable_resume(fwx_matrix *m, int32_t checkpoints)
     return R->count;
 }
 
-void multi_resume_free(fwx_matrix *m)
+// The patched entries (indices of the caller's n x n view) into the kept input, each on the partition that
+// owns its row (an entry of a row another process holds is skipped); local, if given: per partition, their
+// offsets in its slab.
+static int multi_patch_kept(fwx_matrix *m, int32_t count, const int64_t *index, const void *rate_vals,
+                            const int32_t *next_vals, const int32_t *hops_vals, std::vector<int64_t> *local = nullptr)
 {
-    if (!m->resume) return;
-    delete m->resume;          // (the partitions' arrays go with the partitions: multi_free)
-    m->resume = nullptr;
+    MultiState &M = *m->multi;
+    const size_t es = m->dtype == FWX_F64 ? 8 : 4;
+    for (int32_t e = 0; e < count; ++e) {
+        const int row = (int)(index[e] / m->n), col = (int)(index[e] % m->n);
+        const int p = owner_of(M, row);
+        Part &q = M.part[p];
+        if (!M.here(p)) continue;
+        int rc = set_dev(q.device);
+        if (rc) return rc;
+        const size_t off = (size_t)(row - q.row0) * M.nd + col;
+        if (local) local[p].push_back((int64_t)off);
+        if ((rc = patch_kept(slab_of(M, q, es), off, e, rate_vals, next_vals, hops_vals))) return rc;
+    }
+    return FWX_OK;
 }
 
 // The resumed path of fwx_matrix_resolve: patch the kept input, restore checkpoint c_idx on every
@@ -1366,59 +1317,18 @@ static int multi_resolve_typed(fwx_matrix *m, int32_t count, const int64_t *inde
                                const int32_t *next_vals, const int32_t *hops_vals, int c_idx)
 {
     MultiState &M = *m->multi;
-    Resume &R = *m->resume;
-    const int nd = M.nd, c = R.pivot[(size_t)c_idx];
     int rc;
     std::vector<int64_t> local[FWX_MAX_PARTS];
-    for (int32_t e = 0; e < count; ++e) {
-        const int row = (int)(index[e] / m->n), col = (int)(index[e] % m->n);
-        int p = 0;
-        while (p + 1 < M.parts && row >= M.part[p + 1].row0) ++p;
-        Part &q = M.part[p];
-        if (!M.here(p)) continue;
-        if ((rc = set_dev(q.device))) return rc;
-        const size_t off = (size_t)(row - q.row0) * nd + col;
-        local[p].push_back((int64_t)off);
-        FWX_HIP(hipMemcpyAsync((T *)q.rate0 + off, (const T *)rate_vals + e, sizeof(T), hipMemcpyHostToDevice, q.main));
-        if (next_vals) FWX_HIP(hipMemcpyAsync(q.next0 + off, next_vals + e, 4, hipMemcpyHostToDevice, q.main));
-        if (hops_vals) FWX_HIP(hipMemcpyAsync(q.hops0 + off, hops_vals + e, 4, hipMemcpyHostToDevice, q.main));
-    }
+    if ((rc = multi_patch_kept(m, count, index, rate_vals, next_vals, hops_vals, local))) return rc;
     for (int p = 0; p < M.parts; ++p) {
         Part &q = M.part[p];
         if (q.rows == 0 || !M.here(p)) continue;
         if ((rc = set_dev(q.device))) return rc;
-        const size_t cells = (size_t)q.rows * nd, ci = (size_t)c_idx;
-        FWX_HIP(hipMemcpyAsync(q.rate, q.R.rate[ci], cells * sizeof(T), hipMemcpyDeviceToDevice, q.main));
-        if (q.next) FWX_HIP(hipMemcpyAsync(q.next, q.R.next[ci], cells * 4, hipMemcpyDeviceToDevice, q.main));
-        if (q.hops) FWX_HIP(hipMemcpyAsync(q.hops, q.R.hops[ci], cells * 4, hipMemcpyDeviceToDevice, q.main));
-        if (q.plog.last) {
-            FWX_HIP(hipMemcpyAsync(q.plog.last, q.R.last[ci], cells * 4, hipMemcpyDeviceToDevice, q.main));
-            FWX_HIP(hipMemcpyAsync(q.plog.at_col, q.R.at_col[ci], cells * 4, hipMemcpyDeviceToDevice, q.main));
-            FWX_HIP(hipMemcpyAsync(q.plog.at_row, q.R.at_row[ci], cells * 4, hipMemcpyDeviceToDevice, q.main));
-        }
+        const Slab v = slab_of(M, q, sizeof(T));
+        if ((rc = restore_checkpoint(q.R, v, c_idx))) return rc;
         if (local[p].empty()) continue;
-        ReplayTargets tg;
-        memset(&tg, 0, sizeof(tg));
-        for (int t = 0; t <= c_idx; ++t) {
-            const int k = tg.count++;
-            tg.pivot[k] = R.pivot[(size_t)t];
-            tg.rate[k] = q.R.rate[(size_t)t];
-            tg.next[k] = q.next ? q.R.next[(size_t)t] : nullptr;
-            tg.hops[k] = q.hops ? q.R.hops[(size_t)t] : nullptr;
-            tg.last[k] = q.plog.last ? q.R.last[(size_t)t] : nullptr;
-        }
-        {
-            const int k = tg.count++;
-            tg.pivot[k] = c;
-            tg.rate[k] = q.rate; tg.next[k] = q.next; tg.hops[k] = q.hops; tg.last[k] = q.plog.last;
-        }
-        FWX_HIP(hipMemcpyAsync(q.R.idx, local[p].data(), local[p].size() * 8, hipMemcpyHostToDevice, q.main));
-        hipLaunchKernelGGL(replay_entries_kernel<T>, dim3((unsigned)local[p].size()), dim3(64), 0, q.main, q.R.idx, nd,
-                           q.ct_ld, q.row0, c, (const T *)q.rate0, q.next ? q.next0 : nullptr,
-                           q.hops ? q.hops0 : nullptr, (const T *)q.R.rw, (const T *)q.R.rct, q.next ? q.R.rcnt : nullptr,
-                           q.R.rwh, q.R.rcht, tg);
-        FWX_HIP(hipGetLastError());
-        FWX_HIP(hipStreamSynchronize(q.main));      // (local[p] is read by the copy above)
+        if ((rc = replay_entries<T>(q.R, v, *m->resume, c_idx, local[p].data(), local[p].size()))) return rc;
+        FWX_HIP(hipStreamSynchronize(q.main));      // (local[p] is read by the replay's copy)
     }
     return FWX_OK;
 }
@@ -1474,9 +1384,7 @@ int multi_enable_path_log(fwx_matrix *m)
 static int read_rate(fwx_matrix *m, int src, int dst, double *rate_out)
 {
     MultiState &M = *m->multi;
-    int p = 0;
-    while (p + 1 < M.parts && src >= M.part[p + 1].row0) ++p;
-    Part &q = M.part[p];
+    Part &q = M.part[owner_of(M, src)];
     int rc = set_dev(q.device);
     if (rc) return rc;
     const size_t off = (size_t)(src - q.row0) * M.nd + dst;
@@ -1507,9 +1415,7 @@ static int host_walk(fwx_matrix *m, int32_t src, int32_t dst, int32_t *path_out,
 {
     MultiState &M = *m->multi;
     auto next_of = [&](int a, int32_t *out) -> int {
-        int p = 0;
-        while (p + 1 < M.parts && a >= M.part[p + 1].row0) ++p;
-        Part &q = M.part[p];
+        Part &q = M.part[owner_of(M, a)];
         int rc = set_dev(q.device);
         if (rc) return rc;
         FWX_HIP(hipMemcpyAsync(out, q.next + (size_t)(a - q.row0) * M.nd + dst, 4, hipMemcpyDeviceToHost, q.main));
@@ -1622,9 +1528,7 @@ int multi_keep_input(fwx_matrix *m)
         if (q.next && !q.next0) FWX_HIP(hipMalloc((void **)&q.next0, cells * 4 ? cells * 4 : 16));
         if (q.hops) FWX_HIP(hipMalloc((void **)&q.hops0, cells * 4 ? cells * 4 : 16));
         if (m->fresh) {
-            FWX_HIP(hipMemcpyAsync(q.rate0, q.rate, cells * es, hipMemcpyDeviceToDevice, q.main));
-            if (q.next) FWX_HIP(hipMemcpyAsync(q.next0, q.next, cells * 4, hipMemcpyDeviceToDevice, q.main));
-            if (q.hops) FWX_HIP(hipMemcpyAsync(q.hops0, q.hops, cells * 4, hipMemcpyDeviceToDevice, q.main));
+            if ((rc = keep_live(slab_of(M, q, es)))) return rc;
             FWX_HIP(hipStreamSynchronize(q.main));
         }
     }
@@ -1642,27 +1546,11 @@ int multi_patch_input(fwx_matrix *m, int32_t count, const int64_t *index, const 
     int rc;
     if (m->resume) m->resume->valid_upto = 0;      // the kept input changes without a replay
     if (m->dom_known && !patch_keeps_domain(m, count, rate_vals, next_vals)) m->dom_known = 0;
-    for (int32_t e = 0; e < count; ++e) {
-        const int row = (int)(index[e] / m->n), col = (int)(index[e] % m->n);
-        int p = 0;
-        while (p + 1 < M.parts && row >= M.part[p + 1].row0) ++p;
-        Part &q = M.part[p];
-        if (!M.here(p)) continue;                  // (an entry of a row another process holds)
-        if ((rc = set_dev(q.device))) return rc;
-        const size_t off = (size_t)(row - q.row0) * M.nd + col;
-        FWX_HIP(hipMemcpyAsync((char *)q.rate0 + off * es, (const char *)rate_vals + (size_t)e * es, es,
-                               hipMemcpyHostToDevice, q.main));
-        if (next_vals) FWX_HIP(hipMemcpyAsync(q.next0 + off, next_vals + e, 4, hipMemcpyHostToDevice, q.main));
-        if (hops_vals) FWX_HIP(hipMemcpyAsync(q.hops0 + off, hops_vals + e, 4, hipMemcpyHostToDevice, q.main));
-    }
+    if ((rc = multi_patch_kept(m, count, index, rate_vals, next_vals, hops_vals))) return rc;
     for (int p = 0; p < M.parts; ++p) {
         Part &q = M.part[p];
         if (!M.here(p)) continue;
-        if ((rc = set_dev(q.device))) return rc;
-        const size_t cells = (size_t)q.rows * M.nd;
-        FWX_HIP(hipMemcpyAsync(q.rate, q.rate0, cells * es, hipMemcpyDeviceToDevice, q.main));
-        if (q.next) FWX_HIP(hipMemcpyAsync(q.next, q.next0, cells * 4, hipMemcpyDeviceToDevice, q.main));
-        if (q.hops) FWX_HIP(hipMemcpyAsync(q.hops, q.hops0, cells * 4, hipMemcpyDeviceToDevice, q.main));
+        if ((rc = set_dev(q.device)) || (rc = restore_kept(slab_of(M, q, es)))) return rc;
     }
     for (int p = 0; p < M.parts; ++p) {
         if (!M.here(p)) continue;
@@ -1679,7 +1567,8 @@ void multi_destroy(fwx_matrix *m)
 {
     multi_free(m->multi);
     m->multi = nullptr;
-    multi_resume_free(m);
+    delete m->resume;          // (the partitions' stores went with the partitions: multi_free)
+    m->resume = nullptr;
 }
 
 }  // namespace fwxi

@@ -270,3 +270,126 @@ def test_session_resumes_after_price_changes_and_answers_like_a_fresh_session(de
     r2, n2, h2 = fresh.solved_matrix()
     assert_bits_equal(r1, r2, "rate")
     assert np.array_equal(n1, n2) and np.array_equal(h1, h2)
+
+
+def _move_down(dm, cur, idx, factor, with_hops=True):
+    """One accepted change: the entries idx of the running input `cur` = (rate, next, hops) move down a
+    little (inside D2's domain); returns the pivot the resumed solve started at and the oracle's answer."""
+    cur_r, cur_n, cur_h = cur
+    n = cur_r.shape[0]
+    idx = np.asarray(idx, dtype=np.int64)
+    vals = (cur_r.reshape(-1)[idx] * cur_r.dtype.type(factor)).astype(cur_r.dtype)
+    nv = (idx % n).astype(np.int32)
+    hv = np.ones(len(idx), dtype=np.int32)
+    cur_r.reshape(-1)[idx] = vals
+    cur_n.reshape(-1)[idx] = nv
+    cur_h.reshape(-1)[idx] = hv
+    started = dm.resolve(idx, vals, nv, hv if with_hops else None)
+    er, en, eh = cur_r.copy(), cur_n.copy(), cur_h.copy()
+    oracle.relax(er, en, eh)
+    gr, gn, gh = dm.download()
+    assert_bits_equal(gr, er, "rate (resumed at %d)" % started)
+    assert_bits_equal(gn, en, "next (resumed at %d)" % started)
+    if with_hops:
+        assert_bits_equal(gh, eh, "hops (resumed at %d)" % started)
+    return started
+
+
+def _same_lists_as_a_fresh_solve(dm, cur, rnd, pairs=50):
+    n = cur[0].shape[0]
+    src = rnd.integers(0, n, pairs).astype(np.int32)
+    dst = rnd.integers(0, n, pairs).astype(np.int32)
+    assert dm.query_exact_batch(src, dst, cap=16 * n) == _fresh_lists(n, cur[0].dtype, cur[0], cur[1], src, dst)
+
+
+@pytest.mark.parametrize("n,dtype,pivots", [(130, np.float32, [64]), (255, np.float64, [64, 192])],
+                         ids=["n130-f32-pitch132", "n255-f64-pitch256"])
+def test_resolve_on_a_padded_single_device_handle(n, dtype, pivots):
+    """Odd orders: the device arrays, the checkpoints and the all-pivot panels have the padded pitch, the
+    caller's indices the real one.  Changes in the last real row and column, just past the first checkpoint
+    and at (1, 0), each resumed where it must and equal to a from-scratch solve."""
+    rnd = np.random.default_rng(130)
+    rate, nxt, hops = synth.make("d2", n, dtype, seed=21)
+    with engine.DeviceMatrix(n, dtype, with_next=True, with_hops=True) as dm:
+        dm.enable_path_log()
+        dm.keep_input()
+        assert dm.enable_resume(2) == len(pivots)
+        dm.upload(rate, nxt, hops)
+        dm.solve()
+        cur = (rate.copy(), nxt.copy(), hops.copy())
+        assert _move_down(dm, cur, [(n - 1) * n + (n - 2)], 0.95) == max(p for p in pivots if p <= n - 2)
+        _same_lists_as_a_fresh_solve(dm, cur, rnd)
+        assert _move_down(dm, cur, [(pivots[0] + 1) * n + pivots[0]], 0.96) == pivots[0]
+        assert _move_down(dm, cur, [1 * n + 0], 0.97) == 0
+
+
+def test_resolve_on_unaligned_slabs():
+    """300 rows over three partitions: slabs at rows 0 / 100 / 200, column panels of pitch 100 beside rows of
+    pitch 300, one checkpoint (64).  A diagonal-adjacent pair inside the last slab, then a pair whose two
+    entries live in different slabs."""
+    n = 300
+    rnd = np.random.default_rng(300)
+    rate, nxt, hops = synth.make("d2", n, np.float64, seed=22)
+    with engine.DeviceMatrix(n, np.float64, with_next=True, with_hops=True, devices=[0, 0, 0]) as dm:
+        assert [dm.part_rows(p) for p in range(3)] == [(0, 100), (100, 100), (200, 100)]
+        dm.enable_path_log()
+        dm.keep_input()
+        assert dm.enable_resume(3) == 1                        # of 64, 128 and 256 only 64 is a block start
+        dm.upload(rate, nxt, hops)
+        dm.solve()
+        cur = (rate.copy(), nxt.copy(), hops.copy())
+        assert _move_down(dm, cur, [250 * n + 251, 251 * n + 250], 0.95) == 64
+        assert _move_down(dm, cur, [150 * n + 250, 250 * n + 150], 0.96) == 64
+        _same_lists_as_a_fresh_solve(dm, cur, rnd)
+
+
+@pytest.mark.parametrize("devices,traced,expected", [(None, False, 9469952), (None, True, 18907136),
+                                                     ([0, 0], False, 10518528), ([0, 0], True, 19955712)],
+                         ids=["one-device", "one-device-traced", "P2", "P2-traced"])
+def test_resume_bytes_is_pinned(devices, traced, expected):
+    """The session sizes its checkpoint count by this figure (host/session.cpp).  n = 512 f32 + next, three
+    checkpoints; the literals are what commit 795d23a ("Batched small solves") returned.  One device: 3
+    checkpoints x 512^2 x (4 + 4) + panels 512^2 x (4 + 4 + 4) + 4096 x 8 index bytes, the trace adds
+    3 x 512^2 x 12; two partitions keep all pivot rows each (+ 512^2 x 4) and still count ONE index buffer."""
+    import ctypes
+    from floydwarshall_amd._lib import lib
+    with engine.DeviceMatrix(512, np.float32, with_next=True, devices=devices) as dm:
+        if traced:
+            dm.enable_path_log()
+        out = ctypes.c_uint64(0)
+        assert lib().fwx_matrix_resume_bytes(dm._h, 3, ctypes.byref(out)) == 0
+        print("resume_bytes", devices, traced, out.value)
+        assert out.value == expected
+
+
+def test_a_failed_enable_resume_on_partitions_leaves_a_usable_handle():
+    """The injected bad_alloc at enable_resume's allocation point (fwx_test_fail_after: host side, no GPU
+    fault): nothing is kept, the handle solves, a resolve starts at 0, and a second enable_resume works."""
+    from floydwarshall_amd._lib import FWX_ERR_OOM, lib
+    n = 256
+    rate, nxt, hops = synth.make("d2", n, np.float32, seed=23)
+    with engine.DeviceMatrix(n, np.float32, with_next=True, devices=[0, 0]) as dm:
+        dm.keep_input()
+        try:
+            lib().fwx_test_fail_after(1)
+            with pytest.raises(engine.FwxError) as e:
+                dm.enable_resume(2)
+        finally:
+            lib().fwx_test_fail_after(0)
+        assert e.value.status == FWX_ERR_OOM
+        dm.upload(rate, nxt)
+        dm.solve()
+        er, en = rate.copy(), nxt.copy()
+        oracle.relax(er, en)
+        gr, gn, _ = dm.download()
+        assert_bits_equal(gr, er, "rate after the failed enable_resume")
+        assert_bits_equal(gn, en, "next after the failed enable_resume")
+        cur = (rate.copy(), nxt.copy(), hops.copy())
+        assert _move_down(dm, cur, [200 * n + 201], 0.95, with_hops=False) == 0
+        # two checkpoints of n = 256 fall on 64 and 192 (multiples of 64 nearest to 85 and 170), both block
+        # starts of the slabs at rows 0 and 128
+        assert dm.enable_resume(2) == 2
+        dm.upload(cur[0], cur[1])
+        dm.solve()
+        assert _move_down(dm, cur, [200 * n + 150], 0.95, with_hops=False) == 64
+        assert _move_down(dm, cur, [200 * n + 201], 0.96, with_hops=False) == 192
