@@ -321,12 +321,23 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
 // Shaped like relax_k: 256 threads with one 16-byte vector each, RPB rows per workgroup, UNROLL rows of
 // unconditional loads in flight, the same visit_tile mapping, `nt_below` split and GL-lane group store.
 // A thread keeps its slice of the NP pivot rows in registers (NaN at column k+t: skip j == k; NaN in
-// clamped lanes), the workgroup stages ct[t][rows] in LDS (contiguous reads of the panel: no strided
-// gather).  Each loaded vector is folded through t = 0 .. NP-1 in ascending order with
-//   x = (x < c && j != i) ? c : x,   c = ct[t][i] * w[t][j]
+// clamped lanes), the workgroup stages ct[t][rows] in LDS, row-major (s_ct[row][t], so a row's NP values
+// are one or two 16-byte reads; contiguous reads of the panel: no strided gather).  Each loaded vector
+// is folded through t = 0 .. NP-1 in ascending order with
+//   x = x < c ? c : x,   c = ct[t][i] * w[t][j]
 // -- one IEEE multiply, the strict ordered compare, never `max`: no domain assumption enters the per-k
-// engine -- and a group stores once if any of its lanes ended different from what it loaded.  U counts
-// every improvement of every fold step, which is what NP launches of relax_k count.
+// engine.  The fold step is three vector instructions and nothing else (round 10): the diagonal (j == i
+// never updates) is protected outside the per-pivot loop, by folding that one component from +inf and
+// giving it its loaded bits back, and only in the tiles whose rows meet their columns (DIAG, a
+// workgroup-uniform choice like the cache-policy one); whether a vector changed is read off afterwards,
+// from an integer comparison with the loaded bits.  A group stores once if any of its lanes ended
+// different from what it loaded.  U counts every improvement of every fold step, which is what NP
+// launches of relax_k count (the +inf component never counts).
+//
+// The prologue issues every load a workgroup starts with back to back -- its pivot-column value, the NP
+// vectors of W and the first UNROLL rows of the stream, all from addresses valid in every lane -- and
+// patches the NaNs in with selects, so the barrier waits for one overlapped group of loads (round 10;
+// before, NP exec-masked loads each waited for alone, and the stream started after the barrier).
 // -------------------------------------------------------------------------------------------------
 template <typename T, int W, int RPB, int UNROLL, bool COUNT, int GL, int NP>
 __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct, int ct_ld, int n, int k,
@@ -335,11 +346,12 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
 {
     using L = Lanes<T, W>;
     using V = typename L::V;
+    using Bits = std::conditional_t<sizeof(T) == 4, uint32_t, uint64_t>;
     constexpr int SW = 256 * W;
     static_assert(GL == 1 || GL == 2 || GL == 4 || GL == 8, "store group: 1, 2, 4 or 8 lanes");
     static_assert(NP * RPB <= 256, "one thread per staged pivot-column value");
 
-    __shared__ T s_ct[NP][RPB];
+    __shared__ __attribute__((aligned(16))) T s_ct[RPB][NP];
     __shared__ unsigned int s_cnt;
 
     const int t = threadIdx.x;
@@ -348,76 +360,128 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
     const int chunk = bid / nstrips;
     const int r_begin = chunk * RPB;
     const int r_cnt = min(RPB, n - r_begin);
-
-    // Pivot columns -> LDS from the panel (row k+t of it already holds NaN: skip i == k).
-    if (t < NP * RPB) {
-        const int tt = t / RPB, r = t % RPB;
-        if (r < r_cnt) s_ct[tt][r] = ct[(size_t)tt * ct_ld + r_begin + r];
-    }
     if (COUNT && t == 0) s_cnt = 0;
 
-    // Pivot row segments -> registers, clamped past the end of the row as in relax_k.
+    // My 16-byte column slice, clamped past the end of the row as in relax_k.
     const int c0 = strip * SW + t * W;
     const bool own = c0 < n;                  // false: a clamped lane (never stores)
     const int col = own ? c0 : n - W;
-    V p[NP];
-#pragma unroll
-    for (int tt = 0; tt < NP; ++tt) {
-        if (own) {
-            p[tt] = *reinterpret_cast<const V *>(w + (size_t)tt * n + c0);
-#pragma unroll
-            for (int c = 0; c < W; ++c)
-                if (c0 + c == k + tt) L::set(p[tt], c, quiet_nan<T>());
-        } else {
-            p[tt] = L::splat(quiet_nan<T>());
-        }
-    }
-    __syncthreads();
-
-    unsigned int my_updates = 0;
-    T *const base = rate + (size_t)r_begin * n + col;
+    // Row r of the tile is at a workgroup-uniform base plus my 32-bit byte offset: a form the compiler can
+    // address with a scalar base and one offset register (it does for the W loads) instead of keeping a
+    // 64-bit address per row in flight.
+    const unsigned boff = (unsigned)col * (unsigned)sizeof(T);
+    auto at = [&](const T *q, int r) {
+        const char *const row = reinterpret_cast<const char *>(q + (size_t)r * n);
+        return const_cast<T *>(reinterpret_cast<const T *>(row + boff));
+    };
+    T *const base = rate + (size_t)r_begin * n;
     const int g0 = (int)(__lane_id() & ~(GL - 1));   // first lane of my store group
+    unsigned int my_updates = 0;
+    V p[NP];                                  // my slice of the NP pivot rows
 
     // One row of one vector through the NP pivots; all lanes of the wave are active (r is uniform).
-    auto relax_vec = [&](const V &x, int r) {
-        const int i = r_begin + r;
+    // DIAG: the tile may hold diagonal elements (j == i never updates).  Such a component folds from +inf,
+    // which no candidate beats (`+inf < c` is false for every c, NaN included), and gets its loaded bits
+    // back afterwards; the fold step itself carries no diagonal term.
+    auto relax_vec = [&](const V &x, int r, auto dg) {
+        constexpr bool DIAG = decltype(dg)::value;
+        const int d = r_begin + r - col;      // the component of mine on the diagonal, if 0 <= d < W
         V nx = x;
-        bool changed = false;
+        if constexpr (DIAG) {
+#pragma unroll
+            for (int c = 0; c < W; ++c)
+                L::set(nx, c, c == d ? (T)__builtin_huge_val() : L::get(x, c));
+        }
+        T cik[NP];
+#pragma unroll
+        for (int tt = 0; tt < NP; ++tt) cik[tt] = s_ct[r][tt];
 #pragma unroll
         for (int tt = 0; tt < NP; ++tt) {
-            const T cik = s_ct[tt][r];
+            T cand[W];
+            bool up[W];
 #pragma unroll
             for (int c = 0; c < W; ++c) {
-                const T cand = cik * L::get(p[tt], c);
-                const bool up = L::get(nx, c) < cand && col + c != i;
-                L::set(nx, c, up ? cand : L::get(nx, c));
-                changed |= up;
-                if (COUNT) my_updates += up;
+                cand[c] = cik[tt] * L::get(p[tt], c);
+                up[c] = L::get(nx, c) < cand[c];
+            }
+            // All W compares before the first select: a select that directly follows the compare whose
+            // mask it reads costs idle issue slots (the compiler pads the pair with s_nop).
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                L::set(nx, c, up[c] ? cand[c] : L::get(nx, c));
+                if (COUNT) my_updates += up[c];
             }
         }
+        // The fold is monotone under the strict compare: a component improved at some step exactly when
+        // its final bits differ from the loaded ones (a NaN or -0.0 that no candidate beats keeps its bits).
+        Bits diff = 0;
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            if constexpr (DIAG) L::set(nx, c, c == d ? L::get(x, c) : L::get(nx, c));
+            diff |= __builtin_bit_cast(Bits, L::get(nx, c)) ^ __builtin_bit_cast(Bits, L::get(x, c));
+        }
+        const bool changed = diff != 0;
         bool st = changed;
         if constexpr (GL > 1) {
             const unsigned long long m = __ballot(changed);
             st = own && ((m >> g0) & ((1ull << GL) - 1)) != 0;
         }
-        if (st) *reinterpret_cast<V *>(base + (size_t)r * n) = nx;
+        if (st) *reinterpret_cast<V *>(at(base, r)) = nx;
     };
 
-    auto stream = [&](auto nt) {
+    auto stream = [&](auto nt, auto dg) {
         constexpr bool NT = decltype(nt)::value;
         int r = 0;
-        for (; r + UNROLL <= r_cnt; r += UNROLL) {
-            V x[UNROLL];
+        // Prologue: everything the workgroup's first fold needs is requested back to back, from addresses
+        // that are valid in every lane -- the staged pivot-column value, the NP vectors of W (from the
+        // clamped column) and the first UNROLL rows of the stream, which depend on none of the others --
+        // so that one wait covers one overlapped group of loads.  The NaN patches are selects afterwards.
+        const int stt = t / RPB % NP, sr = min(t % RPB, r_cnt - 1);
+        const T cv = ct[(size_t)stt * ct_ld + r_begin + sr];
 #pragma unroll
-            for (int u = 0; u < UNROLL; ++u) x[u] = load_vec<V, NT>(base + (size_t)(r + u) * n);
+        for (int tt = 0; tt < NP; ++tt) p[tt] = *reinterpret_cast<const V *>(at(w, tt));
+        const bool head = UNROLL <= r_cnt;    // workgroup-uniform
+        V x0[UNROLL];
+        if (head) {
 #pragma unroll
-            for (int u = 0; u < UNROLL; ++u) relax_vec(x[u], r + u);
+            for (int u = 0; u < UNROLL; ++u) x0[u] = load_vec<V, NT>(at(base, u));
         }
-        for (; r < r_cnt; ++r) relax_vec(load_vec<V, NT>(base + (size_t)r * n), r);
+        // Pivot columns -> LDS (row k+t of the panel already holds NaN: skip i == k).
+        if (t < NP * RPB && t % RPB < r_cnt) s_ct[sr][stt] = cv;
+        // NaN at column k+t: skip j == k; NaN everywhere in a clamped lane.
+#pragma unroll
+        for (int tt = 0; tt < NP; ++tt)
+#pragma unroll
+            for (int c = 0; c < W; ++c)
+                L::set(p[tt], c, !own || col + c == k + tt ? quiet_nan<T>() : L::get(p[tt], c));
+        __syncthreads();
+        if (head) {
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) relax_vec(x0[u], u, dg);
+            r = UNROLL;
+        }
+        if constexpr (RPB > UNROLL) {
+            for (; r + UNROLL <= r_cnt; r += UNROLL) {
+                V x[UNROLL];
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) x[u] = load_vec<V, NT>(at(base, r + u));
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) relax_vec(x[u], r + u, dg);
+            }
+        }
+        for (; r < r_cnt; ++r) relax_vec(load_vec<V, NT>(at(base, r)), r, dg);
     };
-    // workgroup-uniform: one of the two instantiations, never both
-    if (bid < nt_below) stream(std::true_type());
-    else stream(std::false_type());
+    // workgroup-uniform: one of the four instantiations, never two.  Only a tile whose rows meet its
+    // columns holds diagonal elements (one strip in sixteen at N = 16384).
+    const bool diag = r_begin < (strip + 1) * SW && r_begin + r_cnt > strip * SW;
+    if (bid < nt_below) {
+        if (diag) stream(std::true_type(), std::true_type());
+        else stream(std::true_type(), std::false_type());
+    } else {
+        if (diag) stream(std::false_type(), std::true_type());
+        else stream(std::false_type(), std::false_type());
+    }
 
     if (COUNT) {
         if (my_updates) atomicAdd(&s_cnt, my_updates);
