@@ -15,6 +15,7 @@
 #include "fwx_guard.h"
 #include "fwx_internal.h"
 #include "fwx_kernels.h"
+#include "fwx_query.h"
 #include "fwx_resume.h"
 
 using namespace fwxi;
@@ -597,22 +598,6 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     return FWX_OK;
 }
 
-// Single-thread device walk of the next-hop matrix (fwx_matrix_query).
-__global__ void follow_path_kernel(const int32_t *next, int n, int ld, int src, int dst, int32_t *out,
-                                   int cap, int32_t *len_out)
-{
-    int len = 0, cur = src;
-    if (next[(size_t)src * ld + dst] < 0) { *len_out = 0; return; }
-    while (cur != dst || len == 0) {
-        const int nx = next[(size_t)cur * ld + dst];
-        if (nx < 0 || nx >= n || len >= n) { *len_out = FWX_ERR_CYCLE; return; }
-        if (len >= cap) { *len_out = FWX_ERR_CAPACITY; return; }
-        out[len++] = nx;
-        cur = nx;
-    }
-    *len_out = len;
-}
-
 template <typename T>
 int matrix_solve_typed(fwx_matrix *m, const Opts &op, unsigned long long *upd, hipStream_t s,
                        CallCtx *cx = nullptr);
@@ -685,7 +670,152 @@ int panel_impl(const fwx_slab *b, T *w, int32_t *w_hops, unsigned long long *d_u
 
 }  // namespace
 
+// ---- path queries of both handle kinds (fwx_query.h) ------------------------------------------------
+namespace fwxi {
+
+// Single-thread device walk of the next-hop matrix (fwx_matrix_query).
+__global__ void follow_path_kernel(EntryTab t, int n_real, int src, int dst, int32_t *out, int cap,
+                                   int32_t *len_out)
+{
+    int len = 0, cur = src, p;
+    {
+        const size_t off = t.locate(src, dst, p);
+        if (t.next[p][off] < 0) { *len_out = 0; return; }
+    }
+    while (cur != dst || len == 0) {
+        const size_t off = t.locate(cur, dst, p);
+        const int nx = t.next[p][off];
+        if (nx < 0 || nx >= n_real || len >= n_real) { *len_out = FWX_ERR_CYCLE; return; }
+        if (len >= cap) { *len_out = FWX_ERR_CAPACITY; return; }
+        out[len++] = nx;
+        cur = nx;
+    }
+    *len_out = len;
+}
+
+// The reference's `_path` list of entry (src,dst), rebuilt from the path trace exactly as
+// Algorithms.hs:55 built it: the newest update of (a,b) before time T, by pivot q, splits the path
+// into path_q(a,q) ++ path_q(q,b); an entry with no update before T still has its buildMatrix path
+// ([b] if next0[a][b] >= 0, else []).  T is the end of the solve for the query itself (`last`), and
+// for every sub-entry it is the step named by one of its own indices: (a,q) at time q is read from
+// at_col, (q,b) at time q from at_row.  Iterative, one thread: the list goes to out (cap entries), the
+// stack holds (a, b, kind) triples (3 * cap entries).  The length, or FWX_ERR_CAPACITY if it does not fit.
+__device__ int exact_walk(const EntryTab &t, int src, int dst, int32_t *out, int32_t *stack, int cap)
+{
+    enum { FINAL = 0, AS_COLUMN = 1, AS_ROW = 2 };
+    int sp = 0, len = 0;
+    stack[0] = src; stack[1] = dst; stack[2] = FINAL; sp = 1;
+    while (sp > 0) {
+        --sp;
+        const int a = stack[3 * sp], b = stack[3 * sp + 1], kind = stack[3 * sp + 2];
+        int p;
+        const size_t off = t.locate(a, b, p);
+        const int q = kind == FINAL ? t.last[p][off] : kind == AS_COLUMN ? t.at_col[p][off] : t.at_row[p][off];
+        if (q < 0) {
+            if (t.next0[p][off] >= 0) {
+                if (len >= cap) return FWX_ERR_CAPACITY;
+                out[len++] = b;
+            }
+        } else {
+            if (sp + 2 > cap) return FWX_ERR_CAPACITY;
+            stack[3 * sp] = q; stack[3 * sp + 1] = b; stack[3 * sp + 2] = AS_ROW; ++sp;      // second half
+            stack[3 * sp] = a; stack[3 * sp + 1] = q; stack[3 * sp + 2] = AS_COLUMN; ++sp;   // first half
+        }
+    }
+    return len;
+}
+
+// Batch form: one thread per (src[q], dst[q]); query q writes its list to paths + q*cap and uses
+// stacks + q*3*cap as its stack.  len_out[q] = length, or the error of that item.
+__global__ __launch_bounds__(64) void exact_paths_kernel(EntryTab t, int n_real, int count, const int32_t *src,
+                                                         const int32_t *dst, int32_t *paths, int32_t *stacks,
+                                                         int cap, int32_t *len_out)
+{
+    const int qi = blockIdx.x * 64 + threadIdx.x;
+    if (qi >= count) return;
+    const int s0 = src[qi], d0 = dst[qi];
+    if (s0 < 0 || d0 < 0 || s0 >= n_real || d0 >= n_real) { len_out[qi] = FWX_ERR_INVALID; return; }
+    len_out[qi] = exact_walk(t, s0, d0, paths + (size_t)qi * cap, stacks + (size_t)qi * 3 * cap, cap);
+}
+
+// One query, the pair by value (checked by the caller): nothing is copied in before the launch.  List and
+// stack live in `walk` (4 * cap entries).
+__global__ void exact_path_kernel(EntryTab t, int src, int dst, int32_t *walk, int cap, int32_t *len_out)
+{
+    *len_out = exact_walk(t, src, dst, walk, walk + cap, cap);
+}
+
+// What a one-query kernel just launched on `s` leaves: the length (or error) at len_dev, which is returned,
+// and that many entries at list_dev, which go to path_out.
+static int read_list(hipStream_t s, const int32_t *len_dev, const int32_t *list_dev, int32_t *path_out)
+{
+    FWX_HIP(hipGetLastError());
+    int32_t len = 0;
+    FWX_HIP(hipMemcpyAsync(&len, len_dev, 4, hipMemcpyDeviceToHost, s));
+    FWX_HIP(hipStreamSynchronize(s));
+    if (len > 0) {
+        FWX_HIP(hipMemcpyAsync(path_out, list_dev, (size_t)len * 4, hipMemcpyDeviceToHost, s));
+        FWX_HIP(hipStreamSynchronize(s));
+    }
+    return len;
+}
+
+int run_follow(const EntryTab &tab, int n_real, hipStream_t s, int32_t *scratch, int32_t src, int32_t dst,
+               int32_t *path_out, int32_t cap)
+{
+    const int dcap = cap < n_real ? cap : n_real;
+    hipLaunchKernelGGL(follow_path_kernel, dim3(1), dim3(1), 0, s, tab, n_real, src, dst, scratch + 1, dcap,
+                       scratch);
+    return read_list(s, scratch, scratch + 1, path_out);
+}
+
+int run_exact_batch(const EntryTab &tab, int n_real, hipStream_t s, int32_t count, const int32_t *src,
+                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap)
+{
+    // device scratch from a pooled per-call context: no hipMalloc / hipFree per query (and no hipFree
+    // right behind the kernel that used the memory: drain_stream in fwx_internal.h)
+    CtxLease lease;
+    int rc = lease.open();
+    if (rc) return rc;
+    lease.c->uses_stream(s);             // the kernel below runs on the handle's stream
+    const size_t c = (size_t)count;
+    void *ids = nullptr, *d_paths = nullptr, *d_stacks = nullptr;
+    if ((rc = lease.c->reserve(CallCtx::NEXT, c * 12, &ids)) ||
+        (rc = lease.c->reserve(CallCtx::RATE, c * cap * 4, &d_paths)) ||
+        (rc = lease.c->reserve(CallCtx::WS, c * cap * 12, &d_stacks)))
+        return rc;
+    int32_t *const d_src = (int32_t *)ids, *const d_dst = d_src + c, *const d_len = d_dst + c;
+    FWX_HIP(hipMemcpyAsync(d_src, src, c * 4, hipMemcpyHostToDevice, s));
+    FWX_HIP(hipMemcpyAsync(d_dst, dst, c * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(exact_paths_kernel, dim3((unsigned)((c + 63) / 64)), dim3(64), 0, s, tab, n_real, count,
+                       (const int32_t *)d_src, (const int32_t *)d_dst, (int32_t *)d_paths, (int32_t *)d_stacks, cap,
+                       d_len);
+    FWX_HIP(hipGetLastError());
+    FWX_HIP(hipMemcpyAsync(len_out, d_len, c * 4, hipMemcpyDeviceToHost, s));
+    FWX_HIP(hipMemcpyAsync(path_out, d_paths, c * cap * 4, hipMemcpyDeviceToHost, s));
+    FWX_HIP(hipStreamSynchronize(s));
+    return FWX_OK;
+}
+
+}  // namespace fwxi
+
 namespace {
+// A single-device handle as the query table: one partition of all nd rows.
+EntryTab tab_of(const fwx_matrix *m)
+{
+    EntryTab t;
+    memset(&t, 0, sizeof(t));
+    t.parts = 1;
+    t.nd = m->nd;
+    t.row0[1] = m->nd;
+    t.next[0] = m->next;
+    t.last[0] = m->plog.last;
+    t.at_col[0] = m->plog.at_col;
+    t.at_row[0] = m->plog.at_row;
+    t.next0[0] = m->next0;
+    return t;
+}
+
 template <typename T>
 int matrix_solve_typed(fwx_matrix *m, const Opts &op, unsigned long long *upd, hipStream_t s, CallCtx *cx)
 {
@@ -800,73 +930,6 @@ int logged_solve(fwx_matrix *m, const Opts &op_in, hipStream_t s, bool resumed =
     return FWX_OK;
 }
 
-// The reference's `_path` list of entry (src,dst), rebuilt from the path trace exactly as
-// Algorithms.hs:55 built it: the newest update of (a,b) before time T, by pivot q, splits the path
-// into path_q(a,q) ++ path_q(q,b); an entry with no update before T still has its buildMatrix path
-// ([b] if next0[a][b] >= 0, else []).  T is the end of the solve for the query itself (`last`), and
-// for every sub-entry it is the step named by one of its own indices: (a,q) at time q is read from
-// at_col, (q,b) at time q from at_row.  Iterative, one thread; stack and output live in `walk`.
-__global__ void exact_path_kernel(fwx::PathLog plog, const int32_t *next0, int n, int src, int dst,
-                                  int32_t *walk, int cap, int32_t *len_out)
-{
-    enum { FINAL = 0, AS_COLUMN = 1, AS_ROW = 2 };
-    int32_t *out = walk;                 // cap entries
-    int32_t *stack = walk + cap;         // 3 * cap entries: (a, b, kind) triples
-    int sp = 0, len = 0;
-    stack[0] = src; stack[1] = dst; stack[2] = FINAL; sp = 1;
-    while (sp > 0) {
-        --sp;
-        const int a = stack[3 * sp], b = stack[3 * sp + 1], kind = stack[3 * sp + 2];
-        const size_t off = (size_t)a * n + b;
-        const int q = kind == FINAL ? plog.last[off] : kind == AS_COLUMN ? plog.at_col[off] : plog.at_row[off];
-        if (q < 0) {
-            if (next0[off] >= 0) {
-                if (len >= cap) { *len_out = FWX_ERR_CAPACITY; return; }
-                out[len++] = b;
-            }
-        } else {
-            if (sp + 2 > cap) { *len_out = FWX_ERR_CAPACITY; return; }
-            stack[3 * sp] = q; stack[3 * sp + 1] = b; stack[3 * sp + 2] = AS_ROW; ++sp;      // second half
-            stack[3 * sp] = a; stack[3 * sp + 1] = q; stack[3 * sp + 2] = AS_COLUMN; ++sp;   // first half
-        }
-    }
-    *len_out = len;
-}
-
-// Batch form: one thread per (src[q], dst[q]); query q writes its list to paths + q*cap and uses
-// stacks + q*3*cap as its stack.  len_out[q] = length, FWX_ERR_CAPACITY if it does not fit.
-__global__ __launch_bounds__(64) void exact_paths_kernel(fwx::PathLog plog, const int32_t *next0, int n_real,
-                                                         int n, int count, const int32_t *src,
-                                                         const int32_t *dst, int32_t *paths,
-                                                         int32_t *stacks, int cap, int32_t *len_out)
-{
-    enum { FINAL = 0, AS_COLUMN = 1, AS_ROW = 2 };
-    const int qi = blockIdx.x * 64 + threadIdx.x;
-    if (qi >= count) return;
-    const int s0 = src[qi], d0 = dst[qi];
-    if (s0 < 0 || d0 < 0 || s0 >= n_real || d0 >= n_real) { len_out[qi] = FWX_ERR_INVALID; return; }
-    int32_t *out = paths + (size_t)qi * cap;
-    int32_t *stack = stacks + (size_t)qi * 3 * cap;
-    int sp = 0, len = 0;
-    stack[0] = s0; stack[1] = d0; stack[2] = FINAL; sp = 1;
-    while (sp > 0) {
-        --sp;
-        const int a = stack[3 * sp], b = stack[3 * sp + 1], kind = stack[3 * sp + 2];
-        const size_t off = (size_t)a * n + b;                 // n: the pitch of the trace arrays
-        const int q = kind == FINAL ? plog.last[off] : kind == AS_COLUMN ? plog.at_col[off] : plog.at_row[off];
-        if (q < 0) {
-            if (next0[off] >= 0) {
-                if (len >= cap) { len_out[qi] = FWX_ERR_CAPACITY; return; }
-                out[len++] = b;
-            }
-        } else {
-            if (sp + 2 > cap) { len_out[qi] = FWX_ERR_CAPACITY; return; }
-            stack[3 * sp] = q; stack[3 * sp + 1] = b; stack[3 * sp + 2] = AS_ROW; ++sp;
-            stack[3 * sp] = a; stack[3 * sp + 1] = q; stack[3 * sp + 2] = AS_COLUMN; ++sp;
-        }
-    }
-    len_out[qi] = len;
-}
 // The caller's arrays are n x n; a single-device handle holds them at pitch nd (fwx_matrix::nd).
 // src / dst may be host or device memory (hipMemcpyDefault).
 int copy_in(fwx_matrix *m, void *dev, const void *src, size_t es, hipStream_t s)
@@ -1192,18 +1255,7 @@ int fwx_matrix_enable_path_log(fwx_matrix *m)
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        const size_t nn = (size_t)m->nd * (size_t)m->nd;
-        FWX_HIP(hipMalloc((void **)&m->plog.at_col, nn * 4));
-        FWX_HIP(hipMalloc((void **)&m->plog.at_row, nn * 4));
-        if (!m->next0) FWX_HIP(hipMalloc((void **)&m->next0, nn * 4));
-        FWX_HIP(hipMalloc((void **)&m->plog.last, nn * 4));      // last: `last != nullptr` = enabled
-        // next0 = the UPLOADED next-hops.  If the arrays already hold an unsolved upload, keep it;
-        // otherwise (nothing uploaded yet, or already solved) `fresh` is 0 and a traced solve is
-        // refused until the next upload, which fills next0.
-        if (m->fresh) {
-            FWX_HIP(hipMemcpyAsync(m->next0, m->next, nn * 4, hipMemcpyDeviceToDevice, m->stream));
-            FWX_HIP(hipStreamSynchronize(m->stream));
-        }
+        if ((rc = trace_alloc(m->plog, m->next0, m->next, (size_t)m->nd * (size_t)m->nd, m->fresh, m->stream))) return rc;
         m->rec_ready = 0;
         return FWX_OK;
     });
@@ -1218,10 +1270,9 @@ int fwx_matrix_keep_input(fwx_matrix *m)
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        const size_t nn = (size_t)m->nd * (size_t)m->nd, es = m->dtype == FWX_F64 ? 8 : 4;
-        FWX_HIP(hipMalloc(&m->rate0, nn * es));
-        if (m->next && !m->next0) FWX_HIP(hipMalloc((void **)&m->next0, nn * 4));
-        if (m->hops) FWX_HIP(hipMalloc((void **)&m->hops0, nn * 4));
+        if ((rc = kept_alloc(m->rate0, m->next0, m->hops0, m->next, m->hops, (size_t)m->nd * (size_t)m->nd,
+                             m->dtype == FWX_F64 ? 8 : 4)))
+            return rc;
         m->keep = 1;
         if (m->fresh) {          // an unsolved upload is in the arrays: that is the input to keep
             if ((rc = keep_live(slab_of(m)))) return rc;
@@ -1440,32 +1491,18 @@ int fwx_matrix_query_exact(fwx_matrix *m, int32_t src, int32_t dst, double *rate
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        const size_t idx = (size_t)src * m->nd + dst;
         hipStream_t s = m->stream;
-        float f32_rate = 0;
-        if (rate_out) {
-            if (m->dtype == FWX_F64)
-                FWX_HIP(hipMemcpyAsync(rate_out, (double *)m->rate + idx, 8, hipMemcpyDeviceToHost, s));
-            else
-                FWX_HIP(hipMemcpyAsync(&f32_rate, (float *)m->rate + idx, 4, hipMemcpyDeviceToHost, s));
-        }
+        RateRead rate;
+        if ((rc = rate.queue(m->rate, (size_t)src * m->nd + dst, m->dtype, s, rate_out))) return rc;
         if (!m->walk || m->walk_cap < cap) {      // grow-only scratch, reused across queries
             if (m->walk) { drain_stream(s); (void)hipFree(m->walk); m->walk = nullptr; }
             FWX_HIP(hipMalloc((void **)&m->walk, ((size_t)4 * cap + 1) * 4));
             m->walk_cap = cap;
         }
-        int32_t *len_dev = m->walk + (size_t)4 * cap;
-        hipLaunchKernelGGL(exact_path_kernel, dim3(1), dim3(1), 0, s, m->plog, m->next0, m->nd, src,
-                           dst, m->walk, cap, len_dev);
-        FWX_HIP(hipGetLastError());
-        int32_t len = 0;
-        FWX_HIP(hipMemcpyAsync(&len, len_dev, 4, hipMemcpyDeviceToHost, s));
-        FWX_HIP(hipStreamSynchronize(s));
-        if (rate_out && m->dtype != FWX_F64) *rate_out = (double)f32_rate;
-        if (len > 0) {
-            FWX_HIP(hipMemcpyAsync(path_out, m->walk, (size_t)len * 4, hipMemcpyDeviceToHost, s));
-            FWX_HIP(hipStreamSynchronize(s));
-        }
+        int32_t *const len_dev = m->walk + (size_t)4 * cap;
+        hipLaunchKernelGGL(exact_path_kernel, dim3(1), dim3(1), 0, s, tab_of(m), src, dst, m->walk, cap, len_dev);
+        const int len = read_list(s, len_dev, m->walk, path_out);
+        rate.done();
         return len;
     });
 }
@@ -1482,32 +1519,7 @@ int fwx_matrix_query_exact_batch(fwx_matrix *m, int32_t count, const int32_t *sr
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        // device scratch from a pooled per-call context: no hipMalloc / hipFree per query (and no hipFree
-        // right behind the kernel that used the memory: drain_stream in fwx_internal.h)
-        CtxLease lease;
-        if ((rc = lease.open())) return rc;
-        lease.c->uses_stream(m->stream);     // the kernel below runs on the handle's stream
-        const size_t c = (size_t)count;
-        struct { void *p = nullptr; } d_src, d_dst, d_len, d_paths, d_stacks;
-        void *ids = nullptr;
-        if ((rc = lease.c->reserve(CallCtx::NEXT, c * 12, &ids)) ||
-            (rc = lease.c->reserve(CallCtx::RATE, c * cap * 4, &d_paths.p)) ||
-            (rc = lease.c->reserve(CallCtx::WS, c * cap * 12, &d_stacks.p)))
-            return rc;
-        d_src.p = ids;
-        d_dst.p = (char *)ids + c * 4;
-        d_len.p = (char *)ids + c * 8;
-        hipStream_t s = m->stream;
-        FWX_HIP(hipMemcpyAsync(d_src.p, src, c * 4, hipMemcpyHostToDevice, s));
-        FWX_HIP(hipMemcpyAsync(d_dst.p, dst, c * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(exact_paths_kernel, dim3((unsigned)((c + 63) / 64)), dim3(64), 0, s, m->plog,
-                           m->next0, m->n, m->nd, count, (const int32_t *)d_src.p, (const int32_t *)d_dst.p,
-                           (int32_t *)d_paths.p, (int32_t *)d_stacks.p, cap, (int32_t *)d_len.p);
-        FWX_HIP(hipGetLastError());
-        FWX_HIP(hipMemcpyAsync(len_out, d_len.p, c * 4, hipMemcpyDeviceToHost, s));
-        FWX_HIP(hipMemcpyAsync(path_out, d_paths.p, c * cap * 4, hipMemcpyDeviceToHost, s));
-        FWX_HIP(hipStreamSynchronize(s));
-        return FWX_OK;
+        return run_exact_batch(tab_of(m), m->n, m->stream, count, src, dst, len_out, path_out, cap);
     });
 }
 
@@ -1569,32 +1581,15 @@ int fwx_matrix_query(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out, 
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        const size_t idx = (size_t)src * m->nd + dst;
-        hipStream_t s = m->stream;
-        float f32_rate = 0;
-        if (rate_out) {
-            if (m->dtype == FWX_F64)
-                FWX_HIP(hipMemcpyAsync(rate_out, (double *)m->rate + idx, 8, hipMemcpyDeviceToHost, s));
-            else
-                FWX_HIP(hipMemcpyAsync(&f32_rate, (float *)m->rate + idx, 4, hipMemcpyDeviceToHost, s));
-        }
+        RateRead rate;
+        if ((rc = rate.queue(m->rate, (size_t)src * m->nd + dst, m->dtype, m->stream, rate_out))) return rc;
         if (!m->next) {
-            FWX_HIP(hipStreamSynchronize(s));
-            if (rate_out && m->dtype != FWX_F64) *rate_out = (double)f32_rate;
+            FWX_HIP(hipStreamSynchronize(m->stream));
+            rate.done();
             return FWX_ERR_INVALID;
         }
-        const int dcap = cap < m->n ? cap : m->n;
-        hipLaunchKernelGGL(follow_path_kernel, dim3(1), dim3(1), 0, s, m->next, m->n, m->nd, src, dst,
-                           m->scratch + 1, dcap, m->scratch);
-        FWX_HIP(hipGetLastError());
-        int32_t len = 0;
-        FWX_HIP(hipMemcpyAsync(&len, m->scratch, 4, hipMemcpyDeviceToHost, s));
-        FWX_HIP(hipStreamSynchronize(s));
-        if (rate_out && m->dtype != FWX_F64) *rate_out = (double)f32_rate;
-        if (len > 0) {
-            FWX_HIP(hipMemcpyAsync(path_out, m->scratch + 1, (size_t)len * 4, hipMemcpyDeviceToHost, s));
-            FWX_HIP(hipStreamSynchronize(s));
-        }
+        const int len = run_follow(tab_of(m), m->n, m->stream, m->scratch, src, dst, path_out, cap);
+        rate.done();
         return len;
     });
 }

@@ -32,6 +32,7 @@
 #include "fwx_guard.h"
 #include "fwx_internal.h"
 #include "fwx_kernels.h"
+#include "fwx_query.h"
 #include "fwx_resume.h"
 
 namespace fwxi {
@@ -234,26 +235,13 @@ struct MultiState {
     int32_t qcap = 0;
 };
 
-// Everything a query kernel needs to address entry (a, b) of a partitioned matrix.
-struct SlabTab {
-    int parts, n;                              // n = device pitch
-    int row0[FWX_MAX_PARTS + 1];
-    const int32_t *next[FWX_MAX_PARTS], *last[FWX_MAX_PARTS], *at_col[FWX_MAX_PARTS],
-        *at_row[FWX_MAX_PARTS], *next0[FWX_MAX_PARTS];
-    __device__ __forceinline__ size_t locate(int a, int b, int &p) const
-    {
-        p = 0;
-        while (p + 1 < parts && a >= row0[p + 1]) ++p;
-        return (size_t)(a - row0[p]) * n + b;
-    }
-};
-
-static SlabTab make_tab(const MultiState &M)
+// The partitions as the table the query kernels address entries through (fwx_query.h).
+static EntryTab make_tab(const MultiState &M)
 {
-    SlabTab t;
+    EntryTab t;
     memset(&t, 0, sizeof(t));
     t.parts = M.parts;
-    t.n = M.nd;
+    t.nd = M.nd;
     for (int p = 0; p < M.parts; ++p) {
         const Part &q = M.part[p];
         t.row0[p] = q.row0;
@@ -265,60 +253,6 @@ static SlabTab make_tab(const MultiState &M)
     }
     t.row0[M.parts] = M.nd;
     return t;
-}
-
-__global__ void multi_follow_path_kernel(SlabTab t, int n_real, int src, int dst, int32_t *out, int cap,
-                                         int32_t *len_out)
-{
-    int len = 0, cur = src, p;
-    {
-        const size_t off = t.locate(src, dst, p);
-        if (t.next[p][off] < 0) { *len_out = 0; return; }
-    }
-    while (cur != dst || len == 0) {
-        const size_t off = t.locate(cur, dst, p);
-        const int nx = t.next[p][off];
-        if (nx < 0 || nx >= n_real || len >= n_real) { *len_out = FWX_ERR_CYCLE; return; }
-        if (len >= cap) { *len_out = FWX_ERR_CAPACITY; return; }
-        out[len++] = nx;
-        cur = nx;
-    }
-    *len_out = len;
-}
-
-// Same walk as exact_path(s)_kernel in fwx_api.hip (see there), entries addressed through the table.
-__global__ __launch_bounds__(64) void multi_exact_paths_kernel(SlabTab t, int n_real, int count,
-                                                               const int32_t *src, const int32_t *dst,
-                                                               int32_t *paths, int32_t *stacks, int cap,
-                                                               int32_t *len_out)
-{
-    enum { FINAL = 0, AS_COLUMN = 1, AS_ROW = 2 };
-    const int qi = blockIdx.x * 64 + threadIdx.x;
-    if (qi >= count) return;
-    const int s0 = src[qi], d0 = dst[qi];
-    if (s0 < 0 || d0 < 0 || s0 >= n_real || d0 >= n_real) { len_out[qi] = FWX_ERR_INVALID; return; }
-    int32_t *out = paths + (size_t)qi * cap;
-    int32_t *stack = stacks + (size_t)qi * 3 * cap;
-    int sp = 0, len = 0;
-    stack[0] = s0; stack[1] = d0; stack[2] = FINAL; sp = 1;
-    while (sp > 0) {
-        --sp;
-        const int a = stack[3 * sp], b = stack[3 * sp + 1], kind = stack[3 * sp + 2];
-        int p;
-        const size_t off = t.locate(a, b, p);
-        const int q = kind == FINAL ? t.last[p][off] : kind == AS_COLUMN ? t.at_col[p][off] : t.at_row[p][off];
-        if (q < 0) {
-            if (t.next0[p][off] >= 0) {
-                if (len >= cap) { len_out[qi] = FWX_ERR_CAPACITY; return; }
-                out[len++] = b;
-            }
-        } else {
-            if (sp + 2 > cap) { len_out[qi] = FWX_ERR_CAPACITY; return; }
-            stack[3 * sp] = q; stack[3 * sp + 1] = b; stack[3 * sp + 2] = AS_ROW; ++sp;
-            stack[3 * sp] = a; stack[3 * sp + 1] = q; stack[3 * sp + 2] = AS_COLUMN; ++sp;
-        }
-    }
-    len_out[qi] = len;
 }
 
 static int set_dev(int d)
@@ -1366,15 +1300,7 @@ int multi_enable_path_log(fwx_matrix *m)
         if (!M.here(p)) continue;
         int rc = set_dev(q.device);
         if (rc) return rc;
-        const size_t bytes = (size_t)q.rows * M.nd * 4;
-        FWX_HIP(hipMalloc((void **)&q.plog.at_col, bytes ? bytes : 16));
-        FWX_HIP(hipMalloc((void **)&q.plog.at_row, bytes ? bytes : 16));
-        if (!q.next0) FWX_HIP(hipMalloc((void **)&q.next0, bytes ? bytes : 16));
-        FWX_HIP(hipMalloc((void **)&q.plog.last, bytes ? bytes : 16));
-        if (m->fresh) {
-            FWX_HIP(hipMemcpyAsync(q.next0, q.next, bytes, hipMemcpyDeviceToDevice, q.main));
-            FWX_HIP(hipStreamSynchronize(q.main));
-        }
+        if ((rc = trace_alloc(q.plog, q.next0, q.next, (size_t)q.rows * M.nd, m->fresh, q.main))) return rc;
     }
     m->plog.last = M.part[M.first_here()].plog.last;     // "enabled" marker for the shared handle logic
     m->rec_ready = 0;
@@ -1387,16 +1313,10 @@ static int read_rate(fwx_matrix *m, int src, int dst, double *rate_out)
     Part &q = M.part[owner_of(M, src)];
     int rc = set_dev(q.device);
     if (rc) return rc;
-    const size_t off = (size_t)(src - q.row0) * M.nd + dst;
-    if (m->dtype == FWX_F64) {
-        FWX_HIP(hipMemcpyAsync(rate_out, (double *)q.rate + off, 8, hipMemcpyDeviceToHost, q.main));
-        FWX_HIP(hipStreamSynchronize(q.main));
-    } else {
-        float f = 0;
-        FWX_HIP(hipMemcpyAsync(&f, (float *)q.rate + off, 4, hipMemcpyDeviceToHost, q.main));
-        FWX_HIP(hipStreamSynchronize(q.main));
-        *rate_out = (double)f;
-    }
+    RateRead rate;
+    if ((rc = rate.queue(q.rate, (size_t)(src - q.row0) * M.nd + dst, m->dtype, q.main, rate_out))) return rc;
+    FWX_HIP(hipStreamSynchronize(q.main));
+    rate.done();
     return FWX_OK;
 }
 
@@ -1448,19 +1368,8 @@ int multi_query(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out, int32
     if (!M.peer_all) return host_walk(m, src, dst, path_out, cap);
     Part &z = M.part[0];
     if ((rc = set_dev(z.device))) return rc;
-    const int dcap = cap < m->n ? cap : m->n;
     if ((rc = query_scratch(M, m->n + 2))) return rc;
-    hipLaunchKernelGGL(multi_follow_path_kernel, dim3(1), dim3(1), 0, z.main, make_tab(M), m->n, src, dst,
-                       M.qscratch + 1, dcap, M.qscratch);
-    FWX_HIP(hipGetLastError());
-    int32_t len = 0;
-    FWX_HIP(hipMemcpyAsync(&len, M.qscratch, 4, hipMemcpyDeviceToHost, z.main));
-    FWX_HIP(hipStreamSynchronize(z.main));
-    if (len > 0) {
-        FWX_HIP(hipMemcpyAsync(path_out, M.qscratch + 1, (size_t)len * 4, hipMemcpyDeviceToHost, z.main));
-        FWX_HIP(hipStreamSynchronize(z.main));
-    }
-    return len;
+    return run_follow(make_tab(M), m->n, z.main, M.qscratch, src, dst, path_out, cap);
 }
 
 int multi_query_exact_batch(fwx_matrix *m, int32_t count, const int32_t *src, const int32_t *dst,
@@ -1472,31 +1381,7 @@ int multi_query_exact_batch(fwx_matrix *m, int32_t count, const int32_t *src, co
     Part &z = M.part[0];
     int rc = set_dev(z.device);
     if (rc) return rc;
-    // device scratch from a pooled per-call context: no hipMalloc / hipFree per query (and no hipFree
-    // right behind the kernel that used the memory: drain_stream in fwx_internal.h)
-    CtxLease lease;
-    if ((rc = lease.open())) return rc;
-    lease.c->uses_stream(z.main);            // the kernel below runs on partition 0's stream
-    const size_t c = (size_t)count;
-    struct { void *p = nullptr; } d_src, d_dst, d_len, d_paths, d_stacks;
-    void *ids = nullptr;
-    if ((rc = lease.c->reserve(CallCtx::NEXT, c * 12, &ids)) ||
-        (rc = lease.c->reserve(CallCtx::RATE, c * cap * 4, &d_paths.p)) ||
-        (rc = lease.c->reserve(CallCtx::WS, c * cap * 12, &d_stacks.p)))
-        return rc;
-    d_src.p = ids;
-    d_dst.p = (char *)ids + c * 4;
-    d_len.p = (char *)ids + c * 8;
-    FWX_HIP(hipMemcpyAsync(d_src.p, src, c * 4, hipMemcpyHostToDevice, z.main));
-    FWX_HIP(hipMemcpyAsync(d_dst.p, dst, c * 4, hipMemcpyHostToDevice, z.main));
-    hipLaunchKernelGGL(multi_exact_paths_kernel, dim3((unsigned)((c + 63) / 64)), dim3(64), 0, z.main,
-                       make_tab(M), m->n, count, (const int32_t *)d_src.p, (const int32_t *)d_dst.p,
-                       (int32_t *)d_paths.p, (int32_t *)d_stacks.p, cap, (int32_t *)d_len.p);
-    FWX_HIP(hipGetLastError());
-    FWX_HIP(hipMemcpyAsync(len_out, d_len.p, c * 4, hipMemcpyDeviceToHost, z.main));
-    FWX_HIP(hipMemcpyAsync(path_out, d_paths.p, c * cap * 4, hipMemcpyDeviceToHost, z.main));
-    FWX_HIP(hipStreamSynchronize(z.main));
-    return FWX_OK;
+    return run_exact_batch(make_tab(M), m->n, z.main, count, src, dst, len_out, path_out, cap);
 }
 
 int multi_query_exact(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out, int32_t *path_out,
@@ -1523,10 +1408,7 @@ int multi_keep_input(fwx_matrix *m)
         if (!M.here(p)) continue;
         int rc = set_dev(q.device);
         if (rc) return rc;
-        const size_t cells = (size_t)q.rows * M.nd;
-        FWX_HIP(hipMalloc(&q.rate0, cells * es ? cells * es : 16));
-        if (q.next && !q.next0) FWX_HIP(hipMalloc((void **)&q.next0, cells * 4 ? cells * 4 : 16));
-        if (q.hops) FWX_HIP(hipMalloc((void **)&q.hops0, cells * 4 ? cells * 4 : 16));
+        if ((rc = kept_alloc(q.rate0, q.next0, q.hops0, q.next, q.hops, (size_t)q.rows * M.nd, es))) return rc;
         if (m->fresh) {
             if ((rc = keep_live(slab_of(M, q, es)))) return rc;
             FWX_HIP(hipStreamSynchronize(q.main));

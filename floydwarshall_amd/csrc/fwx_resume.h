@@ -172,6 +172,41 @@ inline int restore_checkpoint(const ResumeStore &st, const Slab &v, int c) { ret
 inline int restore_kept(const Slab &v) { return copy_arrays(v, v.live, v.kept); }   // (the trace is not input)
 inline int keep_live(const Slab &v) { return copy_arrays(v, v.kept, v.live); }
 
+// One array of a slab on the current device.  (A zero-size array -- an empty partition -- is 16 bytes.)
+template <typename P> inline int slab_array(P **p, uint64_t bytes)
+{
+    FWX_HIP(hipMalloc((void **)p, bytes ? bytes : 16));
+    return FWX_OK;
+}
+
+// The path trace of a slab of `cells` entries (fwx_matrix_enable_path_log), into the handle's own members:
+// `last` goes last, a non-null `last` is the "enabled" marker.  next0 = the UPLOADED next-hops: if the arrays
+// hold an unsolved upload (`fresh`), keep it; otherwise a traced solve is refused until the next upload,
+// which fills next0.
+inline int trace_alloc(fwx::PathLog &plog, int32_t *&next0, const int32_t *next, size_t cells, bool fresh, hipStream_t s)
+{
+    int rc;
+    if ((rc = slab_array(&plog.at_col, cells * 4)) || (rc = slab_array(&plog.at_row, cells * 4)) ||
+        (!next0 && (rc = slab_array(&next0, cells * 4))) || (rc = slab_array(&plog.last, cells * 4)))
+        return rc;
+    if (fresh) {
+        FWX_HIP(hipMemcpyAsync(next0, next, cells * 4, hipMemcpyDeviceToDevice, s));
+        FWX_HIP(hipStreamSynchronize(s));
+    }
+    return FWX_OK;
+}
+
+// The kept input of a slab (fwx_matrix_keep_input) for the arrays the handle carries; next0 may be there
+// already, as the trace's.
+inline int kept_alloc(void *&rate0, int32_t *&next0, int32_t *&hops0, bool with_next, bool with_hops, size_t cells, size_t es)
+{
+    int rc;
+    if ((rc = slab_array(&rate0, cells * es)) || (with_next && !next0 && (rc = slab_array(&next0, cells * 4))) ||
+        (with_hops && (rc = slab_array(&hops0, cells * 4))))
+        return rc;
+    return FWX_OK;
+}
+
 // (the store's device must be current)
 inline void store_free(ResumeStore &st)
 {
@@ -182,29 +217,25 @@ inline void store_free(ResumeStore &st)
 }
 
 // `count` checkpoints of the arrays the slab carries, the all-pivot panels and the index buffer, on the
-// current device; a partial set is released again.  (A zero-size array -- an empty partition -- is 16 bytes.)
+// current device; a partial set is released again.
 inline int store_alloc(ResumeStore &st, const Slab &v, int count)
 {
     const SlabCells d = slab_cells(v.rows, v.nd, v.ct_ld);
-    auto alloc = [](auto **p, uint64_t bytes) -> int {
-        FWX_HIP(hipMalloc((void **)p, bytes ? bytes : 16));
-        return FWX_OK;
-    };
     auto all = [&]() -> int {
         int rc;
         for (int c = 0; c < count; ++c) {
             Arrays &a = st.cp[c];
-            if ((rc = alloc(&a.rate, d.cells * v.es))) return rc;
-            if (v.live.next && (rc = alloc(&a.next, d.cells * 4))) return rc;
-            if (v.live.hops && (rc = alloc(&a.hops, d.cells * 4))) return rc;
-            if (v.live.last && ((rc = alloc(&a.last, d.cells * 4)) || (rc = alloc(&a.at_col, d.cells * 4)) ||
-                                (rc = alloc(&a.at_row, d.cells * 4))))
+            if ((rc = slab_array(&a.rate, d.cells * v.es))) return rc;
+            if (v.live.next && (rc = slab_array(&a.next, d.cells * 4))) return rc;
+            if (v.live.hops && (rc = slab_array(&a.hops, d.cells * 4))) return rc;
+            if (v.live.last && ((rc = slab_array(&a.last, d.cells * 4)) || (rc = slab_array(&a.at_col, d.cells * 4)) ||
+                                (rc = slab_array(&a.at_row, d.cells * 4))))
                 return rc;
         }
-        if ((rc = alloc(&st.w, d.w_cells * v.es)) || (rc = alloc(&st.ct, d.col_cells * v.es))) return rc;
-        if (v.live.next && (rc = alloc(&st.cnt, d.col_cells * 4))) return rc;
-        if (v.live.hops && ((rc = alloc(&st.wh, d.w_cells * 4)) || (rc = alloc(&st.cht, d.col_cells * 4)))) return rc;
-        return alloc(&st.idx, (uint64_t)FWX_MAX_PATCH * 8);
+        if ((rc = slab_array(&st.w, d.w_cells * v.es)) || (rc = slab_array(&st.ct, d.col_cells * v.es))) return rc;
+        if (v.live.next && (rc = slab_array(&st.cnt, d.col_cells * 4))) return rc;
+        if (v.live.hops && ((rc = slab_array(&st.wh, d.w_cells * 4)) || (rc = slab_array(&st.cht, d.col_cells * 4)))) return rc;
+        return slab_array(&st.idx, (uint64_t)FWX_MAX_PATCH * 8);
     };
     const int rc = all();
     if (rc) store_free(st);
