@@ -13,10 +13,10 @@
 
 #include "fwx.h"
 #include "fwx_guard.h"
+#include "fwx_handle.h"
 #include "fwx_internal.h"
 #include "fwx_kernels.h"
 #include "fwx_query.h"
-#include "fwx_resume.h"
 
 using namespace fwxi;
 
@@ -91,7 +91,7 @@ constexpr int kLookaheadMinN = INT32_MAX, kLookaheadMinNWithNext = 16384, kLooka
 template <typename T>
 int fused_range(T *rate, int32_t *next, int32_t *hops, int n, int k_begin, int k_end, void *ws,
                 unsigned long long *d_updates, hipStream_t s, fwx::PathLog plog, bool nonneg,
-                SideStream *kept_side = nullptr, Resume *rec = nullptr)
+                SideStream *kept_side = nullptr, Resume *rec = nullptr, ResumeStore *store = nullptr)
 {
     char *p = (char *)ws;
     const int ld = (n + 3) & ~3;
@@ -114,12 +114,12 @@ int fused_range(T *rate, int32_t *next, int32_t *hops, int n, int k_begin, int k
     whole.rows = whole.nd = n; whole.ct_ld = ld; whole.es = sizeof(T); whole.s = s;
     auto panel_set = [&](int k0, int b) {
         if (!rec) return;
-        const PanelRows pr = store_panels(rec->store, whole, k0);
+        const PanelRows pr = store_panels(*store, whole, k0);
         wbuf[b] = (T *)pr.w; ctbuf[b] = (T *)pr.ct; cntbuf[b] = pr.cnt; whbuf[b] = pr.wh; chtbuf[b] = pr.cht;
     };
     auto checkpoint = [&](int k0) -> int {        // the state at the START of step k0, if it is one
         const int c = rec ? rec->checkpoint_at(k0) : -1;
-        return c < 0 ? FWX_OK : save_checkpoint(rec->store, whole, c);
+        return c < 0 ? FWX_OK : save_checkpoint(*store, whole, c);
     };
     SideStream local_side;
     SideStream &side = kept_side ? *kept_side : local_side;
@@ -370,7 +370,7 @@ int route_solve(const Opts &op, int n, int nd, const T *rate, const int32_t *nex
         } else {
             const int rc = domain_bits<T>(rate, next, (size_t)nd * nd, d_flag, s, bits);
             if (rc) return rc;
-            if (cache && (next || !cache->next)) { cache->dom_bits = bits; cache->dom_known = 1; }
+            if (cache && (next || !cache->with_next)) { cache->dom_bits = bits; cache->dom_known = 1; }
         }
     }
     if (next && bits != 3) { route = fallback; return FWX_OK; }
@@ -808,11 +808,11 @@ EntryTab tab_of(const fwx_matrix *m)
     t.parts = 1;
     t.nd = m->nd;
     t.row0[1] = m->nd;
-    t.next[0] = m->next;
-    t.last[0] = m->plog.last;
-    t.at_col[0] = m->plog.at_col;
-    t.at_row[0] = m->plog.at_row;
-    t.next0[0] = m->next0;
+    t.next[0] = m->slab.next;
+    t.last[0] = m->slab.plog.last;
+    t.at_col[0] = m->slab.plog.at_col;
+    t.at_row[0] = m->slab.plog.at_row;
+    t.next0[0] = m->slab.next0;
     return t;
 }
 
@@ -820,7 +820,8 @@ template <typename T>
 int matrix_solve_typed(fwx_matrix *m, const Opts &op, unsigned long long *upd, hipStream_t s, CallCtx *cx)
 {
     const int n = m->n, nd = m->nd;      // order of the matrix; order (= pitch) of the device arrays
-    T *r = (T *)m->rate;
+    const SlabData &d = m->slab;
+    T *r = (T *)d.rate;
     Route route;
     bool nonneg = false;
     int *d_flag = m->flag;
@@ -832,19 +833,19 @@ int matrix_solve_typed(fwx_matrix *m, const Opts &op, unsigned long long *upd, h
         d_flag = (int *)((unsigned long long *)small + FWX_UPDATE_SHARDS);
     }
     m->fresh = 0;                        // whatever happens next, the arrays are no longer the upload
-    if ((rc = route_solve<T>(op, n, nd, r, m->next, m->hops, upd != nullptr, d_flag, s, route, nonneg,
+    if ((rc = route_solve<T>(op, n, nd, r, d.next, d.hops, upd != nullptr, d_flag, s, route, nonneg,
                              m->flag ? m : nullptr)))
         return rc;
     if (route == ROUTE_SMALL) {
         if (m->resume) { m->resume->valid_upto = 0; m->resume->state_at = -1; }
-        FWX_HIP(fwx::launch_small_solve<T>(r, m->next, m->hops, nd, op.k_begin, op.k_end, upd,
-                                           m->plog, s));
+        FWX_HIP(fwx::launch_small_solve<T>(r, d.next, d.hops, nd, op.k_begin, op.k_end, upd,
+                                           d.plog, s));
         return FWX_OK;
     }
     if (route == ROUTE_FUSED) {
         // a handle keeps its workspace and look-ahead stream across solves; a view borrows the
         // pooled context's
-        const size_t need = fused_ws_bytes(nd, sizeof(T), m->hops != nullptr);
+        const size_t need = fused_ws_bytes(nd, sizeof(T), d.hops != nullptr);
         void *ws = nullptr;
         SideStream *side = nullptr;
         if (m->flag) {
@@ -867,8 +868,6 @@ int matrix_solve_typed(fwx_matrix *m, const Opts &op, unsigned long long *upd, h
             if ((rc = cx->reserve(CallCtx::WS, need, &ws))) return rc;
             side = &cx->side;
         }
-        // a resumable handle records the panels of every pass and the checkpoints it walks over; what
-        // it holds beyond k_begin belongs to an older solve until this one has finished
         // a resumable handle records the panels of every pass and the checkpoints it walks over -- if
         // this solve continues the kept input's own solve (the arrays are that input at time k_begin)
         Resume *rec = nullptr;
@@ -880,17 +879,18 @@ int matrix_solve_typed(fwx_matrix *m, const Opts &op, unsigned long long *upd, h
             R.state_at = -1;
             if (chain) rec = &R;
         }
-        rc = fused_range<T>(r, m->next, m->hops, nd, op.k_begin, op.k_end, ws, upd, s, m->plog, nonneg, side, rec);
+        rc = fused_range<T>(r, d.next, d.hops, nd, op.k_begin, op.k_end, ws, upd, s, d.plog, nonneg, side, rec,
+                            &m->slab.store);
         if (rc) return rc;
         FWX_HIP(hipStreamSynchronize(s));
         if (rec) rec->valid_upto = rec->state_at = op.k_end;
         return FWX_OK;
     }
     if (m->resume) { m->resume->valid_upto = 0; m->resume->state_at = -1; }   // nothing was recorded
-    return relax_range<T>(r, m->next, m->hops, nd, nd, 0, r + (size_t)op.k_begin * nd,
-                          m->hops ? m->hops + (size_t)op.k_begin * nd : nullptr, nd, op.k_begin,
-                          op.k_end, op.serpentine, upd, s, m->plog, 0, 0,
-                          m->next ? m->next + (size_t)op.k_begin * nd : nullptr);
+    return relax_range<T>(r, d.next, d.hops, nd, nd, 0, r + (size_t)op.k_begin * nd,
+                          d.hops ? d.hops + (size_t)op.k_begin * nd : nullptr, nd, op.k_begin,
+                          op.k_end, op.serpentine, upd, s, d.plog, 0, 0,
+                          d.next ? d.next + (size_t)op.k_begin * nd : nullptr);
 }
 
 // Solve with the path trace (PathLog): one pass.  `last` starts at -1 everywhere; the kernels set
@@ -906,9 +906,9 @@ int logged_solve(fwx_matrix *m, const Opts &op_in, hipStream_t s, bool resumed =
                                                  //   (no hops), per-k -- all three keep the trace
     const size_t nn = (size_t)m->nd * (size_t)m->nd;
     if (!resumed) {
-        FWX_HIP(hipMemsetAsync(m->plog.last, 0xFF, nn * 4, s));
-        FWX_HIP(hipMemsetAsync(m->plog.at_col, 0xFF, nn * 4, s));
-        FWX_HIP(hipMemsetAsync(m->plog.at_row, 0xFF, nn * 4, s));
+        FWX_HIP(hipMemsetAsync(m->slab.plog.last, 0xFF, nn * 4, s));
+        FWX_HIP(hipMemsetAsync(m->slab.plog.at_col, 0xFF, nn * 4, s));
+        FWX_HIP(hipMemsetAsync(m->slab.plog.at_row, 0xFF, nn * 4, s));
     }
     unsigned long long *upd = op.updates_out ? m->upd : nullptr;   // counting costs registers
     if (upd) FWX_HIP(hipMemsetAsync(upd, 0, FWX_UPDATE_SHARDS * 8, s));
@@ -930,60 +930,51 @@ int logged_solve(fwx_matrix *m, const Opts &op_in, hipStream_t s, bool resumed =
     return FWX_OK;
 }
 
-// The caller's arrays are n x n; a single-device handle holds them at pitch nd (fwx_matrix::nd).
-// src / dst may be host or device memory (hipMemcpyDefault).
-int copy_in(fwx_matrix *m, void *dev, const void *src, size_t es, hipStream_t s)
+// ---- the data operations of a handle, once for both kinds: loops over its slabs (fwx_handle.h) --------
+
+// The device of a single-device handle becomes current, with DeviceGuard::enter's checks; the slabs of a
+// partitioned handle select theirs as they are visited.
+int enter_handle(DeviceGuard &g, const fwx_matrix *m) { return m->multi ? FWX_OK : g.enter(m->device); }
+
+// The rows of slab `d` that exist in the caller's n x n arrays (the last slab also holds the padding rows) ...
+int real_rows(const fwx_matrix *m, const SlabData &d) { return d.row0 + d.rows <= m->n ? d.rows : m->n - d.row0; }
+// ... to (`in`) or from the slab's array `dev` of pitch nd.  `host` is the caller's array, host or device memory
+// (hipMemcpyDefault): all n rows -- or, with one partition per process, just this slab's.  One flat copy where
+// nd == n on a single-device handle; partitions always take the 2-D form, as they always did, so that merging
+// the two kinds changed no HIP call there.
+int copy_rows(const fwx_matrix *m, const SlabData &d, void *dev, void *host, size_t es, bool in)
 {
     const size_t n = (size_t)m->n, nd = (size_t)m->nd;
-    if (nd == n) FWX_HIP(hipMemcpyAsync(dev, src, n * n * es, hipMemcpyDefault, s));
-    else FWX_HIP(hipMemcpy2DAsync(dev, nd * es, src, n * es, n * es, n, hipMemcpyDefault, s));
+    const int real = real_rows(m, d);
+    if (!host || real <= 0) return FWX_OK;
+    if (!m->multi || multi_self(m) < 0) host = (char *)host + (size_t)d.row0 * n * es;
+    void *dst = in ? dev : host;
+    const void *src = in ? host : dev;
+    if (nd == n && !m->multi) FWX_HIP(hipMemcpyAsync(dst, src, (size_t)real * n * es, hipMemcpyDefault, d.main));
+    else FWX_HIP(hipMemcpy2DAsync(dst, (in ? nd : n) * es, src, (in ? n : nd) * es, n * es, (size_t)real,
+                                  hipMemcpyDefault, d.main));
     return FWX_OK;
 }
-int copy_out(fwx_matrix *m, void *dst, const void *dev, size_t es, hipStream_t s)
-{
-    const size_t n = (size_t)m->n, nd = (size_t)m->nd;
-    if (nd == n) FWX_HIP(hipMemcpyAsync(dst, dev, n * n * es, hipMemcpyDefault, s));
-    else FWX_HIP(hipMemcpy2DAsync(dst, n * es, dev, nd * es, n * es, n, hipMemcpyDefault, s));
-    return FWX_OK;
-}
-// entry index of the caller's n x n view (i * n + j) -> offset in the device arrays
-inline size_t dev_offset(const fwx_matrix *m, int64_t index)
-{
-    return (size_t)(index / m->n) * (size_t)m->nd + (size_t)(index % m->n);
-}
 
-// The handle as one slab of all its rows (fwx_resume.h), work on its own stream.
-Slab slab_of(const fwx_matrix *m)
-{
-    Slab v;
-    v.live = {m->rate, m->next, m->hops, m->plog.last, m->plog.at_col, m->plog.at_row};
-    v.kept.rate = m->rate0; v.kept.next = m->next0; v.kept.hops = m->hops0;
-    v.rows = v.nd = m->nd;
-    v.ct_ld = (m->nd + 3) & ~3;
-    v.es = m->dtype == FWX_F64 ? 8 : 4;
-    v.s = m->stream;
-    return v;
-}
-
-void resume_free(Resume *r)
-{
-    if (!r) return;
-    store_free(r->store);
-    delete r;
-}
-
-// The patched entries (indices of the caller's n x n view) into the kept input; offs, if given: their offsets
-// in the device arrays.
-int patch_kept_input(const fwx_matrix *m, const Slab &v, int32_t count, const int64_t *index, const void *rate_vals,
+// The patched entries (indices of the caller's n x n view) into the kept input, each on the slab that owns its
+// row (an entry of a row another process holds is skipped); offs, if given: per slab, their offsets in its
+// arrays.
+int patch_kept_entries(fwx_matrix *m, DeviceGuard &g, int32_t count, const int64_t *index, const void *rate_vals,
                      const int32_t *next_vals, const int32_t *hops_vals, std::vector<int64_t> *offs = nullptr)
 {
-    for (int32_t q = 0; q < count; ++q) {
-        const size_t off = dev_offset(m, index[q]);
-        if (offs) offs->push_back((int64_t)off);
-        const int rc = patch_kept(v, off, q, rate_vals, next_vals, hops_vals);
-        if (rc) return rc;
-    }
-    return FWX_OK;
+    const size_t es = m->dtype == FWX_F64 ? 8 : 4;
+    return each_slab(m, &g, [&](SlabData &d, int p) -> int {
+        const Slab v = slab_of(d, m->nd, es);
+        for (int32_t q = 0; q < count; ++q) {
+            const int64_t row = index[q] / m->n - d.row0;
+            if (row < 0 || row >= d.rows) continue;
+            const size_t off = (size_t)row * (size_t)m->nd + (size_t)(index[q] % m->n);
+            if (offs) offs[p].push_back((int64_t)off);
+            const int rc = patch_kept(v, off, q, rate_vals, next_vals, hops_vals);
+            if (rc) return rc;
+        }
+        return FWX_OK;
+    });
 }
 
 }  // namespace
@@ -1145,24 +1136,28 @@ int fwx_matrix_create(fwx_matrix **out, int32_t n, int32_t dtype, int32_t with_n
         if (!m) return FWX_ERR_OOM;
         memset(m, 0, sizeof(*m));
         m->n = n; m->dtype = dtype; m->device = dev;
+        m->with_next = with_next != 0; m->with_hops = with_hops != 0;
         const size_t es = dtype == FWX_F64 ? 8 : 4;
         // rows of 16-byte vectors for any n (fwx_matrix::nd): the arrays are nd x nd, the padding is
         // written here, once -- nothing ever stores a different value into it
         const int vw = (int)(16 / es);
         m->nd = (n + vw - 1) / vw * vw;
+        SlabData &d = m->slab;               // the one slab: all rows
+        d = SlabData();
+        d.device = dev; d.rows = m->nd; d.ct_ld = (m->nd + 3) & ~3;
         const size_t nn = (size_t)m->nd * (size_t)m->nd;
-        hipError_t e = hipMalloc(&m->rate, nn * es ? nn * es : 1);
-        if (e == hipSuccess && with_next) e = hipMalloc((void **)&m->next, nn * 4 ? nn * 4 : 1);
-        if (e == hipSuccess && with_hops) e = hipMalloc((void **)&m->hops, nn * 4 ? nn * 4 : 1);
+        hipError_t e = hipMalloc(&d.rate, nn * es ? nn * es : 1);
+        if (e == hipSuccess && with_next) e = hipMalloc((void **)&d.next, nn * 4 ? nn * 4 : 1);
+        if (e == hipSuccess && with_hops) e = hipMalloc((void **)&d.hops, nn * 4 ? nn * 4 : 1);
         if (e == hipSuccess) e = hipMalloc((void **)&m->scratch, ((size_t)n + 2) * 4);
         if (e == hipSuccess) e = hipMalloc((void **)&m->upd, FWX_UPDATE_SHARDS * 8);
         if (e == hipSuccess) e = hipMalloc((void **)&m->flag, 16);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&d.main, hipStreamNonBlocking);
         if (e == hipSuccess && m->nd != n) {
-            e = hipMemsetAsync(m->rate, 0, nn * es, m->stream);                                  // +0.0
-            if (e == hipSuccess && m->next) e = hipMemsetAsync(m->next, 0xFF, nn * 4, m->stream);   // -1
-            if (e == hipSuccess && m->hops) e = hipMemsetAsync(m->hops, 0, nn * 4, m->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+            e = hipMemsetAsync(d.rate, 0, nn * es, d.main);                                  // +0.0
+            if (e == hipSuccess && d.next) e = hipMemsetAsync(d.next, 0xFF, nn * 4, d.main);   // -1
+            if (e == hipSuccess && d.hops) e = hipMemsetAsync(d.hops, 0, nn * 4, d.main);
+            if (e == hipSuccess) e = hipStreamSynchronize(d.main);
         }
         if (e != hipSuccess) {
             g_last_hip = (int)e;
@@ -1179,37 +1174,24 @@ int fwx_matrix_destroy(fwx_matrix *m)
 {
     return fwxi::guarded([&]() -> int {
         if (!m) return FWX_OK;
+        // order, on either kind: retire every command that used the arrays, then the streams and their
+        // events, then the memory; a slab's own stream, arrays and store go in slab_release
         if (m->multi) {
             multi_destroy(m);
-            delete m;
-            return FWX_OK;
+        } else {
+            DeviceGuard g;
+            (void)g.enter(m->device);
+            drain_stream(m->slab.main);
+            if (m->side) m->side->drain();
+            delete m->side;
+            slab_release(m->slab);
+            if (m->scratch) (void)hipFree(m->scratch);
+            if (m->upd) (void)hipFree(m->upd);
+            if (m->walk) (void)hipFree(m->walk);
+            if (m->ws) (void)hipFree(m->ws);
+            if (m->flag) (void)hipFree(m->flag);
         }
-        DeviceGuard g;
-        (void)g.enter(m->device);
-        // order: retire every command that used the arrays, then the streams and their events, then
-        // the memory
-        drain_stream(m->stream);
-        if (m->side) m->side->drain();
-        delete m->side;
-        m->side = nullptr;
-        if (m->stream) (void)hipStreamDestroy(m->stream);
-        m->stream = nullptr;
-        if (m->rate) (void)hipFree(m->rate);
-        if (m->next) (void)hipFree(m->next);
-        if (m->hops) (void)hipFree(m->hops);
-        if (m->scratch) (void)hipFree(m->scratch);
-        if (m->upd) (void)hipFree(m->upd);
-        if (m->plog.last) (void)hipFree(m->plog.last);
-        if (m->plog.at_col) (void)hipFree(m->plog.at_col);
-        if (m->plog.at_row) (void)hipFree(m->plog.at_row);
-        if (m->next0) (void)hipFree(m->next0);
-        if (m->rate0) (void)hipFree(m->rate0);
-        if (m->hops0) (void)hipFree(m->hops0);
-        if (m->walk) (void)hipFree(m->walk);
-        resume_free(m->resume);
-        m->resume = nullptr;
-        if (m->ws) (void)hipFree(m->ws);
-        if (m->flag) (void)hipFree(m->flag);
+        delete m->resume;
         delete m;
         return FWX_OK;
     });
@@ -1220,25 +1202,34 @@ int fwx_matrix_upload(fwx_matrix *m, const void *rate, const int32_t *next, cons
     return fwxi::guarded([&]() -> int {
         if (!m) return FWX_ERR_INVALID;
         if (m->n == 0) return FWX_OK;
-        if (!rate || (m->next && !next) || (m->hops && !hops)) return FWX_ERR_INVALID;
-        if (m->multi) return multi_upload(m, rate, next, hops);
+        if (!rate || (m->with_next && !next) || (m->with_hops && !hops)) return FWX_ERR_INVALID;
         DeviceGuard g;
-        int rc = g.enter(m->device);
+        int rc = enter_handle(g, m);
         if (rc) return rc;
         const size_t es = m->dtype == FWX_F64 ? 8 : 4;
-        // hipMemcpyDefault: the sources may be host arrays (what an FFI hands over) or device arrays
-        // (a caller that keeps its pristine input in HBM, e.g. the benchmark)
-        hipStream_t s = m->stream;
         m->dom_known = 0;                  // a new input: the domain check has to look at it
         if (m->resume) m->resume->valid_upto = 0;   // ... and nothing of the old solve can be resumed
-        if ((rc = copy_in(m, m->rate, rate, es, s))) return rc;
-        if (m->next && (rc = copy_in(m, m->next, next, 4, s))) return rc;
-        if (m->hops && (rc = copy_in(m, m->hops, hops, 4, s))) return rc;
-        // traced matrix: keep the uploaded next-hops (paths of entries never improved); kept input: all of it
-        if ((rc = keep_live(slab_of(m)))) return rc;
-        if (m->next0) m->rec_ready = 0;   // the trace of an earlier input is stale
+        // the sources may be host arrays (what an FFI hands over) or device arrays (a caller that keeps its
+        // pristine input in HBM, e.g. the benchmark)
+        rc = each_slab(m, &g, [&](SlabData &d, int) -> int {
+            const size_t cells = (size_t)d.rows * (size_t)m->nd;
+            if (m->multi && m->nd != m->n) {      // a partitioned handle writes its padding on every upload
+                FWX_HIP(hipMemsetAsync(d.rate, 0, cells * es, d.main));                   // +0.0
+                if (d.next) FWX_HIP(hipMemsetAsync(d.next, 0xFF, cells * 4, d.main));     // -1
+                if (d.hops) FWX_HIP(hipMemsetAsync(d.hops, 0, cells * 4, d.main));
+            }
+            if (real_rows(m, d) <= 0) return FWX_OK;   // (an empty partition)
+            int rc2;
+            if ((rc2 = copy_rows(m, d, d.rate, const_cast<void *>(rate), es, true))) return rc2;
+            if (d.next && (rc2 = copy_rows(m, d, d.next, const_cast<int32_t *>(next), 4, true))) return rc2;
+            if (d.hops && (rc2 = copy_rows(m, d, d.hops, const_cast<int32_t *>(hops), 4, true))) return rc2;
+            // traced matrix: keep the uploaded next-hops (paths of entries never improved); kept input: all of it
+            return keep_live(slab_of(d, m->nd, es));
+        });
+        if (rc) return rc;
+        if (m->traced || (m->keep && m->with_next)) m->rec_ready = 0;   // (a next0 exists) the trace of an earlier input is stale
         if (m->keep) m->kept_valid = 1;
-        FWX_HIP(hipStreamSynchronize(s));
+        if ((rc = sync_slabs(m, g))) return rc;
         m->fresh = 1;
         if (m->resume) m->resume->state_at = m->keep ? 0 : -1;
         return FWX_OK;
@@ -1248,14 +1239,17 @@ int fwx_matrix_upload(fwx_matrix *m, const void *rate, const int32_t *next, cons
 int fwx_matrix_enable_path_log(fwx_matrix *m)
 {
     return fwxi::guarded([&]() -> int {
-        if (!m || !m->next || m->plog.last) return FWX_ERR_INVALID;
+        if (!m || !m->with_next || m->traced) return FWX_ERR_INVALID;
         if (m->resume) return FWX_ERR_INVALID;     // the checkpoints were sized without the trace: enable it first
         if (m->n == 0) return FWX_OK;
-        if (m->multi) return multi_enable_path_log(m);
         DeviceGuard g;
-        int rc = g.enter(m->device);
+        int rc = enter_handle(g, m);
         if (rc) return rc;
-        if ((rc = trace_alloc(m->plog, m->next0, m->next, (size_t)m->nd * (size_t)m->nd, m->fresh, m->stream))) return rc;
+        rc = each_slab(m, &g, [&](SlabData &d, int) -> int {
+            return trace_alloc(d, (size_t)d.rows * (size_t)m->nd, m->fresh);
+        });
+        if (rc) return rc;
+        m->traced = 1;
         m->rec_ready = 0;
         return FWX_OK;
     });
@@ -1266,17 +1260,19 @@ int fwx_matrix_keep_input(fwx_matrix *m)
     return fwxi::guarded([&]() -> int {
         if (!m) return FWX_ERR_INVALID;
         if (m->keep || m->n == 0) return FWX_OK;
-        if (m->multi) return multi_keep_input(m);
         DeviceGuard g;
-        int rc = g.enter(m->device);
+        int rc = enter_handle(g, m);
         if (rc) return rc;
-        if ((rc = kept_alloc(m->rate0, m->next0, m->hops0, m->next, m->hops, (size_t)m->nd * (size_t)m->nd,
-                             m->dtype == FWX_F64 ? 8 : 4)))
-            return rc;
+        const size_t es = m->dtype == FWX_F64 ? 8 : 4;
+        rc = each_slab(m, &g, [&](SlabData &d, int) -> int {
+            const int rc2 = kept_alloc(d, (size_t)d.rows * (size_t)m->nd, es);
+            if (rc2 || !m->fresh) return rc2;
+            return keep_live(slab_of(d, m->nd, es));     // an unsolved upload is in the arrays: the input to keep
+        });
+        if (rc) return rc;
         m->keep = 1;
-        if (m->fresh) {          // an unsolved upload is in the arrays: that is the input to keep
-            if ((rc = keep_live(slab_of(m)))) return rc;
-            FWX_HIP(hipStreamSynchronize(m->stream));
+        if (m->fresh) {
+            if ((rc = sync_slabs(m, g))) return rc;
             m->kept_valid = 1;
         }
         return FWX_OK;
@@ -1290,23 +1286,23 @@ int fwx_matrix_patch_input(fwx_matrix *m, int32_t count, const int64_t *index, c
         if (!m || count < 0 || count > FWX_MAX_PATCH || (count > 0 && (!index || !rate_vals)))
             return FWX_ERR_INVALID;
         if (!m->keep || !m->kept_valid) return FWX_ERR_INVALID;
-        if ((next_vals && !m->next) || (hops_vals && !m->hops)) return FWX_ERR_INVALID;
+        if ((next_vals && !m->with_next) || (hops_vals && !m->with_hops)) return FWX_ERR_INVALID;
         const int64_t nn64 = (int64_t)m->n * m->n;
         for (int32_t q = 0; q < count; ++q)
             if (index[q] < 0 || index[q] >= nn64) return FWX_ERR_INVALID;
-        if (m->multi) return multi_patch_input(m, count, index, rate_vals, next_vals, hops_vals);
         DeviceGuard g;
-        int rc = g.enter(m->device);
+        int rc = enter_handle(g, m);
         if (rc) return rc;
-        const Slab v = slab_of(m);
+        const size_t es = m->dtype == FWX_F64 ? 8 : 4;
         if (m->resume) m->resume->valid_upto = 0;   // the kept input changes without a replay
         // the remembered domain answer survives a patch whose values are themselves inside the domain
         // (rate >= +0 and not NaN; a non-zero rate comes with a next-hop >= 0); anything else, or a
         // non-zero rate patched in without its next-hop, sends the next solve through the check again
         if (m->dom_known && !patch_keeps_domain(m, count, rate_vals, next_vals)) m->dom_known = 0;
-        if ((rc = patch_kept_input(m, v, count, index, rate_vals, next_vals, hops_vals))) return rc;
-        if ((rc = restore_kept(v))) return rc;
-        FWX_HIP(hipStreamSynchronize(v.s));
+        if ((rc = patch_kept_entries(m, g, count, index, rate_vals, next_vals, hops_vals))) return rc;
+        if ((rc = each_slab(m, &g, [&](SlabData &d, int) -> int { return restore_kept(slab_of(d, m->nd, es)); })))
+            return rc;
+        if ((rc = sync_slabs(m, g))) return rc;
         m->fresh = 1;
         m->rec_ready = 0;
         if (m->resume) m->resume->state_at = 0;      // the patched kept input, unsolved
@@ -1332,13 +1328,18 @@ int fwx_matrix_resume_bytes(const fwx_matrix *m, int32_t checkpoints, uint64_t *
 {
     return fwxi::guarded([&]() -> int {
         if (!m || !bytes_out || checkpoints < 0 || checkpoints > FWX_MAX_CHECKPOINTS) return FWX_ERR_INVALID;
-        const SlabCells d = m->multi ? multi_resume_cells(m) : slab_cells(m->nd, m->nd, (m->nd + 3) & ~3);
+        SlabCells d = {0, 0, 0};               // summed over the slabs: every partition keeps all pivot rows
+        (void)each_slab(m, nullptr, [&](const SlabData &q, int) -> int {
+            const SlabCells c = slab_cells(q.rows, m->nd, q.ct_ld);
+            d.cells += c.cells; d.col_cells += c.col_cells; d.w_cells += c.w_cells;
+            return FWX_OK;
+        });
         const uint64_t es = m->dtype == FWX_F64 ? 8 : 4;
         // per checkpoint: one copy of every array; panels: w + ct (+ cnt) (+ wh + cht) for all pivots
         // (a partitioned handle: every partition keeps all pivot ROWS, its own part of the columns)
-        const uint64_t per_cp = d.cells * (es + (m->next ? 4 : 0) + (m->hops ? 4 : 0) + (m->plog.last ? 12 : 0));
-        const uint64_t panels = d.w_cells * es + d.col_cells * es + (m->next ? d.col_cells * 4 : 0) +
-                                (m->hops ? d.w_cells * 4 + d.col_cells * 4 : 0);
+        const uint64_t per_cp = d.cells * (es + (m->with_next ? 4 : 0) + (m->with_hops ? 4 : 0) + (m->traced ? 12 : 0));
+        const uint64_t panels = d.w_cells * es + d.col_cells * es + (m->with_next ? d.col_cells * 4 : 0) +
+                                (m->with_hops ? d.w_cells * 4 + d.col_cells * 4 : 0);
         // ONE index buffer, although every partition of a partitioned handle allocates its own: the session's
         // memory budget (host/session.cpp) was tuned against this figure, so it stays as it is
         *bytes_out = (uint64_t)checkpoints * per_cp + panels + (uint64_t)FWX_MAX_PATCH * 8;
@@ -1352,22 +1353,35 @@ int fwx_matrix_enable_resume(fwx_matrix *m, int32_t checkpoints)
         if (!m || checkpoints < 1 || checkpoints > FWX_MAX_CHECKPOINTS) return FWX_ERR_INVALID;
         if (m->resume) return FWX_ERR_INVALID;
         if (!m->keep) return FWX_ERR_INVALID;                // replays start from the kept input
-        if (m->multi) return m->n <= kSmallSolveAutoMax ? FWX_ERR_UNSUPPORTED : multi_enable_resume(m, checkpoints);
         // resumable = AUTO takes the fused engine for this order (fwx.h fwx_engine)
         if (m->n <= kSmallSolveAutoMax) return FWX_ERR_UNSUPPORTED;
         DeviceGuard g;
-        int rc = g.enter(m->device);
+        int rc = enter_handle(g, m);
         if (rc) return rc;
+        const size_t es = m->dtype == FWX_F64 ? 8 : 4;
         fail_point();
         // a failure (an allocation, or the throw above) leaves nothing behind: the handle stays usable
         struct Holder {
+            fwx_matrix *m; DeviceGuard &g;
             Resume *r = new Resume();
-            ~Holder() { resume_free(r); }
-        } hold;
+            ~Holder()
+            {
+                if (!r) return;
+                (void)each_slab(m, &g, [](SlabData &d, int) -> int { store_free(d.store); return FWX_OK; });
+                delete r;
+            }
+        } hold{m, g};
         Resume *R = hold.r;
-        R->pivot = checkpoint_pivots(m->n, checkpoints);
+        // only block starts: a pivot block never straddles two slabs, so inside a slab blocks start at row0 + 64 t
+        R->pivot = checkpoint_pivots(m->n, checkpoints, [&](int c) {
+            return (c - slab_row0_of(m, c)) % FWX_FUSED_B == 0;
+        });
         R->count = (int)R->pivot.size();
-        if ((rc = store_alloc(R->store, slab_of(m), R->count))) return rc;
+        rc = each_slab(m, &g, [&](SlabData &d, int) -> int {
+            fail_point();         // (per slab: a failure here finds the stores of the slabs before it allocated)
+            return store_alloc(d.store, slab_of(d, m->nd, es), R->count);
+        });
+        if (rc) return rc;
         R->state_at = (m->fresh && m->kept_valid) ? 0 : -1;
         m->resume = R;            // complete: owned by the handle from here on
         hold.r = nullptr;
@@ -1384,7 +1398,7 @@ int fwx_matrix_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const
         if (!m || count < 0 || count > FWX_MAX_PATCH || (count > 0 && (!index || !rate_vals)))
             return FWX_ERR_INVALID;
         if (!m->keep || !m->kept_valid) return FWX_ERR_INVALID;
-        if ((next_vals && !m->next) || (hops_vals && !m->hops)) return FWX_ERR_INVALID;
+        if ((next_vals && !m->with_next) || (hops_vals && !m->with_hops)) return FWX_ERR_INVALID;
         const int64_t nn64 = (int64_t)m->n * m->n;
         int64_t lowest = m->n;                       // min over the patched entries' indices
         for (int32_t q = 0; q < count; ++q) {
@@ -1414,41 +1428,41 @@ int fwx_matrix_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const
             if ((rc = fwx_matrix_patch_input(m, count, index, rate_vals, next_vals, hops_vals))) return rc;
             return fwx_matrix_solve(m, opts);
         }
-        if (m->multi) {
-            rc = multi_resolve(m, count, index, rate_vals, next_vals, hops_vals, c_idx, op);
-            if (!rc && resumed_from) *resumed_from = R->pivot[(size_t)c_idx];
-            return rc;
-        }
         DeviceGuard g;
-        if ((rc = g.enter(m->device))) return rc;
-        const Slab v = slab_of(m);
-        hipStream_t s = v.s;
+        if ((rc = enter_handle(g, m))) return rc;
+        const size_t es = m->dtype == FWX_F64 ? 8 : 4;
         const int c = R->pivot[(size_t)c_idx];
         R->valid_upto = 0;                           // until the resumed solve has finished
+        // offs: per slab, the patched entries' offsets in its arrays (pitch nd).  The replay reads them with an
+        // asynchronous copy, so they outlive every synchronisation below, Unwind's included
+        std::vector<int64_t> offs[FWX_MAX_PARTS];
         // Any error return below leaves the handle in a state the next call can start from: nothing of this
-        // call still queued on the stream (the small copies read the caller's arrays), nothing resumable,
+        // call still queued on a slab's stream (the small copies read the caller's arrays), nothing resumable,
         // the live arrays no known state of the kept input (the next resolve / patch_input restores them).
         struct Unwind {
-            fwx_matrix *m; hipStream_t s; bool armed = true;
+            fwx_matrix *m; DeviceGuard &g; bool armed = true;
             ~Unwind()
             {
                 if (!armed) return;
-                (void)hipStreamSynchronize(s);
+                (void)sync_slabs(m, g);
                 m->resume->valid_upto = 0;
                 m->resume->state_at = -1;
                 m->fresh = 0;
                 m->rec_ready = 0;
             }
-        } unwind{m, s};
-        // the kept input first (the replay reads it), then the state at the start of step c, except the patched
-        // entries: replayed.  dindex: their offsets in the device arrays (pitch nd), alive until the solve
-        // below has synchronised the stream
-        std::vector<int64_t> dindex;
-        dindex.reserve((size_t)count);
-        if ((rc = patch_kept_input(m, v, count, index, rate_vals, next_vals, hops_vals, &dindex))) return rc;
-        if ((rc = restore_checkpoint(R->store, v, c_idx))) return rc;
-        rc = m->dtype == FWX_F64 ? replay_entries<double>(R->store, v, *R, c_idx, dindex.data(), dindex.size())
-                                 : replay_entries<float>(R->store, v, *R, c_idx, dindex.data(), dindex.size());
+        } unwind{m, g};
+        // the kept input first (the replay reads it), then on every slab the state at the start of step c, except
+        // its patched entries: replayed through pivots [0, c) from the stored panels (the slab's own column
+        // snapshots and the pivot rows every slab keeps)
+        if ((rc = patch_kept_entries(m, g, count, index, rate_vals, next_vals, hops_vals, offs))) return rc;
+        rc = each_slab(m, &g, [&](SlabData &d, int p) -> int {
+            if (d.rows == 0) return FWX_OK;
+            const Slab v = slab_of(d, m->nd, es);
+            const int rc2 = restore_checkpoint(d.store, v, c_idx);
+            if (rc2 || offs[p].empty()) return rc2;
+            return m->dtype == FWX_F64 ? replay_entries<double>(d.store, v, *R, c_idx, offs[p].data(), offs[p].size())
+                                       : replay_entries<float>(d.store, v, *R, c_idx, offs[p].data(), offs[p].size());
+        });
         if (rc) return rc;
         m->fresh = 0;
         m->rec_ready = 0;
@@ -1456,12 +1470,14 @@ int fwx_matrix_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const
                                                      // later ones are the old solve's until this one passes them
         op.k_begin = c;
         R->state_at = op.k_begin;                    // the live arrays: the NEW kept input at time c
-        if (m->plog.last) {
-            rc = logged_solve(m, op, s, true);
+        if (m->multi) {
+            rc = multi_solve(m, op, true);
+        } else if (m->traced) {
+            rc = logged_solve(m, op, m->slab.main, true);
         } else {
-            rc = m->dtype == FWX_F64 ? matrix_solve_typed<double>(m, op, nullptr, s)
-                                     : matrix_solve_typed<float>(m, op, nullptr, s);
-            if (!rc) FWX_HIP(hipStreamSynchronize(s));
+            rc = m->dtype == FWX_F64 ? matrix_solve_typed<double>(m, op, nullptr, m->slab.main)
+                                     : matrix_solve_typed<float>(m, op, nullptr, m->slab.main);
+            if (!rc) FWX_HIP(hipStreamSynchronize(m->slab.main));
         }
         if (rc) return rc;
         unwind.armed = false;
@@ -1474,7 +1490,7 @@ int fwx_matrix_path_log_count(fwx_matrix *m, uint64_t *count_out)
 {
     return fwxi::guarded([&]() -> int {
         if (!m || !count_out) return FWX_ERR_INVALID;
-        *count_out = (m->plog.last && m->rec_ready) ? m->last_u : 0;
+        *count_out = (m->traced && m->rec_ready) ? m->last_u : 0;
         return FWX_OK;
     });
 }
@@ -1485,15 +1501,15 @@ int fwx_matrix_query_exact(fwx_matrix *m, int32_t src, int32_t dst, double *rate
     return fwxi::guarded([&]() -> int {
         if (!m || src < 0 || dst < 0 || src >= m->n || dst >= m->n || cap <= 0 || !path_out)
             return FWX_ERR_INVALID;
-        if (!m->plog.last) return FWX_ERR_INVALID;
+        if (!m->traced) return FWX_ERR_INVALID;
         if (!m->rec_ready) return FWX_ERR_INVALID;             // no traced solve of this upload yet
         if (m->multi) return multi_query_exact(m, src, dst, rate_out, path_out, cap);
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        hipStream_t s = m->stream;
+        hipStream_t s = m->slab.main;
         RateRead rate;
-        if ((rc = rate.queue(m->rate, (size_t)src * m->nd + dst, m->dtype, s, rate_out))) return rc;
+        if ((rc = rate.queue(m->slab.rate, (size_t)src * m->nd + dst, m->dtype, s, rate_out))) return rc;
         if (!m->walk || m->walk_cap < cap) {      // grow-only scratch, reused across queries
             if (m->walk) { drain_stream(s); (void)hipFree(m->walk); m->walk = nullptr; }
             FWX_HIP(hipMalloc((void **)&m->walk, ((size_t)4 * cap + 1) * 4));
@@ -1513,13 +1529,13 @@ int fwx_matrix_query_exact_batch(fwx_matrix *m, int32_t count, const int32_t *sr
     return fwxi::guarded([&]() -> int {
         if (!m || count < 0 || cap <= 0) return FWX_ERR_INVALID;
         if (count == 0) return FWX_OK;
-        if (!src || !dst || !len_out || !path_out || !m->plog.last) return FWX_ERR_INVALID;
+        if (!src || !dst || !len_out || !path_out || !m->traced) return FWX_ERR_INVALID;
         if (!m->rec_ready) return FWX_ERR_INVALID;
         if (m->multi) return multi_query_exact_batch(m, count, src, dst, len_out, path_out, cap);
         DeviceGuard g;
         int rc = g.enter(m->device);
         if (rc) return rc;
-        return run_exact_batch(tab_of(m), m->n, m->stream, count, src, dst, len_out, path_out, cap);
+        return run_exact_batch(tab_of(m), m->n, m->slab.main, count, src, dst, len_out, path_out, cap);
     });
 }
 
@@ -1528,18 +1544,19 @@ int fwx_matrix_download(fwx_matrix *m, void *rate, int32_t *next, int32_t *hops)
     return fwxi::guarded([&]() -> int {
         if (!m) return FWX_ERR_INVALID;
         if (m->n == 0) return FWX_OK;
-        if ((next && !m->next) || (hops && !m->hops)) return FWX_ERR_INVALID;
-        if (m->multi) return multi_download(m, rate, next, hops);
+        if ((next && !m->with_next) || (hops && !m->with_hops)) return FWX_ERR_INVALID;
         DeviceGuard g;
-        int rc = g.enter(m->device);
+        int rc = enter_handle(g, m);
         if (rc) return rc;
         const size_t es = m->dtype == FWX_F64 ? 8 : 4;
-        hipStream_t s = m->stream;
-        if (rate && (rc = copy_out(m, rate, m->rate, es, s))) return rc;
-        if (next && (rc = copy_out(m, next, m->next, 4, s))) return rc;
-        if (hops && (rc = copy_out(m, hops, m->hops, 4, s))) return rc;
-        FWX_HIP(hipStreamSynchronize(s));
-        return FWX_OK;
+        rc = each_slab(m, &g, [&](SlabData &d, int) -> int {
+            int rc2;
+            if ((rc2 = copy_rows(m, d, d.rate, rate, es, false)) || (rc2 = copy_rows(m, d, d.next, next, 4, false)) ||
+                (rc2 = copy_rows(m, d, d.hops, hops, 4, false)))
+                return rc2;
+            return FWX_OK;
+        });
+        return rc ? rc : sync_slabs(m, g);
     });
 }
 
@@ -1554,8 +1571,8 @@ int fwx_matrix_solve(fwx_matrix *m, const fwx_opts *opts)
         if (m->multi) return multi_solve(m, op);
         DeviceGuard g;
         if ((rc = g.enter(m->device))) return rc;
-        hipStream_t s = op.has_stream ? op.stream : m->stream;
-        if (m->plog.last) return logged_solve(m, op, s);
+        hipStream_t s = op.has_stream ? op.stream : m->slab.main;
+        if (m->traced) return logged_solve(m, op, s);
         unsigned long long *upd = op.updates_out ? m->upd : nullptr;
         if (upd) FWX_HIP(hipMemsetAsync(upd, 0, FWX_UPDATE_SHARDS * 8, s));
         if (m->dtype == FWX_F64)
@@ -1582,13 +1599,13 @@ int fwx_matrix_query(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out, 
         int rc = g.enter(m->device);
         if (rc) return rc;
         RateRead rate;
-        if ((rc = rate.queue(m->rate, (size_t)src * m->nd + dst, m->dtype, m->stream, rate_out))) return rc;
-        if (!m->next) {
-            FWX_HIP(hipStreamSynchronize(m->stream));
+        if ((rc = rate.queue(m->slab.rate, (size_t)src * m->nd + dst, m->dtype, m->slab.main, rate_out))) return rc;
+        if (!m->with_next) {
+            FWX_HIP(hipStreamSynchronize(m->slab.main));
             rate.done();
             return FWX_ERR_INVALID;
         }
-        const int len = run_follow(tab_of(m), m->n, m->stream, m->scratch, src, dst, path_out, cap);
+        const int len = run_follow(tab_of(m), m->n, m->slab.main, m->scratch, src, dst, path_out, cap);
         rate.done();
         return len;
     });
@@ -1658,7 +1675,9 @@ int fwx_dev_solve(const fwx_slab *full, const fwx_opts *opts)
         fwx_matrix m;
         memset(&m, 0, sizeof(m));
         m.n = m.nd = full->n; m.dtype = full->dtype;      // caller-owned memory: pitch n, no padding
-        m.rate = full->rate; m.next = full->next; m.hops = full->hops;
+        m.with_next = full->next != nullptr; m.with_hops = full->hops != nullptr;
+        m.slab.rate = full->rate; m.slab.next = full->next; m.slab.hops = full->hops;
+        m.slab.rows = m.nd; m.slab.ct_ld = (m.nd + 3) & ~3;
         DeviceGuard g;                       // the context belongs to the device the call runs on
         if ((rc = g.enter(op.device))) return rc;
         CtxLease lease;

@@ -41,7 +41,10 @@ inline int device_count()
     return c;
 }
 
-// Sets the requested device for the scope of one ABI call and restores the caller's.
+// The current device for the scope of one ABI call; the caller's is restored on the way out.  enter() is the
+// checked form of the single-device entry points; set() is what the loops over a partitioned handle's slabs
+// call.  Neither issues hipSetDevice for a device that is current already; set() asks the runtime what is
+// current, so code that is not the library's (RCCL, the host's exchange callback) cannot leave it mistaken.
 struct DeviceGuard {
     int prev = -1;
     bool changed = false;
@@ -58,6 +61,18 @@ struct DeviceGuard {
         }
         return FWX_OK;
     }
+    int set(int device)
+    {
+        int now = -1;
+        FWX_HIP(hipGetDevice(&now));
+        if (prev < 0) prev = now;
+        if (device != now) {
+            FWX_HIP(hipSetDevice(device));
+            changed = true;
+        }
+        return FWX_OK;
+    }
+    void keep() { changed = false; }   // (a thread of the library's own: nothing to restore)
     ~DeviceGuard()
     {
         if (changed) (void)hipSetDevice(prev);
@@ -653,10 +668,6 @@ inline fwx::PathLog plog_rows(fwx::PathLog p, size_t off)
     return p;
 }
 
-struct MultiState;   // fwx_multi.hip: the partitions of a multi-device handle
-struct Resume;       // fwx_resume.h: what a resumable handle keeps
-struct SlabCells;
-
 // crossover (single / double pass, ms; profiles/r03_double_pass_crossover.txt): f32 4096: 4.10 / 4.74,
 // 6144: 10.47 / 10.18, 8192: 21.2 / 20.0, 12288: 68.1 / 61.0, 16384: 152.0 / 135.3; f64 6144: 23.1 / 22.1,
 // 16384: 355 / 324 -- below ~6000 the side chain (five launches per 128 pivots) is the critical path
@@ -684,80 +695,6 @@ inline int env_threshold(const char *name, int dflt)
     return dflt;
 }
 
-}  // namespace fwxi
-
-struct fwx_matrix {
-    int32_t n, dtype, device;
-    int32_t nd;            // device order = pitch of every array below: n rounded up to a multiple of 16
-                           // bytes of rate elements, so that the fused engine reads any n.  The padding
-                           // (rate +0.0, next -1, hops 0, trace -1; written once, at create / enable) is
-                           // inert: a padding index is never a pivot, and a +0.0 target never improves
-                           // (0 < +-0 and 0 < NaN are false) -- as in fwx_solve_* and the partitioned handle
-    void *rate;
-    int32_t *next, *hops, *scratch;
-    unsigned long long *upd;
-    fwx::PathLog plog;     // path trace for exact `_path` lists (last == nullptr: disabled)
-    int32_t *next0;        // the uploaded next-hop matrix: the path of an entry never improved
-    void *rate0;           // kept input (fwx_matrix_keep_input): the uploaded rates ...
-    int32_t *hops0;        // ... and hops (next0 serves both purposes)
-    int32_t keep;          // the input is kept on the device
-    int32_t kept_valid;    // ... and holds an upload
-    int32_t *walk;         // scratch of the exact-path walk (stack + output)
-    int32_t walk_cap;      // capacity (path entries) `walk` was sized for
-    int32_t rec_ready;     // a traced solve of the current upload has completed
-    int32_t fresh;         // the arrays hold an uploaded input that has not been solved yet
-    unsigned long long last_u;   // U of the last traced solve
-    hipStream_t stream;    // the handle's own non-blocking stream: every operation on the handle runs
-                           // on it (never the legacy null stream), so handles on different host
-                           // threads overlap and nothing synchronises with torch's streams
-    void *ws;              // fused-engine workspace, allocated by the first fused solve and kept
-    size_t ws_bytes;
-    fwxi::SideStream *side;      // look-ahead stream + events of the fused engine, kept likewise
-    int *flag;             // device int for the domain check
-    int32_t dom_known;     // dom_bits is the domain check's answer for what the arrays hold now.  The
-    int32_t dom_bits;      // domain (fwx.h) is closed under the algorithm -- products of non-negative
-                           // rates are >= +0 or NaN (which never wins), and a relaxation only succeeds
-                           // through a non-zero r[i][k], whose next-hop it copies -- so only an upload
-                           // or a patch can change the answer: the upload forgets it, a patch whose
-                           // values are themselves inside the domain keeps a "3".
-    fwxi::MultiState *multi;   // non-null: a row-partitioned handle (fwx_matrix_create_multi); the
-                           // single-device arrays above are then unused
-    fwxi::Resume *resume;  // non-null: panels of all pivots + state checkpoints are kept (f3, fwx_resume.h)
-};
-
-
-
-// fwx_multi.hip: what the handle entry points of fwx_api.hip call for a handle with m->multi
-namespace fwxi {
-int multi_upload(fwx_matrix *m, const void *rate, const int32_t *next, const int32_t *hops);
-int multi_download(fwx_matrix *m, void *rate, int32_t *next, int32_t *hops);
-int multi_solve(fwx_matrix *m, const Opts &op, bool resumed = false);
-int multi_enable_resume(fwx_matrix *m, int32_t checkpoints);
-SlabCells multi_resume_cells(const fwx_matrix *m);    // summed over the partitions
-int multi_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const void *rate_vals,
-                  const int32_t *next_vals, const int32_t *hops_vals, int c_idx, Opts op);
-// Does a patch with these values keep a matrix inside the domain (fwx.h) inside it?  rate >= +0 and not
-// NaN; a non-zero rate comes with a next-hop >= 0 on a handle that carries next-hops.
-inline bool patch_keeps_domain(const fwx_matrix *m, int32_t count, const void *rate_vals, const int32_t *next_vals)
-{
-    for (int32_t q = 0; q < count; ++q) {
-        const double r = m->dtype == FWX_F64 ? ((const double *)rate_vals)[q] : (double)((const float *)rate_vals)[q];
-        if (r != r || r < 0.0 || (r == 0.0 && 1.0 / r < 0.0)) return false;       // NaN, negative, -0.0
-        if (m->next && r != 0.0 && !(next_vals && next_vals[q] >= 0)) return false;
-    }
-    const int want = m->next ? 3 : 1;
-    return (m->dom_bits & want) == want;
-}
-int multi_enable_path_log(fwx_matrix *m);
-int multi_query(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out, int32_t *path_out, int32_t cap);
-int multi_query_exact(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out, int32_t *path_out,
-                      int32_t cap);
-int multi_query_exact_batch(fwx_matrix *m, int32_t count, const int32_t *src, const int32_t *dst,
-                            int32_t *len_out, int32_t *path_out, int32_t cap);
-void multi_destroy(fwx_matrix *m);
-int multi_keep_input(fwx_matrix *m);
-int multi_patch_input(fwx_matrix *m, int32_t count, const int64_t *index, const void *rate_vals,
-                      const int32_t *next_vals, const int32_t *hops_vals);
 }  // namespace fwxi
 
 #endif

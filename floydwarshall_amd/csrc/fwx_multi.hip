@@ -30,10 +30,10 @@
 
 #include "fwx.h"
 #include "fwx_guard.h"
+#include "fwx_handle.h"
 #include "fwx_internal.h"
 #include "fwx_kernels.h"
 #include "fwx_query.h"
-#include "fwx_resume.h"
 
 namespace fwxi {
 
@@ -146,14 +146,9 @@ private:
 };
 
 // ---- partitions -----------------------------------------------------------------------------------
-struct Part {
-    int device = 0, row0 = 0, rows = 0;    // rows [row0, row0 + rows) of the nd x nd device matrix
-    void *rate = nullptr;
-    int32_t *next = nullptr, *hops = nullptr;
-    fwx::PathLog plog;                      // slab-local trace matrices (rows x nd), or null
-    int32_t *next0 = nullptr;
-    void *rate0 = nullptr;                  // kept input (fwx_matrix_keep_input)
-    int32_t *hops0 = nullptr;
+// A slab (SlabData, fwx_resume.h: its rows, arrays, trace, kept input, store and `main` stream, which runs
+// colpanel + main kernels) and what the partitioned engines need beside it.
+struct Part : SlabData {
     // FOUR panel sets, each contiguous over the sets (set s of W at w[0] + s * 64 * nd, of Ct at
     // ct + s * 64 * ct_ld, ...): the single-pass schedules ping-pong between sets 0 and 1, the double
     // pass keeps block q in set q & 3, so that a pair of blocks (2P, 2P + 1) is one 128-pivot panel
@@ -161,15 +156,13 @@ struct Part {
     int32_t *wh[4] = {nullptr, nullptr, nullptr, nullptr};    // their hops (iff hops)
     void *ct = nullptr;                     // pivot-column snapshots, 4 x 64 x ct_ld
     int32_t *cnt = nullptr, *cht = nullptr; // their next-hops / hops
-    int ct_ld = 0;
     unsigned long long *upd = nullptr;
     int *flag = nullptr;
     // the panel a slot holds right now: w[slot] / wh[slot], or -- on a handle that records for resumed
     // solves -- the block's own rows of the all-pivot arrays below (bind_slot)
     void *wp[4] = {nullptr, nullptr, nullptr, nullptr};
     int32_t *whp[4] = {nullptr, nullptr, nullptr, nullptr};
-    ResumeStore R;                          // this slab's checkpoints and all-pivot panels (fwx_resume.h)
-    hipStream_t main = nullptr, side = nullptr;
+    hipStream_t side = nullptr;
     hipEvent_t rows_done = nullptr, main_done = nullptr, panel_done = nullptr;
     hipEvent_t w_ready[4] = {nullptr, nullptr, nullptr, nullptr}, main_free[4] = {nullptr, nullptr, nullptr, nullptr};
 };
@@ -255,71 +248,12 @@ static EntryTab make_tab(const MultiState &M)
     return t;
 }
 
-static int set_dev(int d)
-{
-    FWX_HIP(hipSetDevice(d));
-    return FWX_OK;
-}
-
-// Restores the caller's device when a multi call returns.
-struct DevRestore {
-    int prev = -1;
-    DevRestore() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-    ~DevRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 // The partition that holds `row`.
 static int owner_of(const MultiState &M, int row)
 {
     int p = 0;
     while (p + 1 < M.parts && row >= M.part[p + 1].row0) ++p;
     return p;
-}
-
-// Partition q as a slab (fwx_resume.h), work on its main stream.
-static Slab slab_of(const MultiState &M, const Part &q, size_t es)
-{
-    Slab v;
-    v.live = {q.rate, q.next, q.hops, q.plog.last, q.plog.at_col, q.plog.at_row};
-    v.kept.rate = q.rate0; v.kept.next = q.next0; v.kept.hops = q.hops0;
-    v.rows = q.rows; v.row0 = q.row0; v.nd = M.nd; v.ct_ld = q.ct_ld;
-    v.es = es;
-    v.s = q.main;
-    return v;
-}
-
-static void multi_free(MultiState *M)
-{
-    if (!M) return;
-    DevRestore keep;
-    // order: retire every command that used the partitions' arrays (drain_stream in fwx_internal.h),
-    // give the communicators back, destroy the streams and events, and only then free the memory
-    for (int p = 0; p < M->parts; ++p) {
-        Part &q = M->part[p];
-        if (hipSetDevice(q.device) != hipSuccess) continue;
-        if (q.main) drain_stream(q.main);
-        if (q.side) drain_stream(q.side);
-    }
-    CommCache::release(M->comms);
-    M->comms = nullptr;
-    for (int p = 0; p < M->parts; ++p) {
-        Part &q = M->part[p];
-        if (hipSetDevice(q.device) != hipSuccess) continue;
-        if (q.main) (void)hipStreamDestroy(q.main);
-        if (q.side) (void)hipStreamDestroy(q.side);
-        for (hipEvent_t e : M->timer.pool[p]) (void)hipEventDestroy(e);
-        hipEvent_t evs[] = {q.rows_done, q.main_done, q.panel_done, q.w_ready[0], q.w_ready[1], q.w_ready[2],
-                            q.w_ready[3], q.main_free[0], q.main_free[1], q.main_free[2], q.main_free[3]};
-        for (hipEvent_t e : evs)
-            if (e) (void)hipEventDestroy(e);
-        void *bufs[] = {q.rate, q.next, q.hops, q.plog.last, q.plog.at_col, q.plog.at_row, q.next0, q.rate0,
-                        q.hops0, q.w[0], q.wh[0], q.ct, q.cnt, q.cht, q.upd, q.flag};
-        for (void *b : bufs)
-            if (b) (void)hipFree(b);
-        store_free(q.R);
-        if (p == 0 && M->qscratch) (void)hipFree(M->qscratch);
-    }
-    delete M;
 }
 
 // First row of partition p of P: balanced row blocks, n * p / P -- rounded down to a multiple of 64 once every
@@ -334,7 +268,7 @@ static int part_bound(int n, int parts, int p)
     return n >= 2 * FWX_FUSED_BLOCK * parts ? b / FWX_FUSED_BLOCK * FWX_FUSED_BLOCK : b;
 }
 
-static int multi_alloc(fwx_matrix *m, int n_parts, const int32_t *devices, int exchange, int self = -1,
+static int multi_alloc(DeviceGuard &g, fwx_matrix *m, int n_parts, const int32_t *devices, int exchange, int self = -1,
                        fwx_exchange_fn xfn = nullptr, void *xctx = nullptr)
 {
     const size_t es = m->dtype == FWX_F64 ? 8 : 4;
@@ -346,7 +280,7 @@ static int multi_alloc(fwx_matrix *m, int n_parts, const int32_t *devices, int e
     M->self = self;
     M->xfn = xfn;
     M->xctx = xctx;
-    M->nd = (m->n + vw - 1) / vw * vw;
+    M->nd = m->nd = (m->n + vw - 1) / vw * vw;
     bool distinct = true;
     for (int p = 0; p < n_parts; ++p)
         for (int q = 0; q < p; ++q) distinct = distinct && devices[p] != devices[q];
@@ -363,19 +297,19 @@ static int multi_alloc(fwx_matrix *m, int n_parts, const int32_t *devices, int e
         q.rows = r1 - q.row0;
         q.ct_ld = (q.rows + 3) & ~3;
         if (!M->here(p)) continue;                 // (another process holds it)
-        int rc = set_dev(q.device);
+        int rc = g.set(q.device);
         if (rc) return rc;
         const size_t cells = (size_t)q.rows * nd;
         M->slab_bytes += cells * es;
         FWX_HIP(hipMalloc(&q.rate, cells * es ? cells * es : 16));
-        if (m->next) FWX_HIP(hipMalloc((void **)&q.next, cells * 4 ? cells * 4 : 16));
+        if (m->with_next) FWX_HIP(hipMalloc((void **)&q.next, cells * 4 ? cells * 4 : 16));
         const size_t wset = (size_t)FWX_FUSED_BLOCK * nd, cset = (size_t)FWX_FUSED_BLOCK * (q.ct_ld ? q.ct_ld : 4);
         FWX_HIP(hipMalloc(&q.w[0], 4 * wset * es));
         for (int b = 1; b < 4; ++b) q.w[b] = (char *)q.w[0] + (size_t)b * wset * es;
         for (int b = 0; b < 4; ++b) q.wp[b] = q.w[b];
         FWX_HIP(hipMalloc(&q.ct, 4 * cset * es));
-        if (m->next) FWX_HIP(hipMalloc((void **)&q.cnt, 4 * cset * 4));
-        if (m->hops) {
+        if (m->with_next) FWX_HIP(hipMalloc((void **)&q.cnt, 4 * cset * 4));
+        if (m->with_hops) {
             FWX_HIP(hipMalloc((void **)&q.hops, cells * 4 ? cells * 4 : 16));
             FWX_HIP(hipMalloc((void **)&q.wh[0], 4 * wset * 4));
             for (int b = 1; b < 4; ++b) q.wh[b] = q.wh[0] + (size_t)b * wset;
@@ -396,7 +330,7 @@ static int multi_alloc(fwx_matrix *m, int n_parts, const int32_t *devices, int e
     for (int p = 0; p < n_parts && M->self < 0; ++p)
         for (int q = 0; q < n_parts; ++q) {
             if (devices[p] == devices[q]) continue;
-            int rc = set_dev(devices[p]);
+            int rc = g.set(devices[p]);
             if (rc) return rc;
             const hipError_t e = hipDeviceEnablePeerAccess(devices[q], 0);
             if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) M->peer_all = false;
@@ -407,51 +341,6 @@ static int multi_alloc(fwx_matrix *m, int n_parts, const int32_t *devices, int e
         for (int p = 0; p < n_parts; ++p) devs[p] = devices[p];
         const int rc = CommCache::acquire(n_parts, devs, &M->comms);
         if (rc) return rc;
-    }
-    // placeholders: the single-device code paths test m->next for "carries next-hops"
-    return FWX_OK;
-}
-
-// The arrays of partition p hold rows [row0, row0 + rows) at pitch nd; the caller's are n x n.
-static int multi_copy(fwx_matrix *m, void *host_rate, int32_t *host_next, int32_t *host_hops,
-                      bool to_device)
-{
-    MultiState &M = *m->multi;
-    const size_t es = m->dtype == FWX_F64 ? 8 : 4;
-    const int n = m->n, nd = M.nd;
-    for (int p = 0; p < M.parts; ++p) {
-        Part &q = M.part[p];
-        if (!M.here(p)) continue;
-        int rc = set_dev(q.device);
-        if (rc) return rc;
-        const int real = (q.row0 + q.rows <= n ? q.rows : n - q.row0);   // rows that exist in the caller's arrays
-        if (to_device && nd != n) {
-            FWX_HIP(hipMemsetAsync(q.rate, 0, (size_t)q.rows * nd * es, q.main));              // +0.0
-            if (q.next) FWX_HIP(hipMemsetAsync(q.next, 0xFF, (size_t)q.rows * nd * 4, q.main));   // -1
-            if (q.hops) FWX_HIP(hipMemsetAsync(q.hops, 0, (size_t)q.rows * nd * 4, q.main));
-        }
-        if (real <= 0) continue;
-        auto copy = [&](void *dev, char *host, size_t e) -> int {
-            if (!host) return FWX_OK;
-            if (M.self < 0) host += (size_t)q.row0 * n * e;      // (one partition per process: the caller's arrays ARE the slab)
-            if (to_device)
-                FWX_HIP(hipMemcpy2DAsync(dev, (size_t)nd * e, host, (size_t)n * e, (size_t)n * e, (size_t)real,
-                                         hipMemcpyDefault, q.main));
-            else
-                FWX_HIP(hipMemcpy2DAsync(host, (size_t)n * e, dev, (size_t)nd * e, (size_t)n * e, (size_t)real,
-                                         hipMemcpyDefault, q.main));
-            return FWX_OK;
-        };
-        if ((rc = copy(q.rate, (char *)host_rate, es))) return rc;
-        if (q.next && (rc = copy(q.next, (char *)host_next, 4))) return rc;
-        if (q.hops && (rc = copy(q.hops, (char *)host_hops, 4))) return rc;
-        if (to_device && (rc = keep_live(slab_of(M, q, es)))) return rc;     // next0 of a traced handle; the kept input
-    }
-    for (int p = 0; p < M.parts; ++p) {
-        if (!M.here(p)) continue;
-        int rc = set_dev(M.part[p].device);
-        if (rc) return rc;
-        FWX_HIP(hipStreamSynchronize(M.part[p].main));
     }
     return FWX_OK;
 }
@@ -550,7 +439,7 @@ template <typename T> static fwx::FusedArgs<T> part_args(const MultiState &M, co
 // Snapshot panel of block b on its owner's side stream + its exchange into slot b & 1 of every
 // partition.  Precondition: the owner's main stream has recorded rows_done after bringing the
 // block's rows up to time k0.
-template <typename T> static int issue_panel(MultiState &M, const Block &blk, int slot, int step = 0)
+template <typename T> static int issue_panel(DeviceGuard &g, MultiState &M, const Block &blk, int slot, int step = 0)
 {
     Part &o = M.part[blk.owner];
     MultiTimer &tm = M.timer;
@@ -558,7 +447,7 @@ template <typename T> static int issue_panel(MultiState &M, const Block &blk, in
     const size_t hbytes = (size_t)blk.bt * M.nd * sizeof(int32_t);
     int rc;
     if (M.here(blk.owner)) {
-        if ((rc = set_dev(o.device))) return rc;
+        if ((rc = g.set(o.device))) return rc;
         FWX_HIP(hipStreamWaitEvent(o.side, o.rows_done, 0));
         FWX_HIP(hipStreamWaitEvent(o.side, o.main_free[slot], 0));       // own main kernels are done with this slot
         if (M.exchange == FWX_XCHG_PEER)
@@ -577,7 +466,7 @@ template <typename T> static int issue_panel(MultiState &M, const Block &blk, in
         // partition's side stream (behind the panel kernel on the owner, behind the last reader of the
         // slot elsewhere); every rank gets here for every panel, in the same order
         Part &q = M.part[M.self];
-        if ((rc = set_dev(q.device))) return rc;
+        if ((rc = g.set(q.device))) return rc;
         if (M.self != blk.owner) FWX_HIP(hipStreamWaitEvent(q.side, q.main_free[slot], 0));
         const int t_x = tm.begin(MultiTimer::XCHG, M.self, step, q.side);
         if (M.xfn(M.xctx, blk.k0, blk.bt, blk.owner, q.wp[slot], q.hops ? q.whp[slot] : nullptr,
@@ -589,7 +478,7 @@ template <typename T> static int issue_panel(MultiState &M, const Block &blk, in
         for (int r = 0; r < M.parts; ++r) {
             if (r == blk.owner) continue;
             Part &q = M.part[r];
-            if ((rc = set_dev(q.device))) return rc;
+            if ((rc = g.set(q.device))) return rc;
             FWX_HIP(hipStreamWaitEvent(q.side, q.main_free[slot], 0));
             FWX_HIP(hipStreamWaitEvent(q.side, o.w_ready[slot], 0));
             const int t_x = tm.begin(MultiTimer::XCHG, r, step, q.side);
@@ -609,18 +498,18 @@ template <typename T> static int issue_panel(MultiState &M, const Block &blk, in
         RcclApi &api = rccl();
         for (int r = 0; r < M.parts; ++r) {
             if (r == blk.owner) continue;
-            if ((rc = set_dev(M.part[r].device))) return rc;
+            if ((rc = g.set(M.part[r].device))) return rc;
             FWX_HIP(hipStreamWaitEvent(M.part[r].side, M.part[r].main_free[slot], 0));
         }
         int t_x[FWX_MAX_PARTS];
         for (int r = 0; r < M.parts; ++r) {
-            if ((rc = set_dev(M.part[r].device))) return rc;
+            if ((rc = g.set(M.part[r].device))) return rc;
             t_x[r] = tm.begin(MultiTimer::XCHG, r, step, M.part[r].side);
         }
         FWX_NCCL(api.GroupStart());
         for (int r = 0; r < M.parts; ++r) {
             Part &q = M.part[r];
-            if ((rc = set_dev(q.device))) return rc;
+            if ((rc = g.set(q.device))) return rc;
             FWX_NCCL(api.Broadcast(q.wp[slot], q.wp[slot], (size_t)blk.bt * M.nd,
                                    sizeof(T) == 8 ? ncclFloat64 : ncclFloat32, blk.owner, M.comms->comm[r], q.side));
             if (q.hops)     // the hops of the pivot rows travel with their rates
@@ -630,7 +519,7 @@ template <typename T> static int issue_panel(MultiState &M, const Block &blk, in
         FWX_NCCL(api.GroupEnd());
         for (int r = 0; r < M.parts; ++r) {
             Part &q = M.part[r];
-            if ((rc = set_dev(q.device))) return rc;
+            if ((rc = g.set(q.device))) return rc;
             tm.end(t_x[r], q.side);
             FWX_HIP(hipEventRecord(q.w_ready[slot], q.side));
         }
@@ -639,7 +528,7 @@ template <typename T> static int issue_panel(MultiState &M, const Block &blk, in
 }
 
 // Turns the spans of the solve that has just been synchronised into fwx_multi_timing.
-static void summarize_timing(MultiState &M)
+static void summarize_timing(DeviceGuard &g, MultiState &M)
 {
     MultiTimer &tm = M.timer;
     fwx_multi_timing &t = tm.last;
@@ -653,7 +542,7 @@ static void summarize_timing(MultiState &M)
     double sum[MultiTimer::NKIND] = {0};
     long cnt[MultiTimer::NKIND] = {0};
     for (const MultiTimer::Span &sp : tm.spans) {
-        if (hipSetDevice(M.part[sp.part].device) != hipSuccess) continue;
+        if (g.set(M.part[sp.part].device)) continue;
         float ms = 0;
         if (hipEventElapsedTime(&ms, sp.e0, sp.e1) != hipSuccess) { (void)hipGetLastError(); continue; }
         float &slot = mx[(size_t)sp.step * MultiTimer::NKIND + sp.kind];
@@ -684,7 +573,7 @@ static void summarize_timing(MultiState &M)
     t.chain_over_bulk = t.bulk_us > 0 ? t.chain_us / t.bulk_us : 0.0f;
 }
 
-static int finish_multi_solve(fwx_matrix *m, bool counting, const Opts &op)
+static int finish_multi_solve(DeviceGuard &g, fwx_matrix *m, bool counting, const Opts &op)
 {
     MultiState &M = *m->multi;
     int rc;
@@ -692,7 +581,7 @@ static int finish_multi_solve(fwx_matrix *m, bool counting, const Opts &op)
     for (int p = 0; p < M.parts; ++p) {
         Part &q = M.part[p];
         if (!M.here(p)) continue;
-        if ((rc = set_dev(q.device))) return rc;
+        if ((rc = g.set(q.device))) return rc;
         FWX_HIP(hipStreamSynchronize(q.side));
         FWX_HIP(hipStreamSynchronize(q.main));
         if (counting) {
@@ -701,7 +590,7 @@ static int finish_multi_solve(fwx_matrix *m, bool counting, const Opts &op)
             total += u;
         }
     }
-    summarize_timing(M);
+    summarize_timing(g, M);
     if (counting) *op.updates_out = total;
     m->last_u = total;
     return FWX_OK;
@@ -723,12 +612,12 @@ static int finish_multi_solve(fwx_matrix *m, bool counting, const Opts &op)
 // for every peer's w_ready[s] before it overwrites a panel peers may still be copying (PEER exchange).
 // done: the number of blocks applied (a multiple of 2 ... or all of them if the count is odd).
 template <typename T>
-static int multi_double_pass(fwx_matrix *m, const std::vector<Block> &blocks, Throttle &thr, int &done)
+static int multi_double_pass(DeviceGuard &g, fwx_matrix *m, const std::vector<Block> &blocks, Throttle &thr, int &done)
 {
     MultiState &M = *m->multi;
     const int P = M.parts, nd = M.nd;
     constexpr int Bq = FWX_FUSED_BLOCK;
-    const bool with_next = m->next != nullptr;
+    const bool with_next = m->with_next != 0;
     done = 0;
     // full 64-aligned blocks from the start of the range; every partition non-empty and 64-aligned
     int nb = 0;
@@ -768,12 +657,12 @@ static int multi_double_pass(fwx_matrix *m, const std::vector<Block> &blocks, Th
     // snapshot panel of block blk on its owner + exchange, then every partition's column panel, all on
     // the side streams
     auto produce = [&](int blk, int step) -> int {
-        int rc2 = issue_panel<T>(M, blocks[(size_t)blk], blk & 3, step);
+        int rc2 = issue_panel<T>(g, M, blocks[(size_t)blk], blk & 3, step);
         if (rc2) return rc2;
         for (int p = 0; p < P; ++p) {
             Part &q = M.part[p];
             if (!M.here(p)) continue;
-            if ((rc2 = set_dev(q.device))) return rc2;
+            if ((rc2 = g.set(q.device))) return rc2;
             FWX_HIP(hipStreamWaitEvent(q.side, q.w_ready[blk & 3], 0));
             FWX_HIP(fwx::launch_fused_colpanel<T>(args(q, blk, 1), q.side));
         }
@@ -782,7 +671,7 @@ static int multi_double_pass(fwx_matrix *m, const std::vector<Block> &blocks, Th
     auto each = [&](auto &&fn) -> int {
         for (int p = 0; p < P; ++p) {
             if (!M.here(p)) continue;
-            int rc2 = set_dev(M.part[p].device);
+            int rc2 = g.set(M.part[p].device);
             if (rc2 || (rc2 = fn(p, M.part[p]))) return rc2;
         }
         return FWX_OK;
@@ -856,7 +745,7 @@ static int multi_double_pass(fwx_matrix *m, const std::vector<Block> &blocks, Th
                 })))
                 return rc;
         }
-        if ((rc = set_dev(M.part[M.first_here()].device))) return rc;
+        if ((rc = g.set(M.part[M.first_here()].device))) return rc;
         if ((rc = thr.tick(M.part[M.first_here()].main, 10))) return rc;
     }
     if (nb & 1) {                                       // the odd last block: its panels are ready
@@ -877,13 +766,13 @@ static int multi_double_pass(fwx_matrix *m, const std::vector<Block> &blocks, Th
     return FWX_OK;
 }
 
-// resumed: the slabs AND their trace hold a restored checkpoint at time op.k_begin (multi_resolve)
-template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op, bool resumed = false)
+// resumed: the slabs AND their trace hold a restored checkpoint at time op.k_begin (fwx_matrix_resolve)
+template <typename T> static int multi_solve_typed(DeviceGuard &g, fwx_matrix *m, const Opts &op, bool resumed = false)
 {
     MultiState &M = *m->multi;
     const int nd = M.nd, P = M.parts;
     const bool counting = op.updates_out != nullptr;
-    const bool with_next = m->next != nullptr;
+    const bool with_next = m->with_next != 0;
     const bool perk = op.engine == FWX_ENGINE_PERK;
     int rc;
     // domain (fwx.h "Domain"), every slab; the handle remembers the answer for what its arrays hold (the
@@ -897,7 +786,7 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
         for (int p = 0; p < P; ++p) {
             Part &q = M.part[p];
             if (q.rows == 0) continue;
-            if ((rc = set_dev(q.device))) return rc;
+            if ((rc = g.set(q.device))) return rc;
             int b = 3;
             if ((rc = domain_bits<T>((const T *)q.rate, q.next, (size_t)q.rows * nd, q.flag, q.main, b))) return rc;
             bits &= b;
@@ -930,19 +819,19 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
         for (int p = 0; p < P; ++p) {
             Part &q = M.part[p];
             if (!here(p)) continue;
-            const PanelRows pr = store_panels(q.R, slab_of(M, q, sizeof(T)), blk.k0);
+            const PanelRows pr = store_panels(q.store, slab_of(q, nd, sizeof(T)), blk.k0);
             q.wp[slot] = pr.w; q.whp[slot] = pr.wh;
         }
     };
     auto bind_cols = [&](fwx::FusedArgs<T> &a, const Part &q, const Block &blk) {
         if (!rec) return;
-        const PanelRows pr = store_panels(q.R, slab_of(M, q, sizeof(T)), blk.k0);
+        const PanelRows pr = store_panels(q.store, slab_of(q, nd, sizeof(T)), blk.k0);
         a.ct = (T *)pr.ct; a.cnt = pr.cnt; a.cht = pr.cht;
     };
     for (int p = 0; p < P; ++p) {
         Part &q = M.part[p];
         if (!here(p)) continue;
-        if ((rc = set_dev(q.device))) return rc;
+        if ((rc = g.set(q.device))) return rc;
         const size_t cells = (size_t)q.rows * nd;
         if (q.plog.last && !resumed) {
             FWX_HIP(hipMemsetAsync(q.plog.last, 0xFF, cells * 4, q.main));
@@ -974,9 +863,9 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
     size_t first = 0;
     if (!perk && nonneg && !counting && !rec) {
         int done = 0;
-        if ((rc = multi_double_pass<T>(m, blocks, thr, done))) return rc;
+        if ((rc = multi_double_pass<T>(g, m, blocks, thr, done))) return rc;
         first = (size_t)done;
-        if (first == blocks.size()) return finish_multi_solve(m, counting, op);
+        if (first == blocks.size()) return finish_multi_solve(g, m, counting, op);
     }
     // the state of every slab at the START of a checkpoint pivot (a block start), on a recording handle
     auto checkpoint = [&](int k0) -> int {
@@ -984,8 +873,8 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
         for (int p = 0; p < P && c >= 0; ++p) {
             Part &q = M.part[p];
             if (q.rows == 0 || !here(p)) continue;
-            int rc2 = set_dev(q.device);
-            if (rc2 || (rc2 = save_checkpoint(q.R, slab_of(M, q, sizeof(T)), c))) return rc2;
+            int rc2 = g.set(q.device);
+            if (rc2 || (rc2 = save_checkpoint(q.store, slab_of(q, nd, sizeof(T)), c))) return rc2;
         }
         return FWX_OK;
     };
@@ -998,11 +887,11 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
     {   // the first panel: its rows are at time k0 already
         Part &o = M.part[blocks[first].owner];
         if (here(blocks[first].owner)) {
-            if ((rc = set_dev(o.device))) return rc;
+            if ((rc = g.set(o.device))) return rc;
             FWX_HIP(hipEventRecord(o.rows_done, o.main));
         }
         bind_slot(blocks[first], 0);
-        if ((rc = issue_panel<T>(M, blocks[first], 0, (int)first))) return rc;
+        if ((rc = issue_panel<T>(g, M, blocks[first], 0, (int)first))) return rc;
     }
     MultiTimer &tm = M.timer;
     int t_bulk[FWX_MAX_PARTS];
@@ -1019,7 +908,7 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
         for (int p = 0; p < P; ++p) {
             Part &q = M.part[p];
             if (q.rows == 0 || !here(p)) continue;
-            if ((rc = set_dev(q.device))) return rc;
+            if ((rc = g.set(q.device))) return rc;
             FWX_HIP(hipStreamWaitEvent(q.main, q.w_ready[slot], 0));
             t_bulk[p] = tm.begin(MultiTimer::BULK, p, step, q.main);
             if (perk) continue;
@@ -1035,7 +924,7 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
             Part &o = M.part[nb.owner];
             la_owner = nb.owner; la_lo = nb.k0 - o.row0; la_hi = la_lo + nb.bt;
             if (here(nb.owner)) {
-            if ((rc = set_dev(o.device))) return rc;
+            if ((rc = g.set(o.device))) return rc;
             fwx::FusedArgs<T> a = part_args<T>(M, o, nonneg, counting);
             a.k0 = blk.k0; a.bt = blk.bt; a.w = (const T *)o.wp[slot]; a.wh = o.whp[slot];
             bind_cols(a, o, blk);
@@ -1057,12 +946,12 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
             FWX_HIP(hipEventRecord(o.rows_done, o.main));
             }
             bind_slot(nb, slot ^ 1);
-            if ((rc = issue_panel<T>(M, nb, slot ^ 1, step + 1))) return rc;
+            if ((rc = issue_panel<T>(g, M, nb, slot ^ 1, step + 1))) return rc;
         }
         for (int p = 0; p < P; ++p) {
             Part &q = M.part[p];
             if (!here(p)) continue;
-            if ((rc = set_dev(q.device))) return rc;
+            if ((rc = g.set(q.device))) return rc;
             if (perk) continue;                       // the per-k sweeps: below, all partitions at once
             if (q.rows > 0) {
                 fwx::FusedArgs<T> a = part_args<T>(M, q, nonneg, counting);
@@ -1089,7 +978,9 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
                 const bool owner = p == la_owner;
                 auto job = [=, &op]() -> int {
                     Part &q = *qp;
-                    int rc2 = set_dev(q.device);      // the worker's own current device
+                    DeviceGuard wg;                   // the worker's own current device
+                    int rc2 = wg.set(q.device);
+                    wg.keep();
                     if (rc2) return rc2;
                     auto sweep = [&](int lo, int hi, int skip_lo, int skip_hi) -> int {
                         if (hi <= lo) return FWX_OK;
@@ -1112,206 +1003,48 @@ template <typename T> static int multi_solve_typed(fwx_matrix *m, const Opts &op
             for (int p = 0; p < P; ++p) {
                 Part &q = M.part[p];
                 if (!here(p)) continue;
-                if ((rc = set_dev(q.device))) return rc;
+                if ((rc = g.set(q.device))) return rc;
                 if (q.rows > 0) tm.end(t_bulk[p], q.main);
                 FWX_HIP(hipEventRecord(q.main_free[slot], q.main));
             }
         }
-        if ((rc = set_dev(M.part[M.first_here()].device))) return rc;
+        if ((rc = g.set(M.part[M.first_here()].device))) return rc;
         if ((rc = thr.tick(M.part[M.first_here()].main, perk ? blk.bt + 4 : 4))) return rc;
     }
-    if ((rc = finish_multi_solve(m, counting, op))) return rc;
+    if ((rc = finish_multi_solve(g, m, counting, op))) return rc;
     if (rec) rec->valid_upto = rec->state_at = op.k_end;
     return FWX_OK;
 }
 
-// ---- entry points used by fwx_api.hip for handles with m->multi -----------------------------------
-int multi_upload(fwx_matrix *m, const void *rate, const int32_t *next, const int32_t *hops)
-{
-    DevRestore keep;
-    const int rc = multi_copy(m, const_cast<void *>(rate), const_cast<int32_t *>(next),
-                              const_cast<int32_t *>(hops), true);
-    if (rc) return rc;
-    if (m->plog.last) m->rec_ready = 0;
-    if (m->keep) m->kept_valid = 1;
-    m->fresh = 1;
-    m->dom_known = 0;                  // a new input: the domain check has to look at it
-    if (m->resume) {                   // ... and nothing of the old solve can be resumed
-        m->resume->valid_upto = 0;
-        m->resume->state_at = m->keep ? 0 : -1;
-    }
-    return FWX_OK;
-}
-
-int multi_download(fwx_matrix *m, void *rate, int32_t *next, int32_t *hops)
-{
-    DevRestore keep;
-    return multi_copy(m, rate, next, hops, false);
-}
+// ---- what fwx_api.hip calls for a handle with m->multi (fwx_handle.h) --------------------------------
+int multi_parts(const fwx_matrix *m) { return m->multi->parts; }
+int multi_self(const fwx_matrix *m) { return m->multi->self; }
+SlabData &multi_slab(const fwx_matrix *m, int p) { return m->multi->part[p]; }
 
 int multi_solve(fwx_matrix *m, const Opts &op, bool resumed)
 {
-    if (m->plog.last && ((!resumed && op.k_begin != 0) || op.k_end != m->n))
+    if (m->traced && ((!resumed && op.k_begin != 0) || op.k_end != m->n))
         return FWX_ERR_UNSUPPORTED;      // the trace covers whole solves (as on one device)
-    if (op.engine == FWX_ENGINE_PERK && m->plog.last)
+    if (op.engine == FWX_ENGINE_PERK && m->traced)
         return FWX_ERR_UNSUPPORTED;      // the per-k kernel keeps no path trace on slabs: AUTO / FUSED do
-    if (m->plog.last && !m->fresh && !resumed) return FWX_ERR_INVALID;   // a traced solve starts from an upload
-    DevRestore keep;
+    if (m->traced && !m->fresh && !resumed) return FWX_ERR_INVALID;   // a traced solve starts from an upload
+    DeviceGuard g;
     m->fresh = 0;
-    const int rc = m->dtype == FWX_F64 ? multi_solve_typed<double>(m, op, resumed)
-                                       : multi_solve_typed<float>(m, op, resumed);
+    const int rc = m->dtype == FWX_F64 ? multi_solve_typed<double>(g, m, op, resumed)
+                                       : multi_solve_typed<float>(g, m, op, resumed);
     if (rc) {
         if (m->resume) { m->resume->valid_upto = 0; m->resume->state_at = -1; }
         return rc;
     }
-    if (m->plog.last) m->rec_ready = 1;
+    if (m->traced) m->rec_ready = 1;
     return FWX_OK;
 }
 
-// ---- resumable solves on a partitioned handle (fwx_matrix_enable_resume / fwx_matrix_resolve) -------
-SlabCells multi_resume_cells(const fwx_matrix *m)
-{
-    const MultiState &M = *m->multi;
-    SlabCells sum = {0, 0, 0};
-    for (int p = 0; p < M.parts; ++p) {
-        if (!M.here(p)) continue;
-        const SlabCells d = slab_cells(M.part[p].rows, M.nd, M.part[p].ct_ld);
-        sum.cells += d.cells;
-        sum.col_cells += d.col_cells;
-        sum.w_cells += d.w_cells;                            // every partition keeps all pivot rows
-    }
-    return sum;
-}
-
-int multi_enable_resume(fwx_matrix *m, int32_t checkpoints)
-{
-    MultiState &M = *m->multi;
-    DevRestore keep;
-    const size_t es = m->dtype == FWX_F64 ? 8 : 4;
-    fail_point();
-    // a failure (an allocation, or the throw above) leaves nothing behind: the handle stays usable
-    struct Holder {
-        Resume *r = new Resume();
-        MultiState *M;
-        ~Holder()
-        {
-            if (!r) return;
-            for (int p = 0; p < M->parts; ++p)
-                if (M->here(p) && hipSetDevice(M->part[p].device) == hipSuccess) store_free(M->part[p].R);
-            delete r;
-        }
-    } hold;
-    hold.M = &M;
-    Resume *R = hold.r;
-    // only block starts: a block never straddles two partitions, so inside partition p blocks start at row0 + 64 t
-    R->pivot = checkpoint_pivots(m->n, checkpoints, [&](int c) {
-        return (c - M.part[owner_of(M, c)].row0) % FWX_FUSED_BLOCK == 0;
-    });
-    R->count = (int)R->pivot.size();
-    for (int p = 0; p < M.parts; ++p) {
-        Part &q = M.part[p];
-        if (!M.here(p)) continue;
-        int rc = set_dev(q.device);
-        if (rc || (rc = store_alloc(q.R, slab_of(M, q, es), R->count))) return rc;
-    }
-    R->state_at = (m->fresh && m->kept_valid) ? 0 : -1;
-    m->resume = R;
-    hold.r = nullptr;
-    return R->count;
-}
-
-// The patched entries (indices of the caller's n x n view) into the kept input, each on the partition that
-// owns its row (an entry of a row another process holds is skipped); local, if given: per partition, their
-// offsets in its slab.
-static int multi_patch_kept(fwx_matrix *m, int32_t count, const int64_t *index, const void *rate_vals,
-                            const int32_t *next_vals, const int32_t *hops_vals, std::vector<int64_t> *local = nullptr)
-{
-    MultiState &M = *m->multi;
-    const size_t es = m->dtype == FWX_F64 ? 8 : 4;
-    for (int32_t e = 0; e < count; ++e) {
-        const int row = (int)(index[e] / m->n), col = (int)(index[e] % m->n);
-        const int p = owner_of(M, row);
-        Part &q = M.part[p];
-        if (!M.here(p)) continue;
-        int rc = set_dev(q.device);
-        if (rc) return rc;
-        const size_t off = (size_t)(row - q.row0) * M.nd + col;
-        if (local) local[p].push_back((int64_t)off);
-        if ((rc = patch_kept(slab_of(M, q, es), off, e, rate_vals, next_vals, hops_vals))) return rc;
-    }
-    return FWX_OK;
-}
-
-// The resumed path of fwx_matrix_resolve: patch the kept input, restore checkpoint c_idx on every
-// partition, replay the changed entries through pivots [0, c) from the stored panels (each on the
-// partition that owns its row: its column snapshots are local, the pivot rows are the exchanged copies
-// every partition keeps), then run pivots [c, n).
-template <typename T>
-static int multi_resolve_typed(fwx_matrix *m, int32_t count, const int64_t *index, const void *rate_vals,
-                               const int32_t *next_vals, const int32_t *hops_vals, int c_idx)
-{
-    MultiState &M = *m->multi;
-    int rc;
-    std::vector<int64_t> local[FWX_MAX_PARTS];
-    if ((rc = multi_patch_kept(m, count, index, rate_vals, next_vals, hops_vals, local))) return rc;
-    for (int p = 0; p < M.parts; ++p) {
-        Part &q = M.part[p];
-        if (q.rows == 0 || !M.here(p)) continue;
-        if ((rc = set_dev(q.device))) return rc;
-        const Slab v = slab_of(M, q, sizeof(T));
-        if ((rc = restore_checkpoint(q.R, v, c_idx))) return rc;
-        if (local[p].empty()) continue;
-        if ((rc = replay_entries<T>(q.R, v, *m->resume, c_idx, local[p].data(), local[p].size()))) return rc;
-        FWX_HIP(hipStreamSynchronize(q.main));      // (local[p] is read by the replay's copy)
-    }
-    return FWX_OK;
-}
-
-int multi_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const void *rate_vals,
-                  const int32_t *next_vals, const int32_t *hops_vals, int c_idx, Opts op)
-{
-    DevRestore keep;
-    Resume &R = *m->resume;
-    const int c = R.pivot[(size_t)c_idx];
-    R.valid_upto = 0;
-    int rc = m->dtype == FWX_F64
-                 ? multi_resolve_typed<double>(m, count, index, rate_vals, next_vals, hops_vals, c_idx)
-                 : multi_resolve_typed<float>(m, count, index, rate_vals, next_vals, hops_vals, c_idx);
-    if (rc) {
-        R.state_at = -1;
-        m->fresh = 0;
-        m->rec_ready = 0;
-        return rc;
-    }
-    m->fresh = 0;
-    m->rec_ready = 0;
-    R.valid_upto = c;
-    R.state_at = c;
-    op.k_begin = c;
-    return multi_solve(m, op, true);
-}
-
-int multi_enable_path_log(fwx_matrix *m)
-{
-    MultiState &M = *m->multi;
-    DevRestore keep;
-    for (int p = 0; p < M.parts; ++p) {
-        Part &q = M.part[p];
-        if (!M.here(p)) continue;
-        int rc = set_dev(q.device);
-        if (rc) return rc;
-        if ((rc = trace_alloc(q.plog, q.next0, q.next, (size_t)q.rows * M.nd, m->fresh, q.main))) return rc;
-    }
-    m->plog.last = M.part[M.first_here()].plog.last;     // "enabled" marker for the shared handle logic
-    m->rec_ready = 0;
-    return FWX_OK;
-}
-
-static int read_rate(fwx_matrix *m, int src, int dst, double *rate_out)
+static int read_rate(DeviceGuard &g, fwx_matrix *m, int src, int dst, double *rate_out)
 {
     MultiState &M = *m->multi;
     Part &q = M.part[owner_of(M, src)];
-    int rc = set_dev(q.device);
+    int rc = g.set(q.device);
     if (rc) return rc;
     RateRead rate;
     if ((rc = rate.queue(q.rate, (size_t)(src - q.row0) * M.nd + dst, m->dtype, q.main, rate_out))) return rc;
@@ -1331,12 +1064,12 @@ static int query_scratch(MultiState &M, int32_t ints)
 
 // fwx_matrix_query where some pair of devices refused peer access: the same walk driven from the
 // host, one 4-byte read per hop from the partition that owns the row (slow, correct, rarely needed).
-static int host_walk(fwx_matrix *m, int32_t src, int32_t dst, int32_t *path_out, int32_t cap)
+static int host_walk(DeviceGuard &g, fwx_matrix *m, int32_t src, int32_t dst, int32_t *path_out, int32_t cap)
 {
     MultiState &M = *m->multi;
     auto next_of = [&](int a, int32_t *out) -> int {
         Part &q = M.part[owner_of(M, a)];
-        int rc = set_dev(q.device);
+        int rc = g.set(q.device);
         if (rc) return rc;
         FWX_HIP(hipMemcpyAsync(out, q.next + (size_t)(a - q.row0) * M.nd + dst, 4, hipMemcpyDeviceToHost, q.main));
         FWX_HIP(hipStreamSynchronize(q.main));
@@ -1361,13 +1094,13 @@ int multi_query(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out, int32
 {
     MultiState &M = *m->multi;
     if (M.self >= 0) return FWX_ERR_UNSUPPORTED;   // one partition per process: a walk crosses the ranks' slabs
-    DevRestore keep;
+    DeviceGuard g;
     int rc;
-    if (rate_out && (rc = read_rate(m, src, dst, rate_out))) return rc;
-    if (!m->next) return FWX_ERR_INVALID;
-    if (!M.peer_all) return host_walk(m, src, dst, path_out, cap);
+    if (rate_out && (rc = read_rate(g, m, src, dst, rate_out))) return rc;
+    if (!m->with_next) return FWX_ERR_INVALID;
+    if (!M.peer_all) return host_walk(g, m, src, dst, path_out, cap);
     Part &z = M.part[0];
-    if ((rc = set_dev(z.device))) return rc;
+    if ((rc = g.set(z.device))) return rc;
     if ((rc = query_scratch(M, m->n + 2))) return rc;
     return run_follow(make_tab(M), m->n, z.main, M.qscratch, src, dst, path_out, cap);
 }
@@ -1377,9 +1110,9 @@ int multi_query_exact_batch(fwx_matrix *m, int32_t count, const int32_t *src, co
 {
     MultiState &M = *m->multi;
     if (!M.peer_all || M.self >= 0) return FWX_ERR_UNSUPPORTED;   // the walk reads every slab from one device
-    DevRestore keep;
+    DeviceGuard g;
     Part &z = M.part[0];
-    int rc = set_dev(z.device);
+    int rc = g.set(z.device);
     if (rc) return rc;
     return run_exact_batch(make_tab(M), m->n, z.main, count, src, dst, len_out, path_out, cap);
 }
@@ -1390,67 +1123,47 @@ int multi_query_exact(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out,
     int rc;
     if (m->multi->self >= 0) return FWX_ERR_UNSUPPORTED;
     {
-        DevRestore keep;
-        if (rate_out && (rc = read_rate(m, src, dst, rate_out))) return rc;
+        DeviceGuard g;
+        if (rate_out && (rc = read_rate(g, m, src, dst, rate_out))) return rc;
     }
     int32_t len = 0;
     if ((rc = multi_query_exact_batch(m, 1, &src, &dst, &len, path_out, cap))) return rc;
     return len;
 }
 
-int multi_keep_input(fwx_matrix *m)
-{
-    MultiState &M = *m->multi;
-    DevRestore keep;
-    const size_t es = m->dtype == FWX_F64 ? 8 : 4;
-    for (int p = 0; p < M.parts; ++p) {
-        Part &q = M.part[p];
-        if (!M.here(p)) continue;
-        int rc = set_dev(q.device);
-        if (rc) return rc;
-        if ((rc = kept_alloc(q.rate0, q.next0, q.hops0, q.next, q.hops, (size_t)q.rows * M.nd, es))) return rc;
-        if (m->fresh) {
-            if ((rc = keep_live(slab_of(M, q, es)))) return rc;
-            FWX_HIP(hipStreamSynchronize(q.main));
-        }
-    }
-    m->keep = 1;
-    m->kept_valid = m->fresh ? 1 : 0;
-    return FWX_OK;
-}
-
-int multi_patch_input(fwx_matrix *m, int32_t count, const int64_t *index, const void *rate_vals,
-                      const int32_t *next_vals, const int32_t *hops_vals)
-{
-    MultiState &M = *m->multi;
-    DevRestore keep;
-    const size_t es = m->dtype == FWX_F64 ? 8 : 4;
-    int rc;
-    if (m->resume) m->resume->valid_upto = 0;      // the kept input changes without a replay
-    if (m->dom_known && !patch_keeps_domain(m, count, rate_vals, next_vals)) m->dom_known = 0;
-    if ((rc = multi_patch_kept(m, count, index, rate_vals, next_vals, hops_vals))) return rc;
-    for (int p = 0; p < M.parts; ++p) {
-        Part &q = M.part[p];
-        if (!M.here(p)) continue;
-        if ((rc = set_dev(q.device)) || (rc = restore_kept(slab_of(M, q, es)))) return rc;
-    }
-    for (int p = 0; p < M.parts; ++p) {
-        if (!M.here(p)) continue;
-        if ((rc = set_dev(M.part[p].device))) return rc;
-        FWX_HIP(hipStreamSynchronize(M.part[p].main));
-    }
-    m->fresh = 1;
-    m->rec_ready = 0;
-    if (m->resume) m->resume->state_at = 0;        // the patched kept input, unsolved
-    return FWX_OK;
-}
-
+// Everything a partitioned handle owns but the fwx_matrix itself and its Resume bookkeeping.
 void multi_destroy(fwx_matrix *m)
 {
-    multi_free(m->multi);
+    MultiState *M = m->multi;
+    if (!M) return;
+    DeviceGuard g;
+    // order: retire every command that used the partitions' arrays (drain_stream in fwx_internal.h),
+    // give the communicators back, destroy the streams and events, and only then free the memory
+    for (int p = 0; p < M->parts; ++p) {
+        Part &q = M->part[p];
+        if (g.set(q.device)) continue;
+        if (q.main) drain_stream(q.main);
+        if (q.side) drain_stream(q.side);
+    }
+    CommCache::release(M->comms);
+    M->comms = nullptr;
+    for (int p = 0; p < M->parts; ++p) {
+        Part &q = M->part[p];
+        if (g.set(q.device)) continue;
+        if (q.side) (void)hipStreamDestroy(q.side);
+        for (hipEvent_t e : M->timer.pool[p]) (void)hipEventDestroy(e);
+        hipEvent_t evs[] = {q.rows_done, q.main_done, q.panel_done, q.w_ready[0], q.w_ready[1], q.w_ready[2],
+                            q.w_ready[3], q.main_free[0], q.main_free[1], q.main_free[2], q.main_free[3]};
+        for (hipEvent_t e : evs)
+            if (e) (void)hipEventDestroy(e);
+        slab_release(q);
+        void *bufs[] = {q.w[0], q.wh[0], q.ct, q.cnt, q.cht, q.upd, q.flag};
+        for (void *b : bufs)
+            if (b) (void)hipFree(b);
+        if (p == 0 && M->qscratch) (void)hipFree(M->qscratch);
+    }
+    delete M;
     m->multi = nullptr;
-    delete m->resume;          // (the partitions' stores went with the partitions: multi_free)
-    m->resume = nullptr;
 }
 
 }  // namespace fwxi
@@ -1482,11 +1195,10 @@ int fwx_matrix_create_multi(fwx_matrix **out, int32_t n, int32_t dtype, int32_t 
         fwx_matrix *m = new (std::nothrow) fwx_matrix();
         if (!m) return FWX_ERR_OOM;
         memset(m, 0, sizeof(*m));
-        m->n = m->nd = n; m->dtype = dtype; m->device = devices[0];   // (the slabs' pitch is MultiState::nd)
-        m->next = with_next ? (int32_t *)(uintptr_t)16 : nullptr;   // markers only: the slabs own the arrays
-        m->hops = with_hops ? (int32_t *)(uintptr_t)16 : nullptr;
-        DevRestore keep;
-        const int rc = multi_alloc(m, n_parts, devices, exchange);
+        m->n = n; m->dtype = dtype; m->device = devices[0];
+        m->with_next = with_next != 0; m->with_hops = with_hops != 0;
+        DeviceGuard g;
+        const int rc = multi_alloc(g, m, n_parts, devices, exchange);
         if (rc) {
             multi_destroy(m);
             delete m;
@@ -1527,11 +1239,10 @@ int fwx_matrix_create_part(fwx_matrix **out, int32_t n, int32_t dtype, int32_t w
         fwx_matrix *m = new (std::nothrow) fwx_matrix();
         if (!m) return FWX_ERR_OOM;
         memset(m, 0, sizeof(*m));
-        m->n = m->nd = n; m->dtype = dtype; m->device = dev;
-        m->next = with_next ? (int32_t *)(uintptr_t)16 : nullptr;   // markers only: the slab owns the arrays
-        m->hops = with_hops ? (int32_t *)(uintptr_t)16 : nullptr;
-        DevRestore keep;
-        const int rc = multi_alloc(m, world, devices, FWX_XCHG_CALLBACK, rank, exchange, ctx);
+        m->n = n; m->dtype = dtype; m->device = dev;
+        m->with_next = with_next != 0; m->with_hops = with_hops != 0;
+        DeviceGuard g;
+        const int rc = multi_alloc(g, m, world, devices, FWX_XCHG_CALLBACK, rank, exchange, ctx);
         if (rc) {
             multi_destroy(m);
             delete m;
@@ -1570,8 +1281,8 @@ int fwx_matrix_domain_bits(fwx_matrix *m, int32_t *bits_out)
         Part &q = M.part[M.self];
         *bits_out = 3;
         if (q.rows == 0 || m->n == 0) return FWX_OK;
-        DevRestore keep;
-        int rc = set_dev(q.device), b = 3;
+        DeviceGuard g;
+        int rc = g.set(q.device), b = 3;
         if (rc) return rc;
         rc = m->dtype == FWX_F64
                  ? domain_bits<double>((const double *)q.rate, q.next, (size_t)q.rows * M.nd, q.flag, q.main, b)
@@ -1714,9 +1425,9 @@ static int solve_multi_host(int32_t n, int dtype, void *rate, int32_t *next, int
     if (!h.m && (rc = fwx_matrix_create_multi(&h.m, n, dtype, next != nullptr, hops != nullptr, n_parts,
                                               devices, exchange)))
         return rc;
-    rc = multi_upload(h.m, rate, next, hops);
+    rc = fwx_matrix_upload(h.m, rate, next, hops);
     if (!rc) rc = multi_solve(h.m, op);
-    if (!rc) rc = multi_download(h.m, rate, next, hops);
+    if (!rc) rc = fwx_matrix_download(h.m, rate, next, hops);
     if (rc) return rc;
     fail_point();
     fwx_matrix *m = h.m;

@@ -1,7 +1,8 @@
 // fwx_resume.h -- resumable solves (fwx_matrix_enable_resume / fwx_matrix_resolve, SURVEY.md section 8f row
 // f3): what a handle keeps so that a solve of a PATCHED input can start at a stored state instead of at pivot 0,
-// and the host code over it.  One copy for both handle kinds: a single-device handle (fwx_api.hip) is one slab
-// of all rows, a partitioned handle (fwx_multi.hip) is one slab per partition.  Not installed, not part of the ABI.
+// and the host code over it.  One copy for both handle kinds: a single-device handle is one slab of all rows, a
+// partitioned handle (fwx_multi.hip) is one slab per partition; SlabData is what either owns per slab, and
+// fwx_handle.h visits the slabs of a handle.  Not installed, not part of the ABI.
 //   panels      the time-k snapshots the fused engine produces anyway, for ALL pivots instead of ping-pong
 //               buffers: w[k][j] = row k at time k (every slab keeps all of them: a partition receives them
 //               anyway, and the replay of a changed entry (i, j) needs w[k][j] for all k), ct[k][i] = column k at
@@ -101,7 +102,7 @@ struct ResumeStore {
     int64_t *idx = nullptr;                        // FWX_MAX_PATCH entry offsets of a resolve, on the device
 };
 
-// The handle-wide bookkeeping (fwx_matrix::resume).
+// The handle-wide bookkeeping (fwx_matrix::resume); the stores are the slabs' (SlabData::store).
 struct Resume {
     int count = 0;
     std::vector<int> pivot;                        // ascending, each a multiple of 64 in (0, n)
@@ -109,7 +110,6 @@ struct Resume {
                            // belong to the solve of the CURRENT kept input (0: nothing to resume from)
     int state_at = -1;     // the live arrays hold the kept input brought to the start of step state_at
                            // (0 right after an upload / patch; -1: unknown, e.g. solved twice over)
-    ResumeStore store;     // a single-device handle's; the partitions of a partitioned handle hold their own
     int checkpoint_at(int k0) const                // index of the checkpoint at pivot k0, or -1
     {
         for (int c = 0; c < count; ++c)
@@ -118,9 +118,25 @@ struct Resume {
     }
 };
 
-// Rows [row0, row0 + rows) of the nd x nd device matrix as their handle holds them, and the stream its work
-// goes on: a single-device handle is one slab with rows = nd, row0 = 0, ct_ld = (nd + 3) & ~3.  A view filled
-// at the call site; it owns nothing.
+// What a handle owns for rows [row0, row0 + rows) of its nd x nd device matrix, on `device`: a single-device
+// handle has one (row0 = 0, rows = nd, ct_ld = (nd + 3) & ~3), a partitioned handle one per partition (Part,
+// fwx_multi.hip).  A null array is one the handle does not carry.  (fwx_dev_solve fills one with the caller's
+// arrays for the length of the call.)
+struct SlabData {
+    int device = 0, row0 = 0, rows = 0, ct_ld = 0;
+    void *rate = nullptr;
+    int32_t *next = nullptr, *hops = nullptr;
+    fwx::PathLog plog;                             // the path trace (rows x nd each), or null: not enabled
+    int32_t *next0 = nullptr;                      // the uploaded next-hops: the trace's and the kept input's
+    void *rate0 = nullptr;                         // the kept input (fwx_matrix_keep_input): rates ...
+    int32_t *hops0 = nullptr;                      // ... and hops
+    ResumeStore store;                             // checkpoints and all-pivot panels (fwx_matrix_enable_resume)
+    hipStream_t main = nullptr;                    // every operation on the slab runs on it: a non-blocking stream
+                                                   // of the handle's own, never the legacy null stream
+};
+
+// A slab as the functions below take it: the live arrays, the kept input, the geometry.  A view filled at the
+// call site; it owns nothing.
 struct Slab {
     Arrays live;                                   // the arrays a solve works on, with the trace
     Arrays kept;                                   // the kept input (fwx_matrix_keep_input): rate0 / next0 / hops0
@@ -128,6 +144,16 @@ struct Slab {
     size_t es = 0;                                 // bytes per rate element
     hipStream_t s = nullptr;
 };
+inline Slab slab_of(const SlabData &d, int nd, size_t es)
+{
+    Slab v;
+    v.live = {d.rate, d.next, d.hops, d.plog.last, d.plog.at_col, d.plog.at_row};
+    v.kept.rate = d.rate0; v.kept.next = d.next0; v.kept.hops = d.hops0;
+    v.rows = d.rows; v.row0 = d.row0; v.nd = nd; v.ct_ld = d.ct_ld;
+    v.es = es;
+    v.s = d.main;
+    return v;
+}
 
 // Element counts of what a slab's store holds: per checkpoint array, per column-panel array, per row-panel
 // array.  The allocator and fwx_matrix_resume_bytes both go through here.  (An empty partition keeps a
@@ -179,30 +205,29 @@ template <typename P> inline int slab_array(P **p, uint64_t bytes)
     return FWX_OK;
 }
 
-// The path trace of a slab of `cells` entries (fwx_matrix_enable_path_log), into the handle's own members:
-// `last` goes last, a non-null `last` is the "enabled" marker.  next0 = the UPLOADED next-hops: if the arrays
-// hold an unsolved upload (`fresh`), keep it; otherwise a traced solve is refused until the next upload,
-// which fills next0.
-inline int trace_alloc(fwx::PathLog &plog, int32_t *&next0, const int32_t *next, size_t cells, bool fresh, hipStream_t s)
+// The path trace of a slab of `cells` entries (fwx_matrix_enable_path_log).  next0 = the UPLOADED next-hops: if
+// the arrays hold an unsolved upload (`fresh`), keep it; otherwise a traced solve is refused until the next
+// upload, which fills next0.
+inline int trace_alloc(SlabData &d, size_t cells, bool fresh)
 {
     int rc;
-    if ((rc = slab_array(&plog.at_col, cells * 4)) || (rc = slab_array(&plog.at_row, cells * 4)) ||
-        (!next0 && (rc = slab_array(&next0, cells * 4))) || (rc = slab_array(&plog.last, cells * 4)))
+    if ((rc = slab_array(&d.plog.at_col, cells * 4)) || (rc = slab_array(&d.plog.at_row, cells * 4)) ||
+        (!d.next0 && (rc = slab_array(&d.next0, cells * 4))) || (rc = slab_array(&d.plog.last, cells * 4)))
         return rc;
     if (fresh) {
-        FWX_HIP(hipMemcpyAsync(next0, next, cells * 4, hipMemcpyDeviceToDevice, s));
-        FWX_HIP(hipStreamSynchronize(s));
+        FWX_HIP(hipMemcpyAsync(d.next0, d.next, cells * 4, hipMemcpyDeviceToDevice, d.main));
+        FWX_HIP(hipStreamSynchronize(d.main));
     }
     return FWX_OK;
 }
 
-// The kept input of a slab (fwx_matrix_keep_input) for the arrays the handle carries; next0 may be there
-// already, as the trace's.
-inline int kept_alloc(void *&rate0, int32_t *&next0, int32_t *&hops0, bool with_next, bool with_hops, size_t cells, size_t es)
+// The kept input of a slab (fwx_matrix_keep_input) for the arrays it carries; next0 may be there already, as
+// the trace's.
+inline int kept_alloc(SlabData &d, size_t cells, size_t es)
 {
     int rc;
-    if ((rc = slab_array(&rate0, cells * es)) || (with_next && !next0 && (rc = slab_array(&next0, cells * 4))) ||
-        (with_hops && (rc = slab_array(&hops0, cells * 4))))
+    if ((rc = slab_array(&d.rate0, cells * es)) || (d.next && !d.next0 && (rc = slab_array(&d.next0, cells * 4))) ||
+        (d.hops && (rc = slab_array(&d.hops0, cells * 4))))
         return rc;
     return FWX_OK;
 }
@@ -214,6 +239,18 @@ inline void store_free(ResumeStore &st)
     for (const Arrays &a : st.cp) { drop(a.rate); drop(a.next); drop(a.hops); drop(a.last); drop(a.at_col); drop(a.at_row); }
     drop(st.w); drop(st.ct); drop(st.cnt); drop(st.wh); drop(st.cht); drop(st.idx);
     st = ResumeStore();
+}
+
+// Everything a slab owns: its stream, then its arrays and its store.  The slab's device must be current and
+// its streams drained (drain_stream).
+inline void slab_release(SlabData &d)
+{
+    if (d.main) (void)hipStreamDestroy(d.main);
+    void *arrays[] = {d.rate, d.next, d.hops, d.plog.last, d.plog.at_col, d.plog.at_row, d.next0, d.rate0, d.hops0};
+    for (void *a : arrays)
+        if (a) (void)hipFree(a);
+    store_free(d.store);
+    d = SlabData();
 }
 
 // `count` checkpoints of the arrays the slab carries, the all-pivot panels and the index buffer, on the

@@ -275,3 +275,31 @@ def test_the_chunk_pre_check_loop_equals_the_plain_loop(dtype):
     if dtype == np.float64:
         assert_bits_equal(rate, erate, "golden solved 4x4")
     assert np.array_equal(nxt, enext) and np.array_equal(hops, ehops)
+
+
+def test_the_handle_kinds_list_fixture_belongs_to_its_input_and_agrees_with_the_dense_oracle():
+    """tests/golden/handle_kinds_lists_n258_f32.json holds list-faithful `_path` lists of synth's t1 input of order
+    258 in f32 (over a minute of pure Python: tests/golden/make_handle_kinds_lists.py).  Without that minute: every
+    list starts at the dense oracle's next-hop, has the oracle's length, ends at its destination, and -- t1's rates
+    are powers of two, so products are exact -- the product of the INPUT rates along it is the solved rate bit for
+    bit; no list is longer than the one recorded as the longest."""
+    g = load_golden("handle_kinds_lists_n258_f32.json")
+    n = g["n"]
+    assert (g["kind"], n, g["dtype"]) == ("t1", 258, "float32")
+    rate, nxt, hops = synth.make(g["kind"], n, np.float32, seed=g["seed"])
+    er, en, eh = rate.copy(), nxt.copy(), hops.copy()
+    oracle.relax(er, en, eh)
+    assert [g["lists"][0]["src"], g["lists"][0]["dst"]] == g["longest"]
+    assert g["max_len"] == int(eh.max()) == len(g["lists"][0]["path"])
+    assert len(g["lists"]) >= 40
+    for e in g["lists"]:
+        s, d, path = e["src"], e["dst"], e["path"]
+        assert len(path) == eh[s, d] and (en[s, d] == (path[0] if path else -1)), (s, d)
+        if not path:
+            continue
+        assert path[-1] == d
+        prod, cur = np.float32(1.0), s
+        for v in path:
+            prod = np.float32(prod * rate[cur, v])
+            cur = v
+        assert_bits_equal(np.array([prod]), np.array([er[s, d]]), "product along the list of (%d, %d)" % (s, d))
