@@ -53,6 +53,20 @@ template <typename V, bool NT, typename T> __device__ __forceinline__ V load_vec
     return *reinterpret_cast<const V *>(p);
 }
 
+// a < b (strict, ordered: false on NaN) as the wave-wide compare: the lane mask of the one v_cmp_lt the plain
+// `<` compiles to, in scalar registers.  A lane that is not active has a zero bit, so a caller that hands the
+// mask back to the lanes (__builtin_amdgcn_inverse_ballot_w64) or counts its bits must run with every lane of
+// the wave active; relax_kt calls it only from workgroup-uniform control flow.
+constexpr int FWX_FCMP_OLT = 4;               // llvm::CmpInst::FCMP_OLT, the predicate operand of llvm.amdgcn.fcmp
+__device__ __forceinline__ unsigned long long wave_lt(float a, float b)
+{
+    return __builtin_amdgcn_fcmpf(a, b, FWX_FCMP_OLT);
+}
+__device__ __forceinline__ unsigned long long wave_lt(double a, double b)
+{
+    return __builtin_amdgcn_fcmp(a, b, FWX_FCMP_OLT);
+}
+
 // Dispatch position -> tile.  flip 0: in order; 1: reversed; 2: reversed in groups of 8, so that a
 // tile keeps blockIdx.x % 8 and with it its XCD under round-robin dispatch (needs gridDim.x % 8 == 0,
 // the launcher passes 1 otherwise).  Speed only: every mapping is a permutation of the tiles.
@@ -334,6 +348,23 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
 // different from what it loaded.  U counts every improvement of every fold step, which is what NP
 // launches of relax_k count (the +inf component never counts).
 //
+// Round 13.  (1) The tile index is split into (strip, chunk) by a multiply-high with a constant the launcher
+// passes (`strip_magic`) instead of an integer division, which the compiler expands into a float
+// reciprocal in vector registers, a readfirstlane and some twenty dependent scalar instructions in front
+// of the first address of every workgroup: that chain, not the instruction count, is what the sweep
+// gained from.  (2) The COUNTING instantiation alone keeps its masks in scalar
+// registers: its fold compares with the wave-wide compare (wave_lt), U is the sum of the set bits of those
+// masks, one scalar count per wave, and its store rule is evaluated on the wave mask with scalar shifts.
+// That needs every lane of the wave active in relax_vec: its callers are workgroup-uniform (`r`, `r_cnt`,
+// `head` and the instantiation choice depend on the tile only, the row tail included), and the one
+// divergent statement, the store, reconverges before the next row.  The non-counting instantiation (what
+// a whole solve runs) has round 10's fold and store rule: the scalar forms compile to the same fold there
+// and gain nothing measurable (profiles/r13_tune_relax_pivots.txt).
+// The NaN patch of W runs in every strip, although only a strip that meets the pivot columns or the end of
+// the row has a lane that needs it: without the selects the kernel was measured slower (DESIGN.md section
+// 4.1, round 13).  Rows are still addressed with 64-bit vector adds: the compiler re-forms base + lane
+// offset + row stride into a per-lane address chain (profiles/r13_experiments_not_adopted.txt).
+//
 // The prologue issues every load a workgroup starts with back to back -- its pivot-column value, the NP
 // vectors of W and the first UNROLL rows of the stream, all from addresses valid in every lane -- and
 // patches the NaNs in with selects, so the barrier waits for one overlapped group of loads (round 10;
@@ -342,7 +373,7 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
 template <typename T, int W, int RPB, int UNROLL, bool COUNT, int GL, int NP>
 __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct, int ct_ld, int n, int k,
                                                 int nstrips, int flip, unsigned long long *updates,
-                                                int nt_below)
+                                                int nt_below, unsigned strip_magic)
 {
     using L = Lanes<T, W>;
     using V = typename L::V;
@@ -356,8 +387,19 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
 
     const int t = threadIdx.x;
     const int bid = visit_tile(flip);
-    const int strip = bid % nstrips;
-    const int chunk = bid / nstrips;
+    // Tile -> (strip, chunk).  strip_magic = ceil(2^32 / nstrips): the high word of bid * strip_magic is
+    // bid / nstrips exactly while bid * nstrips < 2^32 (the launcher checks the whole grid; it passes 0 for one
+    // strip and for a grid past that bound, and the division below stays for those).  Three scalar
+    // instructions; the division is a float reciprocal in vector registers, a readfirstlane and a score of
+    // dependent scalar instructions, and every address of the prologue's loads waits for it.
+    int strip, chunk;
+    if (strip_magic) {
+        chunk = (int)__umulhi((unsigned)bid, strip_magic);
+        strip = bid - chunk * nstrips;
+    } else {
+        strip = bid % nstrips;
+        chunk = bid / nstrips;
+    }
     const int r_begin = chunk * RPB;
     const int r_cnt = min(RPB, n - r_begin);
     if (COUNT && t == 0) s_cnt = 0;
@@ -376,7 +418,7 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
     };
     T *const base = rate + (size_t)r_begin * n;
     const int g0 = (int)(__lane_id() & ~(GL - 1));   // first lane of my store group
-    unsigned int my_updates = 0;
+    unsigned int wave_updates = 0;            // COUNT: U of my wave, the set bits of every compare mask (scalar)
     V p[NP];                                  // my slice of the NP pivot rows
 
     // One row of one vector through the NP pivots; all lanes of the wave are active (r is uniform).
@@ -399,10 +441,16 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
         for (int tt = 0; tt < NP; ++tt) {
             T cand[W];
             bool up[W];
+            unsigned long long upm[COUNT ? W : 1];   // COUNT: the compare's lane mask, for the scalar count
 #pragma unroll
             for (int c = 0; c < W; ++c) {
                 cand[c] = cik[tt] * L::get(p[tt], c);
-                up[c] = L::get(nx, c) < cand[c];
+                if constexpr (COUNT) {
+                    upm[c] = wave_lt(L::get(nx, c), cand[c]);
+                    up[c] = __builtin_amdgcn_inverse_ballot_w64(upm[c]);
+                } else {
+                    up[c] = L::get(nx, c) < cand[c];
+                }
             }
             // All W compares before the first select: a select that directly follows the compare whose
             // mask it reads costs idle issue slots (the compiler pads the pair with s_nop).
@@ -410,24 +458,54 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
 #pragma unroll
             for (int c = 0; c < W; ++c) {
                 L::set(nx, c, up[c] ? cand[c] : L::get(nx, c));
-                if (COUNT) my_updates += up[c];
+                if constexpr (COUNT) wave_updates += (unsigned)__builtin_popcountll(upm[c]);
             }
         }
         // The fold is monotone under the strict compare: a component improved at some step exactly when
         // its final bits differ from the loaded ones (a NaN or -0.0 that no candidate beats keeps its bits).
-        Bits diff = 0;
+        if constexpr (DIAG) {
 #pragma unroll
-        for (int c = 0; c < W; ++c) {
-            if constexpr (DIAG) L::set(nx, c, c == d ? L::get(x, c) : L::get(nx, c));
-            diff |= __builtin_bit_cast(Bits, L::get(nx, c)) ^ __builtin_bit_cast(Bits, L::get(x, c));
+            for (int c = 0; c < W; ++c) L::set(nx, c, c == d ? L::get(x, c) : L::get(nx, c));
         }
-        const bool changed = diff != 0;
-        bool st = changed;
-        if constexpr (GL > 1) {
-            const unsigned long long m = __ballot(changed);
-            st = own && ((m >> g0) & ((1ull << GL) - 1)) != 0;
+        bool st;
+        if constexpr (GL == 1 || !COUNT) {
+            Bits diff = 0;
+#pragma unroll
+            for (int c = 0; c < W; ++c)
+                diff |= __builtin_bit_cast(Bits, L::get(nx, c)) ^ __builtin_bit_cast(Bits, L::get(x, c));
+            const bool changed = diff != 0;
+            st = changed;
+            if constexpr (GL > 1) {
+                const unsigned long long m = __ballot(changed);
+                st = own && ((m >> g0) & ((1ull << GL) - 1)) != 0;
+            }
+        } else {
+            // COUNT: the group rule ("any lane of my aligned GL-lane group changed") on the wave mask itself, in
+            // scalar registers: the W integer compares each leave a lane mask, their OR is `changed` of the
+            // whole wave; bit l of m becomes the OR of the bits l .. l+GL-1, the first lane of every group keeps
+            // its bit and hands it to the group's other lanes, and the result is the wave's store predicate.
+            constexpr unsigned long long FIRST = GL == 2 ? 0x5555555555555555ull
+                                               : GL == 4 ? 0x1111111111111111ull : 0x0101010101010101ull;
+            unsigned long long m = 0;
+#pragma unroll
+            for (int c = 0; c < W; ++c)
+                m |= __builtin_amdgcn_ballot_w64(__builtin_bit_cast(Bits, L::get(nx, c)) !=
+                                                 __builtin_bit_cast(Bits, L::get(x, c)));
+            m |= m >> 1;
+            if constexpr (GL >= 4) m |= m >> 2;
+            if constexpr (GL >= 8) m |= m >> 4;
+            m &= FIRST;
+            m |= m << 1;
+            if constexpr (GL >= 4) m |= m << 2;
+            if constexpr (GL >= 8) m |= m << 4;
+            st = own && __builtin_amdgcn_inverse_ballot_w64(m);
         }
         if (st) *reinterpret_cast<V *>(at(base, r)) = nx;
+        // COUNT: one running count, added up row by row.  The value is uniform already; the readfirstlane is a fence
+        // for the optimiser only (it costs one scalar move): without it the NP * W popcounts of every row are
+        // reassociated into one sum over the whole tile, every compare mask stays live to the end and is
+        // spilled lane by lane into vector registers (profiles/r13_relax_kt_isa.txt, counting kernels).
+        if constexpr (COUNT) wave_updates = (unsigned)__builtin_amdgcn_readfirstlane((int)wave_updates);
     };
 
     auto stream = [&](auto nt, auto dg) {
@@ -449,7 +527,9 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
         }
         // Pivot columns -> LDS (row k+t of the panel already holds NaN: skip i == k).
         if (t < NP * RPB && t % RPB < r_cnt) s_ct[sr][stt] = cv;
-        // NaN at column k+t: skip j == k; NaN everywhere in a clamped lane.
+        // NaN at column k+t: skip j == k; NaN everywhere in a clamped lane.  In every strip, also where no
+        // lane can need it (a strip that meets neither the pivot columns nor the end of the row): leaving the
+        // selects out of those strips was measured slower (round 13).
 #pragma unroll
         for (int tt = 0; tt < NP; ++tt)
 #pragma unroll
@@ -484,7 +564,7 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
     }
 
     if (COUNT) {
-        if (my_updates) atomicAdd(&s_cnt, my_updates);
+        if (__lane_id() == 0 && wave_updates) atomicAdd(&s_cnt, wave_updates);
         __syncthreads();
         if (t == 0 && s_cnt)
             atomicAdd(&updates[bid & (FWX_UPDATE_SHARDS_K - 1)], (unsigned long long)s_cnt);
@@ -936,6 +1016,11 @@ static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
         return hipErrorInvalidValue;
     const int nstrips = (a.n + SW - 1) / SW;
     const int nchunks = (a.n + RPB - 1) / RPB;
+    // ceil(2^32 / nstrips) for the kernel's tile -> (strip, chunk); 0 (the kernel divides) for one strip and
+    // for a grid on which the multiply-high is not proven exact
+    unsigned strip_magic = 0;
+    if (nstrips >= 2 && (unsigned long long)nstrips * nchunks * nstrips < (1ull << 32))
+        strip_magic = (unsigned)(0xffffffffull / (unsigned)nstrips) + 1u;
     const dim3 grid((unsigned)(nstrips * nchunks)), block(256);
     const int flip = a.flip == 2 && grid.x % 8 ? 1 : a.flip;
     int nt_below = 0;
@@ -948,7 +1033,7 @@ static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
     const int gl = sb >= 128 ? 8 : sb >= 64 ? 4 : sb >= 32 ? 2 : 1;
 #define FWX_LAUNCH_KT(CN, GL, NP)                                                                  \
     hipLaunchKernelGGL((relax_kt<T, W, RPB, UNROLL, CN, GL, NP>), grid, block, 0, s, a.rate, a.w, a.ct, \
-                       a.ct_ld, a.n, a.k, nstrips, flip, a.updates, nt_below)
+                       a.ct_ld, a.n, a.k, nstrips, flip, a.updates, nt_below, strip_magic)
 #define FWX_LAUNCH_KT_NP(CN, GL)                                                                   \
     do {                                                                                           \
         if (a.np == 8) FWX_LAUNCH_KT(CN, GL, 8);                                                   \
