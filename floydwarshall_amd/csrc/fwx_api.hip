@@ -1024,6 +1024,8 @@ int fwx_test_perk_pivots(uint64_t *launches, int reset)
     return perk_pivots();
 }
 
+int fwx_test_perk_fold(void) { return perk_fold_compare() ? 1 : 0; }
+
 const char *fwx_test_kernel_form_name(int form)
 {
     static const char *const names[] = {

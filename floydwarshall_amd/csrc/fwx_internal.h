@@ -11,6 +11,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "fwx.h"
 #include "fwx_kernels.h"
@@ -481,6 +482,16 @@ inline int perk_pivots()
     return FWX_PERK_PIVOTS_DEFAULT;
 }
 
+// The fold of relax_kt's non-counting f32 sweeps: FWX_PERK_FOLD=compare forces the compare form in every tile, read on
+// every call; anything else, or unset: automatic (each wave takes the max form where the operands it has loaded
+// are all NaN or sign-clear).  For tests and A/B runs in one binary.  No result bit depends on it (DESIGN.md
+// section 4.1, round 14).
+inline bool perk_fold_compare()
+{
+    const char *e = getenv("FWX_PERK_FOLD");
+    return e && !strcmp(e, "compare");
+}
+
 // Tier choice of the batched small solves (fwx_solve_batch_*, fwx_dev_solve_batch): matrices of order n <=
 // FWX_BATCH_WAVE_MAX_N take the wave tier (one wave per matrix, registers only), larger ones the workgroup
 // tier (small_solve's body, one workgroup per matrix).  An integer 0 ... FWX_BATCH_WAVE_N, read on every
@@ -587,6 +598,7 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
     a.rate = rate; a.ct_ld = (int)ld; a.n = n; a.updates = d_updates;
     a.temporal_bytes = perk_temporal_bytes((size_t)n * n * sizeof(T));
     a.store_bytes = perk_store_bytes();
+    a.fold_compare = perk_fold_compare();
     fwx::RelaxArgs<T> a1;
     a1.rate = rate; a1.next = nullptr; a1.hops = nullptr; a1.phops = nullptr; a1.rows = n; a1.n = n; a1.row0 = 0;
     a1.updates = d_updates; a1.temporal_bytes = a.temporal_bytes; a1.store_bytes = a.store_bytes;

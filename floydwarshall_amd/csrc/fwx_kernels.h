@@ -110,7 +110,8 @@ template <typename T> struct RelaxArgs {
 template <typename T> hipError_t launch_relax(const RelaxArgs<T> &a, hipStream_t s);
 
 // relax_kt: pivots [k, k+np) on the whole n x n matrix in one streaming pass, rates only, operands from
-// the snapshot panels of launch_fused_panels (compare form).  n must be a multiple of 16 bytes of
+// the snapshot panels of launch_fused_panels (compare form; the sweep's own fold is chosen per wave, see
+// fold_compare).  n must be a multiple of 16 bytes of
 // elements, rate and w 16-byte aligned.
 #define FWX_PERK_KT_RPB 8          // rows per workgroup and loads in flight per thread: 8 x 8 is 8-10 % faster per
 #define FWX_PERK_KT_UNROLL 8       //   pivot than relax_k's 4 x 4 at NP = 8 (profiles/r07_tune_relax_pivots.txt)
@@ -122,6 +123,8 @@ template <typename T> struct RelaxKtArgs {
     int flip;                      // as RelaxArgs
     long long temporal_bytes = -1;
     int store_bytes = 0;
+    bool fold_compare = false;     // true: the compare form of the fold in every tile (FWX_PERK_FOLD=compare); false: each
+                                   // wave takes the max form where its operands allow it.  No result bit depends on it
     unsigned long long *updates = nullptr;   // FWX_UPDATE_SHARDS_K counters or nullptr
 };
 template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s);

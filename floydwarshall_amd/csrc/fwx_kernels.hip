@@ -339,8 +339,10 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
 // are one or two 16-byte reads; contiguous reads of the panel: no strided gather).  Each loaded vector
 // is folded through t = 0 .. NP-1 in ascending order with
 //   x = x < c ? c : x,   c = ct[t][i] * w[t][j]
-// -- one IEEE multiply, the strict ordered compare, never `max`: no domain assumption enters the per-k
-// engine.  The fold step is three vector instructions and nothing else (round 10): the diagonal (j == i
+// -- one IEEE multiply, the strict ordered compare -- or, bit for bit the same, through the maximum of the NP
+// candidates and ONE compare, exactly where the operands allow it (round 14, below).  No domain assumption enters
+// the per-k engine: the condition is read off the operands a wave has loaded, and x may be anything.  The compare
+// form's fold step is three vector instructions and nothing else (round 10): the diagonal (j == i
 // never updates) is protected outside the per-pivot loop, by folding that one component from +inf and
 // giving it its loaded bits back, and only in the tiles whose rows meet their columns (DIAG, a
 // workgroup-uniform choice like the cache-policy one); whether a vector changed is read off afterwards,
@@ -365,22 +367,67 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
 // 4.1, round 13).  Rows are still addressed with 64-bit vector adds: the compiler re-forms base + lane
 // offset + row stride into a per-lane address chain (profiles/r13_experiments_not_adopted.txt).
 //
+// Round 14: the max form.  If every candidate of an entry is NaN or has its sign bit clear -- true whenever every
+// w[t][j] and ct[t][i] it is built from is -- then with m = maxNum(c_0 .. c_NP-1), `x < m ? m : x` is the sequential
+// fold bit for bit for every x.  The non-counting f32 instantiations (MAXF) carry both forms; a
+// WAVE takes the max form iff no value of W in its lanes after the NaN patch and no staged Ct value of the tile has its
+// sign bit set (one OR chain and a ballot behind the prologue's loads; FWX_PERK_FOLD=compare, the kernel argument
+// `fold_compare`, forces the compare form).  Per row-vector: NP * W multiplies, a v_max3_f32 per two candidates, W
+// compares, which are `changed` as well; 63 vector instructions per row for 107.  The counting instantiation keeps the
+// compare form (U counts every improving step), f64 too (no max form is written for it), and so does a ragged last row
+// chunk (the max form has no row-by-row tail).  These kernels of the production geometry ask for four waves per SIMD
+// in their launch bound where a store group is at most four lanes (relax_kt_min_waves, below).
+//
 // The prologue issues every load a workgroup starts with back to back -- its pivot-column value, the NP
 // vectors of W and the first UNROLL rows of the stream, all from addresses valid in every lane -- and
 // patches the NaNs in with selects, so the barrier waits for one overlapped group of loads (round 10;
 // before, NP exec-masked loads each waited for alone, and the stream started after the barrier).
 // -------------------------------------------------------------------------------------------------
+// Which element types have a max form of relax_kt's fold: f32.  f64 has the compare form alone; a max form for it
+// is not written.
+template <typename T> constexpr bool relax_kt_max_form() { return sizeof(T) == 4; }
+
+// max(c[0], ..., c[N-1]) as IEEE maxNum (a NaN operand is ignored; NaN if all are): two operands per
+// v_max3_f32, a lone last one by v_max_f32.  By inline asm, like fmax_t in fwx_fused.hip, for another reason: a
+// chain of __builtin_fmaxf is a horizontal reduction to the SLP vectoriser, which then forms the NP products as
+// one vector, multiplies with v_pk_mul_f32 on register pairs and pads every pair with s_nop (576 v_pk_mul_f32
+// and 1281 s_nop in the NP = 8 kernel, profiles/r14_relax_kt_isa.txt).  The operands are products, quiet
+// already, so nothing needs quieting.  VALU results feeding a VALU need no wait states.
+template <int N> __device__ __forceinline__ float max_of(const float (&c)[N])
+{
+    float m = c[0];
+    int i = 1;
+#pragma unroll
+    for (; i + 1 < N; i += 2) asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(c[i]), "v"(c[i + 1]));
+    if (i < N) asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(m), "v"(c[i]));
+    return m;
+}
+
+// Waves per SIMD the launch bound asks for.  With both forms of the fold inside, the production geometry takes 133
+// VGPRs under the plain bound, for a peak in the rarely run tail loop; asked for four waves it stays at 128 without a
+// spill.  Not where a group is 8 lanes (FWX_PERK_STORE_BYTES=128): that kernel spills 8 bytes under the bound and
+// takes 133 VGPRs without it.  Not in the other geometries (tools/tune_relax.hip), which are timed as the compiler
+// makes them (profiles/r14_relax_kt_isa.txt).
+template <typename T, int RPB, int UNROLL, bool COUNT, int GL> constexpr int relax_kt_min_waves()
+{
+    return !COUNT && relax_kt_max_form<T>() && RPB == FWX_PERK_KT_RPB && UNROLL == FWX_PERK_KT_UNROLL && GL < 8 ? 4 : 1;
+}
+
 template <typename T, int W, int RPB, int UNROLL, bool COUNT, int GL, int NP>
-__global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct, int ct_ld, int n, int k,
+__global__ __launch_bounds__(256, (relax_kt_min_waves<T, RPB, UNROLL, COUNT, GL>()))
+void relax_kt(T *rate, const T *w, const T *ct, int ct_ld, int n, int k,
                                                 int nstrips, int flip, unsigned long long *updates,
-                                                int nt_below, unsigned strip_magic)
+                                                int nt_below, unsigned strip_magic, int fold_compare)
 {
     using L = Lanes<T, W>;
     using V = typename L::V;
     using Bits = std::conditional_t<sizeof(T) == 4, uint32_t, uint64_t>;
     constexpr int SW = 256 * W;
+    // The instantiations that carry the max form of the fold beside the compare form (header, round 14).
+    constexpr bool MAXF = !COUNT && relax_kt_max_form<T>();
     static_assert(GL == 1 || GL == 2 || GL == 4 || GL == 8, "store group: 1, 2, 4 or 8 lanes");
     static_assert(NP * RPB <= 256, "one thread per staged pivot-column value");
+    static_assert(64 % (NP * RPB) == 0 || NP * RPB % 64 == 0, "the fold vote: staged values per wave");
 
     __shared__ __attribute__((aligned(16))) T s_ct[RPB][NP];
     __shared__ unsigned int s_cnt;
@@ -421,7 +468,57 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
     unsigned int wave_updates = 0;            // COUNT: U of my wave, the set bits of every compare mask (scalar)
     V p[NP];                                  // my slice of the NP pivot rows
 
-    // One row of one vector through the NP pivots; all lanes of the wave are active (r is uniform).
+    // The store rule on my own `changed`: a group of GL aligned lanes stores if any of its lanes changed, clamped
+    // lanes never.  All lanes of the wave are active.
+    auto group_stores = [&](bool changed) {
+        if constexpr (GL == 1) return changed;
+        const unsigned long long m = __ballot(changed);
+        return own && ((m >> g0) & ((1ull << GL) - 1)) != 0;
+    };
+
+    // One row of one vector through the NP pivots, MAX FORM: only where every operand of the wave -- its lanes'
+    // slices of W after the NaN patch, the tile's staged Ct -- is NaN or has its sign bit clear (`max_form`
+    // below).  Then no candidate is -0 or negative, candidates that compare equal have equal bits, and with m
+    // the maxNum of the NP candidates `x < m ? m : x` is the sequential fold bit for bit for EVERY loaded x:
+    // where nothing beats x both keep the loaded bits (x NaN with any payload, x = -0 against m = +0), otherwise
+    // both end at the bits of the numeric maximum.  m needs no x, so the row's load is
+    // waited for in front of the W compares and not in front of the multiplies; the compare is `changed` as well.
+    // DIAG: the component on the diagonal is masked out of the compare, so it keeps its bits and never counts.
+    auto relax_vec_max = [&](const V &x, int r, auto dg) {
+      if constexpr (MAXF) {
+        constexpr bool DIAG = decltype(dg)::value;
+        const int d = r_begin + r - col;
+        T cik[NP];
+#pragma unroll
+        for (int tt = 0; tt < NP; ++tt) cik[tt] = s_ct[r][tt];
+        T m[W];
+        bool up[W];
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            T cand[NP];
+#pragma unroll
+            for (int tt = 0; tt < NP; ++tt) cand[tt] = cik[tt] * L::get(p[tt], c);
+            m[c] = max_of(cand);
+        }
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            up[c] = L::get(x, c) < m[c];
+            if constexpr (DIAG) up[c] = up[c] && c != d;
+        }
+        // All W compares before the first select, as in the compare form.
+        __builtin_amdgcn_sched_barrier(0);
+        V nx;
+        bool changed = false;
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            L::set(nx, c, up[c] ? m[c] : L::get(x, c));
+            changed = changed || up[c];
+        }
+        if (group_stores(changed)) *reinterpret_cast<V *>(at(base, r)) = nx;
+      }
+    };
+
+    // One row of one vector through the NP pivots, COMPARE FORM; all lanes of the wave are active (r is uniform).
     // DIAG: the tile may hold diagonal elements (j == i never updates).  Such a component folds from +inf,
     // which no candidate beats (`+inf < c` is false for every c, NaN included), and gets its loaded bits
     // back afterwards; the fold step itself carries no diagonal term.
@@ -473,12 +570,7 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
 #pragma unroll
             for (int c = 0; c < W; ++c)
                 diff |= __builtin_bit_cast(Bits, L::get(nx, c)) ^ __builtin_bit_cast(Bits, L::get(x, c));
-            const bool changed = diff != 0;
-            st = changed;
-            if constexpr (GL > 1) {
-                const unsigned long long m = __ballot(changed);
-                st = own && ((m >> g0) & ((1ull << GL) - 1)) != 0;
-            }
+            st = group_stores(diff != 0);
         } else {
             // COUNT: the group rule ("any lane of my aligned GL-lane group changed") on the wave mask itself, in
             // scalar registers: the W integer compares each leave a lane mask, their OR is `changed` of the
@@ -526,7 +618,10 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
             for (int u = 0; u < UNROLL; ++u) x0[u] = load_vec<V, NT>(at(base, u));
         }
         // Pivot columns -> LDS (row k+t of the panel already holds NaN: skip i == k).
-        if (t < NP * RPB && t % RPB < r_cnt) s_ct[sr][stt] = cv;
+        // Rows of a ragged chunk past the end of the matrix get the last row's values again (cv is loaded from the
+        // clamped row): no fold reads them, each cell has one writer, and the store needs no row compare.  With the
+        // compare the default kernel spills 4 bytes in its tail loop (profiles/r14_relax_kt_isa.txt).
+        if (t < NP * RPB) s_ct[t % RPB][stt] = cv;
         // NaN at column k+t: skip j == k; NaN everywhere in a clamped lane.  In every strip, also where no
         // lane can need it (a strip that meets neither the pivot columns nor the end of the row): leaving the
         // selects out of those strips was measured slower (round 13).
@@ -535,22 +630,61 @@ __global__ __launch_bounds__(256) void relax_kt(T *rate, const T *w, const T *ct
 #pragma unroll
             for (int c = 0; c < W; ++c)
                 L::set(p[tt], c, !own || col + c == k + tt ? quiet_nan<T>() : L::get(p[tt], c));
+        // The fold's form, per wave, from what the wave has loaded: the max form iff no operand of its rows has
+        // its sign bit set (a negative NaN included: conservative and exact).  After the patch column k + t and
+        // clamped lanes hold the positive quiet NaN, so a hostile r[k][k] disqualifies nobody.  The RPB x NP staged
+        // Ct values lie across the wave's lanes already, in `cv` (t -> (stt, sr) has the period RPB * NP, which divides
+        // 64, and sr is clamped to the tile's rows); a larger tile reads the staged rows back from LDS behind the
+        // barrier.  A ragged chunk keeps the compare form.
         __syncthreads();
-        if (head) {
+        bool max_form = false;
+        if constexpr (MAXF) {
+            // The OR is written as the instruction itself and takes the values as floats: any integer use of p[]
+            // or of the loaded vectors makes the optimiser pair the multiplies of the compare form's diagonal copies
+            // into v_pk_mul_f32, every pair padded with s_nop (profiles/r14_relax_kt_isa.txt).
+            static_assert(!MAXF || (sizeof(T) == 4 && W == 4), "the vote is written for four 32-bit components");
+            T signs = cv;
 #pragma unroll
-            for (int u = 0; u < UNROLL; ++u) relax_vec(x0[u], u, dg);
-            r = UNROLL;
-        }
-        if constexpr (RPB > UNROLL) {
-            for (; r + UNROLL <= r_cnt; r += UNROLL) {
-                V x[UNROLL];
+            for (int tt = 0; tt < NP; ++tt)
+                asm("v_or3_b32 %0, %0, %1, %2\n\tv_or3_b32 %0, %0, %3, %4"
+                    : "+v"(signs)
+                    : "v"(L::get(p[tt], 0)), "v"(L::get(p[tt], 1)), "v"(L::get(p[tt], 2)), "v"(L::get(p[tt], 3)));
+            if constexpr (RPB * NP > 64) {
 #pragma unroll
-                for (int u = 0; u < UNROLL; ++u) x[u] = load_vec<V, NT>(at(base, r + u));
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u) relax_vec(x[u], r + u, dg);
+                for (int i = 0; i < RPB * NP; i += 64) {
+                    const T v = (&s_ct[0][0])[i + (int)__lane_id()];     // rows past r_cnt repeat the last row
+                    asm("v_or_b32 %0, %1, %2" : "=v"(signs) : "v"(signs), "v"(v));
+                }
             }
+            const bool any = __builtin_amdgcn_ballot_w64(__builtin_signbit(signs)) != 0;
+            max_form = !fold_compare && !any && r_cnt % UNROLL == 0;
         }
-        for (; r < r_cnt; ++r) relax_vec(load_vec<V, NT>(at(base, r)), r, dg);
+        auto rows = [&](auto vec, auto tl) {
+            if (head) {
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) vec(x0[u], u, dg);
+                r = UNROLL;
+            }
+            if constexpr (RPB > UNROLL) {
+                for (; r + UNROLL <= r_cnt; r += UNROLL) {
+                    V x[UNROLL];
+#pragma unroll
+                    for (int u = 0; u < UNROLL; ++u) x[u] = load_vec<V, NT>(at(base, r + u));
+#pragma unroll
+                    for (int u = 0; u < UNROLL; ++u) vec(x[u], r + u, dg);
+                }
+            }
+            // The row-by-row tail (a ragged last chunk), in the compare form only; rare, and kept rolled: unrolled it
+            // sets the kernel's register peak (profiles/r14_relax_kt_isa.txt).
+            if constexpr (decltype(tl)::value)
+#pragma unroll 1
+                for (; __builtin_expect(r < r_cnt, 0); ++r) vec(load_vec<V, NT>(at(base, r)), r, dg);
+        };
+        // wave-uniform: one of the two, never both
+        if constexpr (MAXF) {
+            if (max_form) { rows(relax_vec_max, std::false_type()); return; }
+        }
+        rows(relax_vec, std::true_type());
     };
     // workgroup-uniform: one of the four instantiations, never two.  Only a tile whose rows meet its
     // columns holds diagonal elements (one strip in sixteen at N = 16384).
@@ -1033,7 +1167,7 @@ static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
     const int gl = sb >= 128 ? 8 : sb >= 64 ? 4 : sb >= 32 ? 2 : 1;
 #define FWX_LAUNCH_KT(CN, GL, NP)                                                                  \
     hipLaunchKernelGGL((relax_kt<T, W, RPB, UNROLL, CN, GL, NP>), grid, block, 0, s, a.rate, a.w, a.ct, \
-                       a.ct_ld, a.n, a.k, nstrips, flip, a.updates, nt_below, strip_magic)
+                       a.ct_ld, a.n, a.k, nstrips, flip, a.updates, nt_below, strip_magic, a.fold_compare ? 1 : 0)
 #define FWX_LAUNCH_KT_NP(CN, GL)                                                                   \
     do {                                                                                           \
         if (a.np == 8) FWX_LAUNCH_KT(CN, GL, 8);                                                   \

@@ -134,6 +134,9 @@ const char *fwx_test_kernel_form_name(int form);
  * launches that schedule has made in this process -- single-pivot, 2-, 4- and 8-pivot sweeps, panel
  * launches -- which are cleared if reset.  Needs no device.  Not for production use.                  */
 int fwx_test_perk_pivots(uint64_t *launches, int reset);
+/* TEST HOOK: what FWX_PERK_FOLD parses to right now: 1 = compare (the value `compare`, exactly), 0 = automatic
+ * (anything else, or unset).  Needs no device.  Not for production use.                              */
+int fwx_test_perk_fold(void);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).
@@ -441,7 +444,11 @@ typedef struct fwx_pivots {
  * 8; 1 = one launch per pivot): per block of 64 pivots one panel launch takes the time-k snapshots of
  * the block's rows and columns, then every launch folds 2, 4 or 8 neighbouring pivots from those
  * snapshots into each entry it streams, so the matrix is read once per launch, not once per pivot.
- * The result is bit for bit the same.  The snapshots live in library-owned device scratch on the stream's
+ * The result is bit for bit the same.  FWX_PERK_FOLD (environment, read per call): `compare` makes every
+ * such f32 launch fold with a compare and a select per pivot, as every counting and every f64 launch does;
+ * anything else, or unset, is automatic -- a wave whose loaded pivot operands are all NaN or sign-clear takes
+ * the maximum of its candidates first and compares once, which gives the same bits for every entry.  For
+ * tests and A/B runs; no result bit depends on it.  The snapshots live in library-owned device scratch on the stream's
  * device, one buffer of 128 * n elements per stream (at most 16 are kept, the least recently used goes):
  * the FIRST such call on a stream calls hipMalloc, and a call with a larger n than the stream has seen
  * waits for the stream before it frees and allocates again -- so such a call cannot be captured into a

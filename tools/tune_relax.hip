@@ -198,14 +198,15 @@ static int stores_sweep(float *d, int n, int per, int rounds)
 }
 
 // `pivots` mode: the multi-pivot schedule of the per-k engine (relax_range_kt in fwx_internal.h).  For NP = 1
-// (relax_k, one launch per pivot) and NP = 2, 4, 8 (relax_kt, geometries RPB x UNROLL) a window of `per`
+// (relax_k, one launch per pivot) and NP = 2, 4, 8 (relax_kt, geometries RPB x UNROLL; `cmp`: the production
+// geometry with the compare form of the fold forced in every tile, RelaxKtArgs::fold_compare) a window of `per`
 // pivots -- from k = 0, 4096 and 12000, each started from a copy of the matrix state at its first pivot -- is
 // issued as production issues it: per 64 pivots one fused_panels launch, then 64 / NP sweeps, serpentine in
 // groups of 8, the default temporal tail.  Reported per window: us per pivot over the whole window (panel
 // launches included) and us per sweep launch (the window minus its panel launches, which are timed on
 // their own, back to back on an otherwise idle chip, and reported separately).
 //   tune_relax 16384 0 256 3 pivots
-struct KtCfg { const char *name; int np; hipError_t (*fn)(const fwx::RelaxKtArgs<float> &, hipStream_t); };
+struct KtCfg { const char *name; int np; hipError_t (*fn)(const fwx::RelaxKtArgs<float> &, hipStream_t); bool cmp = false; };
 template <int RPB, int UNROLL>
 static hipError_t run_kt(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
 {
@@ -219,6 +220,7 @@ static int pivots_sweep(float *d, int n, int per, int rounds)
         vars.push_back({"RPB4 U4", np, run_kt<4, 4>});
         vars.push_back({"RPB8 U4", np, run_kt<8, 4>});
         vars.push_back({"RPB8 U8", np, run_kt<8, 8>});
+        vars.push_back({"RPB8 U8 cmp", np, run_kt<8, 8>, true});   // the compare form forced in every tile
         vars.push_back({"RPB16 U8", np, run_kt<16, 8>});
     }
     const int k0s[3] = {0, 4096, 12000}, nw = 3, nv = (int)vars.size();
@@ -258,6 +260,7 @@ static int pivots_sweep(float *d, int n, int per, int rounds)
             for (int t = 0; t < bt; t += v.np, ++launches) {
                 a.k = k0 + t; a.np = v.np; a.w = w + (size_t)t * n; a.ct = ct + (size_t)t * n;
                 a.flip = 2 * (sweeps++ & 1);
+                a.fold_compare = v.cmp;
                 CK(v.fn(a, 0));
             }
         }
@@ -266,7 +269,7 @@ static int pivots_sweep(float *d, int n, int per, int rounds)
     // window states: the NP = 8 path from the pristine matrix (bit for bit the per-k states)
     CK(hipMemcpy(work, d, bytes, hipMemcpyDeviceToDevice));
     for (int i = 0, k = 0; i < nw; ++i) {
-        if (k0s[i] > k) run(vars[nv - 4], k, std::min(n, k0s[i]));
+        if (k0s[i] > k) run(vars[nv - 3], k, std::min(n, k0s[i]));
         k = std::min(n, k0s[i]);
         CK(hipMemcpy(snap[i], work, bytes, hipMemcpyDeviceToDevice));
     }
