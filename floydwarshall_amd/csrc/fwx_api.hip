@@ -699,10 +699,21 @@ __global__ void follow_path_kernel(EntryTab t, int n_real, int src, int dst, int
 // ([b] if next0[a][b] >= 0, else []).  T is the end of the solve for the query itself (`last`), and
 // for every sub-entry it is the step named by one of its own indices: (a,q) at time q is read from
 // at_col, (q,b) at time q from at_row.  Iterative, one thread: the list goes to out (cap entries), the
-// stack holds (a, b, kind) triples (3 * cap entries).  The length, or FWX_ERR_CAPACITY if it does not fit.
-__device__ int exact_walk(const EntryTab &t, int src, int dst, int32_t *out, int32_t *stack, int cap)
+// stack holds (a, b, kind) triples.  The length, or FWX_ERR_CAPACITY if the LIST is longer than cap.
+//
+// The stack is sized by the order, not by cap (exact_stack_triples).  Along any descent the pivots strictly
+// decrease -- at_col[a][q] and at_row[q][b] are pivots applied before step q -- so an item at depth d has d + 1
+// distinct pivots above it, d <= n - 1, and with one pending sibling per level the stack never holds more than
+// n + 1 triples.  cap cannot bound it: on the reference's domain every pending item yields at least one list
+// entry, outside it (a leaf with next0 < 0, an update whose ikPath was empty) a pending item can yield nothing,
+// and a list of length L can need more than L triples.  The depth test below cannot fire on a trace a solve
+// wrote; it keeps a corrupted one inside the scratch.
+__host__ __device__ inline size_t exact_stack_triples(int n_real) { return (size_t)n_real + 2; }
+
+__device__ int exact_walk(const EntryTab &t, int n_real, int src, int dst, int32_t *out, int32_t *stack, int cap)
 {
     enum { FINAL = 0, AS_COLUMN = 1, AS_ROW = 2 };
+    const int scap = (int)exact_stack_triples(n_real);
     int sp = 0, len = 0;
     stack[0] = src; stack[1] = dst; stack[2] = FINAL; sp = 1;
     while (sp > 0) {
@@ -717,7 +728,7 @@ __device__ int exact_walk(const EntryTab &t, int src, int dst, int32_t *out, int
                 out[len++] = b;
             }
         } else {
-            if (sp + 2 > cap) return FWX_ERR_CAPACITY;
+            if (sp + 2 > scap || q >= n_real) return FWX_ERR_CYCLE;
             stack[3 * sp] = q; stack[3 * sp + 1] = b; stack[3 * sp + 2] = AS_ROW; ++sp;      // second half
             stack[3 * sp] = a; stack[3 * sp + 1] = q; stack[3 * sp + 2] = AS_COLUMN; ++sp;   // first half
         }
@@ -726,7 +737,7 @@ __device__ int exact_walk(const EntryTab &t, int src, int dst, int32_t *out, int
 }
 
 // Batch form: one thread per (src[q], dst[q]); query q writes its list to paths + q*cap and uses
-// stacks + q*3*cap as its stack.  len_out[q] = length, or the error of that item.
+// stacks + q * 3 * exact_stack_triples(n_real) as its stack.  len_out[q] = length, or the error of that item.
 __global__ __launch_bounds__(64) void exact_paths_kernel(EntryTab t, int n_real, int count, const int32_t *src,
                                                          const int32_t *dst, int32_t *paths, int32_t *stacks,
                                                          int cap, int32_t *len_out)
@@ -735,14 +746,15 @@ __global__ __launch_bounds__(64) void exact_paths_kernel(EntryTab t, int n_real,
     if (qi >= count) return;
     const int s0 = src[qi], d0 = dst[qi];
     if (s0 < 0 || d0 < 0 || s0 >= n_real || d0 >= n_real) { len_out[qi] = FWX_ERR_INVALID; return; }
-    len_out[qi] = exact_walk(t, s0, d0, paths + (size_t)qi * cap, stacks + (size_t)qi * 3 * cap, cap);
+    len_out[qi] = exact_walk(t, n_real, s0, d0, paths + (size_t)qi * cap,
+                             stacks + (size_t)qi * 3 * exact_stack_triples(n_real), cap);
 }
 
-// One query, the pair by value (checked by the caller): nothing is copied in before the launch.  List and
-// stack live in `walk` (4 * cap entries).
-__global__ void exact_path_kernel(EntryTab t, int src, int dst, int32_t *walk, int cap, int32_t *len_out)
+// One query, the pair by value (checked by the caller): nothing is copied in before the launch.  `walk` holds
+// the list (cap entries), then the stack (3 * exact_stack_triples(n_real) entries).
+__global__ void exact_path_kernel(EntryTab t, int n_real, int src, int dst, int32_t *walk, int cap, int32_t *len_out)
 {
-    *len_out = exact_walk(t, src, dst, walk, walk + cap, cap);
+    *len_out = exact_walk(t, n_real, src, dst, walk, walk + cap, cap);
 }
 
 // What a one-query kernel just launched on `s` leaves: the length (or error) at len_dev, which is returned,
@@ -782,7 +794,7 @@ int run_exact_batch(const EntryTab &tab, int n_real, hipStream_t s, int32_t coun
     void *ids = nullptr, *d_paths = nullptr, *d_stacks = nullptr;
     if ((rc = lease.c->reserve(CallCtx::NEXT, c * 12, &ids)) ||
         (rc = lease.c->reserve(CallCtx::RATE, c * cap * 4, &d_paths)) ||
-        (rc = lease.c->reserve(CallCtx::WS, c * cap * 12, &d_stacks)))
+        (rc = lease.c->reserve(CallCtx::WS, c * exact_stack_triples(n_real) * 12, &d_stacks)))
         return rc;
     int32_t *const d_src = (int32_t *)ids, *const d_dst = d_src + c, *const d_len = d_dst + c;
     FWX_HIP(hipMemcpyAsync(d_src, src, c * 4, hipMemcpyHostToDevice, s));
@@ -1512,13 +1524,16 @@ int fwx_matrix_query_exact(fwx_matrix *m, int32_t src, int32_t dst, double *rate
         hipStream_t s = m->slab.main;
         RateRead rate;
         if ((rc = rate.queue(m->slab.rate, (size_t)src * m->nd + dst, m->dtype, s, rate_out))) return rc;
-        if (!m->walk || m->walk_cap < cap) {      // grow-only scratch, reused across queries
+        // grow-only scratch, reused across queries: the list (cap), the walk's stack (sized by the order), the length
+        const size_t stack_ints = 3 * exact_stack_triples(m->n);
+        if (!m->walk || m->walk_cap < cap) {
             if (m->walk) { drain_stream(s); (void)hipFree(m->walk); m->walk = nullptr; }
-            FWX_HIP(hipMalloc((void **)&m->walk, ((size_t)4 * cap + 1) * 4));
+            FWX_HIP(hipMalloc((void **)&m->walk, ((size_t)cap + stack_ints + 1) * 4));
             m->walk_cap = cap;
         }
-        int32_t *const len_dev = m->walk + (size_t)4 * cap;
-        hipLaunchKernelGGL(exact_path_kernel, dim3(1), dim3(1), 0, s, tab_of(m), src, dst, m->walk, cap, len_dev);
+        int32_t *const len_dev = m->walk + (size_t)cap + stack_ints;
+        hipLaunchKernelGGL(exact_path_kernel, dim3(1), dim3(1), 0, s, tab_of(m), m->n, src, dst, m->walk, cap,
+                           len_dev);
         const int len = read_list(s, len_dev, m->walk, path_out);
         rate.done();
         return len;

@@ -26,7 +26,7 @@ struct fwx_matrix {
     unsigned long long *upd;
     int32_t keep;          // the input is kept on the device
     int32_t kept_valid;    // ... and holds an upload
-    int32_t *walk;         // scratch of the exact-path walk (stack + output)
+    int32_t *walk;         // scratch of the exact-path walk (output, then a stack sized by the order)
     int32_t walk_cap;      // capacity (path entries) `walk` was sized for
     int32_t rec_ready;     // a traced solve of the current upload has completed
     int32_t fresh;         // the arrays hold an uploaded input that has not been solved yet

@@ -274,14 +274,21 @@ int fwx_matrix_resolve(fwx_matrix *m, int32_t count, const int64_t *index, const
  * uploaded input (fwx_matrix_solve on an already solved traced matrix: FWX_ERR_INVALID).
  * query_exact before a completed traced solve of the current upload: FWX_ERR_INVALID.
  * fwx_matrix_path_log_count: U of that solve if it was asked to count (fwx_opts.updates_out),
- * else 0.  path_out receives the vertices after src up to dst; returns the length.              */
+ * else 0.  path_out receives the vertices after src up to dst; returns the length.
+ * Capacity, for every input (inside the domain or not): a list of L entries is returned whenever
+ * cap >= L, and FWX_ERR_CAPACITY exactly when L > cap -- cap bounds the list and nothing else.  The
+ * walk's own stack is sized by n (its depth is at most n: the pivots along a descent of the
+ * concatenation tree strictly decrease), so a list whose tree has halves that contribute nothing (an
+ * empty ikPath, a leaf without an edge: possible only outside the domain) needs no more cap than its
+ * length.  An empty list (length 0) fits any cap >= 1.                                            */
 int fwx_matrix_enable_path_log(fwx_matrix *m);
 int fwx_matrix_path_log_count(fwx_matrix *m, uint64_t *count_out);
 int fwx_matrix_query_exact(fwx_matrix *m, int32_t src, int32_t dst, double *rate_out,
                            int32_t *path_out, int32_t cap);
 /* Batch form: count (src, dst) pairs in one launch (one thread per pair).  len_out[q] = length of
- * list q or a negative fwx_status (FWX_ERR_CAPACITY: longer than cap); path_out + q*cap receives
- * it.  Host arrays in and out.                                                                  */
+ * list q or a negative fwx_status (FWX_ERR_CAPACITY: list q is longer than cap, the rule above, item
+ * by item: the other items of the batch are answered); path_out + q*cap receives it.  Host arrays in
+ * and out.  Device scratch: cap + 3 (n + 2) int32 per pair.                                        */
 int fwx_matrix_query_exact_batch(fwx_matrix *m, int32_t count, const int32_t *src, const int32_t *dst,
                                  int32_t *len_out, int32_t *path_out, int32_t cap);
 

@@ -12,6 +12,10 @@ Contents
   list_faithful.py               entry-for-entry restatement with whole `_path` lists of
                                  buildMatrix / runAlgo / floydWarshall / optimum
                                  (Algorithms.hs:19-78).
+  list_ropes.py                  the same whole `_path` lists of runAlgo with O(1) concatenation (a list is a
+                                 node id: empty, one vertex, or left ++ right), a pivot step in numpy: all
+                                 n^2 lists at n = 260 in 0.1 s; pinned to list_faithful.py list for list and to
+                                 the C loop in rate bits, next, hops and U (tests/test_oracle_ropes.py).
 
 Parity pinning: the reference is Haskell and cannot be built here (no GHC/cabal/nix in the
 image), so the oracle is pinned by the reference's own golden vectors committed as data under

@@ -22,3 +22,21 @@ def hostile_matrix_mix(rnd, n, dtype):
     nxt = np.where(rnd.random((n, n)) < 0.8, np.arange(n, dtype=np.int32)[None, :], -1).astype(np.int32)
     hops = (nxt >= 0).astype(np.int32)
     return np.ascontiguousarray(rate), np.ascontiguousarray(nxt), np.ascontiguousarray(hops), bool(heavy)
+
+
+def market_rates(n_exch, n_ccy, seed, density=0.5):
+    """The reference's own kind of graph: per-exchange quotes plus its built-in rate-1.0 edges
+    between the same currency on two exchanges (Algorithms.hs:35) -- exact ties everywhere."""
+    rnd = np.random.default_rng(seed)
+    ccys = ["C%02d" % i for i in range(n_ccy)]
+    price = dict(zip(ccys, 0.5 + 1.5 * rnd.random(n_ccy)))
+    rates = {}
+    for e in range(n_exch):
+        exch = "X%02d" % e
+        for i in range(n_ccy):
+            for j in range(i + 1, n_ccy):
+                if rnd.random() < density:
+                    a, b = ccys[i], ccys[j]
+                    rates[((exch, a), (exch, b))] = price[b] / price[a] * (0.97 + 0.03 * rnd.random())
+                    rates[((exch, b), (exch, a))] = price[a] / price[b] * (0.97 + 0.03 * rnd.random())
+    return rates

@@ -5,7 +5,9 @@ them needs a fresh interpreter: the parent starts this module with the knobs in 
 JSON list of cases as argv[1], one child at a time.  Each case solves one input on the GPU and on the
 oracle and compares every field bit for bit; it also records the launch forms it reached
 (fwx_test_kernel_forms).  The child prints one JSON line: per case an error message or null and the
-forms seen.  It imports numpy, the oracle and floydwarshall_amd only -- never torch.
+forms seen.  It imports numpy, the oracle and floydwarshall_amd only -- never torch.  A traced case (nt) of
+order <= 452 also has the exact `_path` lists of 800 sampled pairs compared with the rope oracle
+(oracle/list_ropes.py), hostile inputs included; "lists" keeps one case on the list-faithful restatement.
 
 A case: {"kind": t1 | t2 | t3 | t4 | hostile, "n", "dtype": f32 | f64, "fields", "seed",
 "engine": fused | perk | auto, "lists": bool}.  fields: r (rates), ru (rates, counting U),
@@ -30,6 +32,7 @@ from helpers import assert_bits_equal  # noqa: E402
 from hostile_inputs import hostile_matrix  # noqa: E402
 
 THREADS = min(16, len(os.sched_getaffinity(0)))
+ROPES_MAX_N = 452             # traced cases up to this order also have 800 sampled lists read (oracle/list_ropes.py)
 ENGINES = {"fused": engine.FWX_ENGINE_FUSED, "perk": engine.FWX_ENGINE_PERK, "auto": engine.FWX_ENGINE_AUTO}
 
 
@@ -59,15 +62,33 @@ def run_case(c):
             dm.upload(rate, nxt)
             dm.solve(engine=eng)
             gr, gn, _ = dm.download()
-            lists = None
-            if c.get("lists"):
+            lists = ropes = None
+            if c.get("lists") or n <= ROPES_MAX_N:
                 rnd = np.random.default_rng(c["seed"] + 1)
                 src = rnd.integers(0, n, 800).astype(np.int32)
                 dst = rnd.integers(0, n, 800).astype(np.int32)
-                lists = (src, dst, dm.query_exact_batch(src, dst))
+                cap = None
+                if not c.get("lists"):
+                    # every other traced case: the sampled lists against the rope oracle, hostile inputs included
+                    # (there a list can be far longer than the default cap of 4 n: cap comes from the oracle)
+                    from oracle import list_ropes
+                    ropes = list_ropes.solve(rate, nxt)
+                    longest = int(ropes.lengths[src, dst].max())
+                    assert longest <= 1 << 16, "sampled list of %d entries" % longest
+                    cap = max(longest, 1) + 2
+                lists = (src, dst, dm.query_exact_batch(src, dst, cap=cap))
         assert_bits_equal(gr, er, "rate")
         assert_bits_equal(gn, en, "next")
-        if lists is not None:
+        if ropes is not None:
+            assert_bits_equal(ropes.rate, er, "rope oracle vs dense oracle: rate")
+            assert_bits_equal(ropes.next, en, "rope oracle vs dense oracle: next")
+            assert ropes.updates == eu, "rope oracle U %d vs dense oracle %d" % (ropes.updates, eu)
+            src, dst, got = lists
+            want = ropes.paths(src, dst)
+            assert sum(len(w) for w in want) > 0
+            for q in range(len(src)):
+                assert tuple(got[q]) == want[q], "exact list (%d, %d): %r vs %r" % (src[q], dst[q], got[q], want[q])
+        elif lists is not None:
             from oracle import list_faithful as lf
             m = lf.run_algo(lf.from_dense([("X", "C%04d" % i) for i in range(n)], rate, nxt), dtype)
             paths = lf.path_indices(m)

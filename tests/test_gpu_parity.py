@@ -12,6 +12,7 @@ from oracle import list_faithful as lf
 
 from helpers import (assert_bits_equal, dev, dev_empty, dev_sync, dev_zeros, golden_dense,
                      golden_rates_dict, host, host_cat, load_golden, path_from_trace)
+from hostile_inputs import market_rates as _market_rates
 
 pytestmark = pytest.mark.gpu
 
@@ -965,24 +966,6 @@ def test_index_math_beyond_2_to_31_elements():
 # ---------------------------------------------------------------------------------------------
 # Exact `_path` lists: path trace + fwx_matrix_query_exact
 # ---------------------------------------------------------------------------------------------
-
-def _market_rates(n_exch, n_ccy, seed, density=0.5):
-    """The reference's own kind of graph: per-exchange quotes plus its built-in rate-1.0 edges
-    between the same currency on two exchanges (Algorithms.hs:35) -- exact ties everywhere."""
-    rnd = np.random.default_rng(seed)
-    ccys = ["C%02d" % i for i in range(n_ccy)]
-    price = dict(zip(ccys, 0.5 + 1.5 * rnd.random(n_ccy)))
-    rates = {}
-    for e in range(n_exch):
-        exch = "X%02d" % e
-        for i in range(n_ccy):
-            for j in range(i + 1, n_ccy):
-                if rnd.random() < density:
-                    a, b = ccys[i], ccys[j]
-                    rates[((exch, a), (exch, b))] = price[b] / price[a] * (0.97 + 0.03 * rnd.random())
-                    rates[((exch, b), (exch, a))] = price[a] / price[b] * (0.97 + 0.03 * rnd.random())
-    return rates
-
 
 def _exact_paths_case(m0, dtype=np.float64, solve_engine=engine.FWX_ENGINE_AUTO):
     """m0: list-form initial matrix.  Solve with the list-faithful reference and with the logged

@@ -9,10 +9,13 @@ blocks, three partitions split at rows that are no multiples of 64).  Inputs are
 non-zero powers of two, so ties abound.  (At these orders the lists coincide with the walks of the final
 next-hops; the two queries still read different arrays -- the trace and next0 against next.)
 
-Capacity on these inputs: every sub-entry the walk visits is off-diagonal and has an edge, so each pending stack
-item yields at least one list entry; len + pending <= L at every step and both bounds (len >= cap, sp + 2 > cap)
-hold off exactly while cap >= L.  The tests only rely on "cap < L fails" and on lists no longer than cap
-succeeding next to a failing one, as the library documents."""
+Capacity: cap bounds the list alone -- a list of L entries is returned whenever cap >= L and FWX_ERR_CAPACITY exactly
+when L > cap (fwx.h), on every input; the walk's stack is sized by the order.  On these inputs the older rule, a stack
+of cap triples, gave the same answers: every sub-entry the walk visits is off-diagonal and has an edge, so each pending
+stack item yields at least one list entry and len + pending <= L at every step.  Outside the reference's domain a
+pending item can yield nothing and that rule refused lists that fit; tests/test_gpu_exact_lists_edges.py pins the
+rule there.  The tests here rely on "cap < L fails" and on lists no longer than cap succeeding next to a failing one,
+as the library documents."""
 import ctypes
 import functools
 
