@@ -103,6 +103,15 @@ SIGNATURES = {
     "fwx_dev_solve_batch": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32,
                                            c_vp, c_vp]),
     "fwx_test_batch_wave_max_n": (ctypes.c_int, []),
+    "fwx_dev_solve_batch_traced": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64,
+                                                  ctypes.POINTER(FwxTrace), c_vp, c_vp]),
+    "fwx_dev_exact_paths_batch": (ctypes.c_int, [c_i32, c_i32, ctypes.c_int64, c_vp, ctypes.POINTER(FwxTrace), c_i32,
+                                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "fwx_solve_batch_lists_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                 c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_batch_lists_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                 c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
+    "fwx_test_batch_lists_chunk": (ctypes.c_int64, [c_i32, c_i32]),
     "fwx_follow_path": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i32, c_vp, c_i32]),
     "fwx_matrix_create": (ctypes.c_int, [ctypes.POINTER(c_vp), c_i32, c_i32, c_i32, c_i32, c_i32]),
     "fwx_matrix_upload": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),

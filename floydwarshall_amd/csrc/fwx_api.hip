@@ -504,27 +504,42 @@ int batch_range(int32_t n, int32_t k_begin, int32_t &k_end)
 
 template <typename T>
 int dev_solve_batch(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, int64_t stride,
-                    int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, hipStream_t s)
+                    int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, hipStream_t s,
+                    const fwx::PathLog &plog = fwx::PathLog())
 {
     const hipError_t e = fwx::launch_batch_solve<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
-                                                    d_updates_each, batch_wave_max_n(), s);
+                                                    d_updates_each, batch_wave_max_n(), s, plog);
     if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
     FWX_HIP(e);
     return FWX_OK;
 }
 
+// What fwx_solve_batch_lists_* adds to a batch solve: the exact lists of `items` triples, host arrays.
+struct BatchLists {
+    int32_t items;
+    const int32_t *mat, *src, *dst;
+    int32_t *len_out, *path_out;
+    int32_t cap;
+};
+
 // fwx_solve_batch_f64 / _f32: count matrices of order n from / to host arrays, one launch.  Pitch n, no
 // padding (the batch kernels load scalars), the arrays of the batch back to back on the device.
+// ls (fwx_solve_batch_lists_*): the solve also keeps the unsolved next-hops and the path trace in the context
+// and walks the items' lists from them, batch_lists_chunk items per launch.
 template <typename T>
 int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
-                     const fwx_opts *o)
+                     const fwx_opts *o, const BatchLists *ls = nullptr)
 {
-    if (count < 0 || n < 0) return FWX_ERR_INVALID;
+    if (count < 0 || n < 0 || (ls && ls->items < 0)) return FWX_ERR_INVALID;
     if (count == 0 || n == 0) return FWX_OK;
     if (!rate || (hops && !next)) return FWX_ERR_INVALID;
+    if (ls && (!next || (ls->items > 0 && (ls->cap < 1 || !ls->mat || !ls->src || !ls->dst || !ls->len_out ||
+                                           !ls->path_out))))
+        return FWX_ERR_INVALID;
     Opts op;
     int rc = read_opts(o, n, op);
     if (rc) return rc;
+    if (ls && (op.k_begin != 0 || op.k_end != n)) return FWX_ERR_INVALID;      // the trace covers whole solves only
     if ((rc = batch_range(n, op.k_begin, op.k_end))) return rc;
     if (op.engine != FWX_ENGINE_AUTO) return FWX_ERR_UNSUPPORTED;
     DeviceGuard g;
@@ -572,8 +587,27 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     if (next) FWX_HIP(hipMemcpyAsync(d_next, staged ? (const void *)st_next : (const void *)next, b_idx, hipMemcpyHostToDevice, s));
     if (hops) FWX_HIP(hipMemcpyAsync(d_hops, staged ? (const void *)st_hops : (const void *)hops, b_idx, hipMemcpyHostToDevice, s));
 
+    // lists: the unsolved next-hops and the three trace arrays, then the walk's own memory for one chunk of items
+    // (triples and lengths, lists, stacks), all in the context's SMALL buffer
+    fwx::PathLog plog;
+    int32_t *d_next0 = nullptr, *d_walk = nullptr;
+    const long long chunk = ls ? std::min<long long>(batch_lists_chunk(n, ls->cap), ls->items) : 0;
+    const size_t stack_ints = FWX_EXACT_SCRATCH_INTS((size_t)n);
+    if (ls) {
+        void *p = nullptr;
+        const size_t walk_ints = (size_t)chunk * (4 + (size_t)ls->cap + stack_ints);
+        fail_point();
+        if ((rc = cx.reserve(CallCtx::SMALL, (4 * cells + walk_ints) * sizeof(int32_t), &p))) return rc;
+        d_next0 = (int32_t *)p;
+        plog.last = d_next0 + cells;
+        plog.at_col = plog.last + cells;
+        plog.at_row = plog.at_col + cells;
+        d_walk = plog.at_row + cells;
+        FWX_HIP(hipMemcpyAsync(d_next0, d_next, b_idx, hipMemcpyDeviceToDevice, s));
+    }
+
     if ((rc = dev_solve_batch<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
-                                 op.k_begin, op.k_end, (unsigned long long *)d_upd, s)))
+                                 op.k_begin, op.k_end, (unsigned long long *)d_upd, s, plog)))
         return rc;
 
     FWX_HIP(hipMemcpyAsync(staged ? (void *)st_rate : (void *)rate, d_rate, b_rate, hipMemcpyDeviceToHost, s));
@@ -581,6 +615,19 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     if (hops) FWX_HIP(hipMemcpyAsync(staged ? (void *)st_hops : (void *)hops, d_hops, b_idx, hipMemcpyDeviceToHost, s));
     if (counting)
         FWX_HIP(hipMemcpyAsync(h_upd.data(), d_upd, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    for (long long q0 = 0; ls && q0 < ls->items; q0 += chunk) {
+        const size_t c = (size_t)std::min<long long>(chunk, ls->items - q0), cap = (size_t)ls->cap;
+        int32_t *d_mat = d_walk, *d_src = d_mat + c, *d_dst = d_src + c, *d_len = d_dst + c, *d_paths = d_len + c,
+                *d_stacks = d_paths + c * cap;
+        FWX_HIP(hipMemcpyAsync(d_mat, ls->mat + q0, c * 4, hipMemcpyHostToDevice, s));
+        FWX_HIP(hipMemcpyAsync(d_src, ls->src + q0, c * 4, hipMemcpyHostToDevice, s));
+        FWX_HIP(hipMemcpyAsync(d_dst, ls->dst + q0, c * 4, hipMemcpyHostToDevice, s));
+        if ((rc = fwxi::launch_exact_batch(count, n, (long long)n * n, d_next0, plog, (int)c, d_mat, d_src, d_dst,
+                                           d_len, d_paths, ls->cap, d_stacks, s)))
+            return rc;
+        FWX_HIP(hipMemcpyAsync(ls->len_out + q0, d_len, c * 4, hipMemcpyDeviceToHost, s));
+        FWX_HIP(hipMemcpyAsync(ls->path_out + (size_t)q0 * cap, d_paths, c * cap * 4, hipMemcpyDeviceToHost, s));
+    }
     FWX_HIP(hipStreamSynchronize(s));
     if (staged) {
         memcpy(rate, st_rate, b_rate);
@@ -708,22 +755,23 @@ __global__ void follow_path_kernel(EntryTab t, int n_real, int src, int dst, int
 // entry, outside it (a leaf with next0 < 0, an update whose ikPath was empty) a pending item can yield nothing,
 // and a list of length L can need more than L triples.  The depth test below cannot fire on a trace a solve
 // wrote; it keeps a corrupted one inside the scratch.
-__host__ __device__ inline size_t exact_stack_triples(int n_real) { return (size_t)n_real + 2; }
+__host__ __device__ constexpr size_t exact_stack_triples(int n_real) { return (size_t)n_real + 2; }
+static_assert(FWX_EXACT_SCRATCH_INTS(128) == 3 * exact_stack_triples(128), "fwx.h states the walk's scratch per item");
 
-__device__ int exact_walk(const EntryTab &t, int n_real, int src, int dst, int32_t *out, int32_t *stack, int cap)
+template <typename Tab>
+__device__ int exact_walk(const Tab &t, int n_real, int src, int dst, int32_t *out, int32_t *stack, int cap)
 {
-    enum { FINAL = 0, AS_COLUMN = 1, AS_ROW = 2 };
+    enum { FINAL = WALK_FINAL, AS_COLUMN = WALK_AS_COLUMN, AS_ROW = WALK_AS_ROW };
     const int scap = (int)exact_stack_triples(n_real);
     int sp = 0, len = 0;
     stack[0] = src; stack[1] = dst; stack[2] = FINAL; sp = 1;
     while (sp > 0) {
         --sp;
         const int a = stack[3 * sp], b = stack[3 * sp + 1], kind = stack[3 * sp + 2];
-        int p;
-        const size_t off = t.locate(a, b, p);
-        const int q = kind == FINAL ? t.last[p][off] : kind == AS_COLUMN ? t.at_col[p][off] : t.at_row[p][off];
+        const typename Tab::Cell cell = t.cell(a, b);
+        const int q = t.pivot(cell, kind);
         if (q < 0) {
-            if (t.next0[p][off] >= 0) {
+            if (t.edge(cell)) {
                 if (len >= cap) return FWX_ERR_CAPACITY;
                 out[len++] = b;
             }
@@ -748,6 +796,40 @@ __global__ __launch_bounds__(64) void exact_paths_kernel(EntryTab t, int n_real,
     if (s0 < 0 || d0 < 0 || s0 >= n_real || d0 >= n_real) { len_out[qi] = FWX_ERR_INVALID; return; }
     len_out[qi] = exact_walk(t, n_real, s0, d0, paths + (size_t)qi * cap,
                              stacks + (size_t)qi * 3 * exact_stack_triples(n_real), cap);
+}
+
+// The same over a traced batch (fwx_dev_exact_paths_batch): item q is (mat[q], src[q], dst[q]), matrix m of the
+// batch at + m*stride in each of the four arrays, pitch n.  An item outside the batch gets FWX_ERR_INVALID, alone.
+__global__ __launch_bounds__(64) void exact_paths_batch_kernel(int count, int n, long long stride,
+                                                               const int32_t *next0, fwx::PathLog plog, int items,
+                                                               const int32_t *mat, const int32_t *src,
+                                                               const int32_t *dst, int32_t *paths, int32_t *stacks,
+                                                               int cap, int32_t *len_out)
+{
+    const int qi = blockIdx.x * 64 + threadIdx.x;
+    if (qi >= items) return;
+    const int m0 = mat[qi], s0 = src[qi], d0 = dst[qi];
+    if (m0 < 0 || m0 >= count || s0 < 0 || d0 < 0 || s0 >= n || d0 >= n) { len_out[qi] = FWX_ERR_INVALID; return; }
+    const size_t off = (size_t)m0 * (size_t)stride;
+    BatchTab t;
+    t.n = n;
+    t.last = plog.last + off;
+    t.at_col = plog.at_col + off;
+    t.at_row = plog.at_row + off;
+    t.next0 = next0 + off;
+    len_out[qi] = exact_walk(t, n, s0, d0, paths + (size_t)qi * cap, stacks + (size_t)qi * 3 * exact_stack_triples(n),
+                             cap);
+}
+
+int launch_exact_batch(int count, int n, long long stride, const int32_t *next0, const fwx::PathLog &plog,
+                       int items, const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
+                       int32_t *paths, int cap, int32_t *stacks, hipStream_t s)
+{
+    if (items <= 0) return FWX_OK;
+    hipLaunchKernelGGL(exact_paths_batch_kernel, dim3((unsigned)(((size_t)items + 63) / 64)), dim3(64), 0, s, count,
+                       n, stride, next0, plog, items, mat, src, dst, paths, stacks, cap, len_out);
+    FWX_HIP(hipGetLastError());
+    return FWX_OK;
 }
 
 // One query, the pair by value (checked by the caller): nothing is copied in before the launch.  `walk` holds
@@ -1112,6 +1194,78 @@ int fwx_dev_solve_batch(int32_t count, int32_t n, int32_t dtype, void *rate, int
 }
 
 int fwx_test_batch_wave_max_n(void) { return batch_wave_max_n(); }
+
+int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                               int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
+                               void *stream)
+{
+    return fwxi::guarded([&]() -> int {
+        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
+        if (count == 0 || n == 0) return FWX_OK;
+        if (!rate || !next || !trace || !trace->last || !trace->at_col || !trace->at_row ||
+            stride < (int64_t)n * n)
+            return FWX_ERR_INVALID;
+        if (n > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        fwx::PathLog plog;
+        plog.last = trace->last;
+        plog.at_col = trace->at_col;
+        plog.at_row = trace->at_row;
+        hipStream_t s = (hipStream_t)stream;
+        if (dtype == FWX_F64)
+            return dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, 0, n, d_updates_each, s, plog);
+        return dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, 0, n, d_updates_each, s, plog);
+    });
+}
+
+int fwx_dev_exact_paths_batch(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                              const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              int32_t *scratch, void *stream)
+{
+    return fwxi::guarded([&]() -> int {
+        if (count < 0 || n < 0 || items < 0) return FWX_ERR_INVALID;
+        if (count == 0 || n == 0 || items == 0) return FWX_OK;
+        if (!next0 || !trace || !trace->last || !trace->at_col || !trace->at_row || stride < (int64_t)n * n ||
+            cap < 1 || !mat || !src || !dst || !len_out || !path_out || !scratch)
+            return FWX_ERR_INVALID;
+        if (n > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        fwx::PathLog plog;
+        plog.last = trace->last;
+        plog.at_col = trace->at_col;
+        plog.at_row = trace->at_row;
+        return launch_exact_batch(count, n, (long long)stride, next0, plog, items, mat, src, dst, len_out, path_out,
+                                  cap, scratch, (hipStream_t)stream);
+    });
+}
+
+int fwx_solve_batch_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, &ls);
+    });
+}
+
+int fwx_solve_batch_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, &ls);
+    });
+}
+
+int64_t fwx_test_batch_lists_chunk(int32_t n, int32_t cap)
+{
+    return n < 0 || cap < 1 ? (int64_t)FWX_ERR_INVALID : (int64_t)batch_lists_chunk(n, cap);
+}
 
 int fwx_follow_path(int32_t n, const int32_t *next, int32_t src, int32_t dst, int32_t *out,
                     int32_t cap)

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <new>
 #include <vector>
+#include <errno.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <stdint.h>
@@ -266,7 +267,8 @@ struct SideStream {
 // static destructors).
 // ------------------------------------------------------------------------------------------------
 struct CallCtx {
-    enum { RATE, NEXT, HOPS, WS, SMALL, NBUF };            // SMALL: update shards + domain flag
+    enum { RATE, NEXT, HOPS, WS, SMALL, NBUF };            // SMALL: update shards + domain flag; in
+                                                           // fwx_solve_batch_lists_*: next0, the trace, the walk's chunk
     static constexpr size_t kKeepBytes = (size_t)256 << 20;
     int device = -1;
     hipStream_t s = nullptr;
@@ -506,6 +508,25 @@ inline int batch_wave_max_n()
         if (*e >= '0' && *e <= '9' && *end == '\0' && v >= 0 && v <= FWX_BATCH_WAVE_N) return (int)v;
     }
     return FWX_BATCH_WAVE_MAX_N_DEFAULT;
+}
+
+// fwx_solve_batch_lists_*: items walked per launch.  The lists (cap int32 per item), the walk stacks
+// (FWX_EXACT_SCRATCH_INTS(n)) and the item triples + lengths (4) of one launch stay within
+// FWX_BATCH_LISTS_BUDGET_BYTES of device memory; FWX_BATCH_LISTS_CHUNK (environment, read per call: digits only,
+// >= 1, anything else means the default) asks for fewer.  At least one item per launch.  No result depends on it.
+#define FWX_BATCH_LISTS_BUDGET_BYTES ((long long)64 << 20)
+inline long long batch_lists_chunk(int n, int cap)
+{
+    const long long per_item = 4ll * ((long long)cap + 3ll * ((long long)n + 2) + 4);
+    long long fit = FWX_BATCH_LISTS_BUDGET_BYTES / per_item;
+    if (fit < 1) fit = 1;
+    if (const char *e = getenv("FWX_BATCH_LISTS_CHUNK")) {
+        char *end = nullptr;
+        errno = 0;
+        const long long v = strtoll(e, &end, 10);
+        if (*e >= '0' && *e <= '9' && *end == '\0' && errno == 0 && v >= 1 && v < fit) return v;
+    }
+    return fit;
 }
 
 // Launches of the multi-pivot schedule by pivots per launch: [0] relax_k (ragged single pivots), [1] / [2] /

@@ -140,11 +140,14 @@ hipError_t launch_small_solve(T *rate, int32_t *next, int32_t *hops, int n, int 
 // 2^21 matrices).  n <= wave_max_n (at most FWX_BATCH_WAVE_N): one wave per matrix, the matrix in registers,
 // no LDS; otherwise small_solve's body with one workgroup per matrix.  updates_each: count counters or
 // nullptr, counter b is incremented by U of matrix b.  No kernel-form bit is recorded.
+// plog (optional; plog.last != nullptr): the path trace of matrix b goes to the three arrays at + b*stride, pitch n
+// like next -- every cell of the n x n part is written, the gap never.  Needs next and the whole pivot range
+// [0, n) (hipErrorInvalidValue otherwise).
 #define FWX_BATCH_WAVE_N 16
 template <typename T>
 hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride,
                               int k_begin, int k_end, unsigned long long *updates_each, int wave_max_n,
-                              hipStream_t s);
+                              hipStream_t s, PathLog plog = PathLog());
 
 template <typename T>
 hipError_t launch_snapshot_row(T *dst, const T *src, int32_t *hdst, const int32_t *hsrc, int n,

@@ -869,19 +869,22 @@ __global__ __launch_bounds__(M * RG) void small_solve(T *rate, int32_t *next, in
 
 // -------------------------------------------------------------------------------------------------
 // Batched small solves: `count` independent matrices of one order n <= 128 in one launch, matrix b at
-// rate + b*stride (next / hops alike), U of matrix b added to updates[b].  No path trace.
+// rate + b*stride (next / hops alike), U of matrix b added to updates[b].  LOG: the path trace of matrix b
+// (PathLog) goes to plog's three arrays at + b*stride, pitch n like next; whole pivot range only (the launcher
+// sees to that), every cell of the n x n part written, the gap never.
 //
 // Workgroup tier (any n <= 128): small_solve's body, workgroup b on matrix b.
 // -------------------------------------------------------------------------------------------------
-template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS>
+template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
 __global__ __launch_bounds__(M * RG) void small_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
                                                             long long stride, int k_begin, int k_end,
-                                                            unsigned long long *updates)
+                                                            unsigned long long *updates, PathLog plog)
 {
     const size_t off = (size_t)blockIdx.x * (size_t)stride;
-    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, false>(rate + off, HAS_NEXT ? next + off : nullptr,
-                                                          HAS_HOPS ? hops + off : nullptr, n, k_begin, k_end,
-                                                          updates ? updates + blockIdx.x : nullptr, PathLog());
+    if constexpr (LOG) { plog.last += off; plog.at_col += off; plog.at_row += off; }
+    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(rate + off, HAS_NEXT ? next + off : nullptr,
+                                                        HAS_HOPS ? hops + off : nullptr, n, k_begin, k_end,
+                                                        updates ? updates + blockIdx.x : nullptr, plog);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -898,11 +901,18 @@ __global__ __launch_bounds__(M * RG) void small_solve_batch(T *rate, int32_t *ne
 // entry (never a target; never an operand, because the only steps that would read it skip it), whose
 // value in memory is left alone.  Row groups and pivots that are padding only are skipped by
 // wave-uniform tests.  A wave past `count` leaves at once: there is no barrier it could be missed at.
+//
+// LOG (the path trace, see PathLog): hd[m] = pivot of the newest update of the lane's m-th entry, -1 = none,
+// selected beside x / nx / hp.  The snapshots of step k are two stores: the 16 lanes that hold row k store
+// hd[mk] to at_row[k][c], the four lanes that hold column k store hd[m] to at_col[r][k] for their rows.  Row k
+// and column k are fixed points of step k (their row / column operand is NaN), so hd of these entries does not
+// change inside the step and "the start of step k" is anywhere in it: the stores are issued at the top,
+// before the cross-lane reads, and drain behind them.  `last` is stored with the results.
 // -------------------------------------------------------------------------------------------------
-template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
 __global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
                                                         long long stride, int count, int k_begin,
-                                                        int k_end, unsigned long long *updates)
+                                                        int k_end, unsigned long long *updates, PathLog plog)
 {
     constexpr int E = 4;                      // rows per lane: q, q + 4, q + 8, q + 12
     const int lane = threadIdx.x & 63;
@@ -913,12 +923,15 @@ __global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, 
     const size_t base = (size_t)b * (size_t)stride;
 
     T x[E];
-    int32_t nx[E], hp[E];
+    int32_t nx[E], hp[E], hd[LOG ? E : 1];
+    if constexpr (LOG) { plog.last += base; plog.at_col += base; plog.at_row += base; }
+    const int qn = q * n;
 #pragma unroll
     for (int m = 0; m < E; ++m) {
         const int r = q + 4 * m;
         const bool in = r < n && c < n;
         const size_t off = base + (size_t)(r * n + c);
+        if constexpr (LOG) hd[m] = -1;
         x[m] = in ? rate[off] : quiet_nan<T>();
         if (r == c) x[m] = (T)__builtin_huge_val();           // skip j == i (see small_solve)
         nx[m] = -1;
@@ -934,6 +947,15 @@ __global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, 
         for (int kq = 0; kq < 4; ++kq) {
             const int k = 4 * mk + kq;
             if (k < k_begin || k >= k_end) continue;          // scalar (k_end <= n)
+            if constexpr (LOG) {                              // the snapshots of step k (k < n)
+                // scalar bases, one vector offset each (c, q * n): no address lives across steps
+                if (q == kq && c < n) (plog.at_row + k * n)[c] = hd[mk];
+                if (c == k) {
+#pragma unroll
+                    for (int m = 0; m < E; ++m)
+                        if (q + 4 * m < n) (plog.at_col + (4 * m * n + k))[qn] = hd[m];
+                }
+            }
             // every operand of step k, before any register changes
             const int rsrc = kq * 16 + c;
             T rkc = __shfl(x[mk], rsrc, 64);
@@ -964,6 +986,7 @@ __global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, 
                 // head (ikPath ++ kjPath): next[i][k] unless ikPath is empty, then next[k][j]
                 if constexpr (HAS_NEXT) nx[m] = p ? (cn[m] < 0 ? nkc : cn[m]) : nx[m];
                 if constexpr (HAS_HOPS) hp[m] = p ? ch[m] + hkc : hp[m];
+                if constexpr (LOG) hd[m] = p ? k : hd[m];
                 mine += (unsigned int)__builtin_popcountll(__ballot(p));   // scalar; wave total
             }
         }
@@ -977,6 +1000,7 @@ __global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, 
             if (r != c) rate[off] = x[m];
             if constexpr (HAS_NEXT) next[off] = nx[m];
             if constexpr (HAS_HOPS) hops[off] = hp[m];
+            if constexpr (LOG) (plog.last + 4 * m * n)[qn + c] = hd[m];
         }
     }
     if (updates && mine && lane == 0) atomicAdd(&updates[b], (unsigned long long)mine);
@@ -985,11 +1009,13 @@ __global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, 
 template <typename T>
 hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride,
                               int k_begin, int k_end, unsigned long long *updates_each, int wave_max_n,
-                              hipStream_t s)
+                              hipStream_t s, PathLog plog)
 {
     if (count <= 0 || n <= 0 || k_end <= k_begin) return hipSuccess;
     if (n > FWX_SMALL_N || (hops && !next) || k_begin < 0 || k_end > n || stride < (long long)n * n)
         return hipErrorInvalidValue;
+    const bool lg = plog.last != nullptr;
+    if (lg && (!next || !plog.at_col || !plog.at_row || k_begin != 0 || k_end != n)) return hipErrorInvalidValue;
     const bool wave = n <= wave_max_n && n <= FWX_BATCH_WAVE_N;
     // One launch; a launch is limited to 2^32 - 1 threads, so a batch of more than kChunk matrices
     // (2^21 workgroups of 1024 threads) takes one launch per kChunk.
@@ -1000,17 +1026,19 @@ hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, 
         T *r = rate + off;
         int32_t *nx = next ? next + off : nullptr, *hp = hops ? hops + off : nullptr;
         unsigned long long *u = updates_each ? updates_each + b0 : nullptr;
-#define FWX_BATCH_WAVE(HN, HH)                                                                     \
-    hipLaunchKernelGGL((wave_solve_batch<T, HN, HH>), dim3((cnt + 3) / 4), dim3(256), 0, s, r, nx, hp, n, \
-                       stride, cnt, k_begin, k_end, u)
-#define FWX_BATCH_WG(M, RG, HN, HH)                                                                \
-    hipLaunchKernelGGL((small_solve_batch<T, M, RG, HN, HH>), dim3(cnt), dim3(M * RG), 0, s, r, nx, hp, n, \
-                       stride, k_begin, k_end, u)
+        PathLog pl;
+        if (lg) { pl.last = plog.last + off; pl.at_col = plog.at_col + off; pl.at_row = plog.at_row + off; }
+#define FWX_BATCH_WAVE(HN, HH, LG)                                                                 \
+    hipLaunchKernelGGL((wave_solve_batch<T, HN, HH, LG>), dim3((cnt + 3) / 4), dim3(256), 0, s, r, nx, hp, n, \
+                       stride, cnt, k_begin, k_end, u, pl)
+#define FWX_BATCH_WG(M, RG, HN, HH, LG)                                                            \
+    hipLaunchKernelGGL((small_solve_batch<T, M, RG, HN, HH, LG>), dim3(cnt), dim3(M * RG), 0, s, r, nx, hp, n, \
+                       stride, k_begin, k_end, u, pl)
 #define FWX_BATCH_FIELDS(LAUNCH, ...)                                                              \
     do {                                                                                           \
-        if (hops) LAUNCH(__VA_ARGS__ true, true);                                                  \
-        else if (next) LAUNCH(__VA_ARGS__ true, false);                                            \
-        else LAUNCH(__VA_ARGS__ false, false);                                                     \
+        if (hops) { if (lg) LAUNCH(__VA_ARGS__ true, true, true); else LAUNCH(__VA_ARGS__ true, true, false); }   \
+        else if (next) { if (lg) LAUNCH(__VA_ARGS__ true, false, true); else LAUNCH(__VA_ARGS__ true, false, false); } \
+        else LAUNCH(__VA_ARGS__ false, false, false);                                              \
     } while (0)
         if (wave) FWX_BATCH_FIELDS(FWX_BATCH_WAVE);
         else if (n <= 64) FWX_BATCH_FIELDS(FWX_BATCH_WG, 64, 16,);
@@ -1025,9 +1053,9 @@ hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, 
 }
 
 template hipError_t launch_batch_solve<float>(float *, int32_t *, int32_t *, int, int, long long, int, int,
-                                              unsigned long long *, int, hipStream_t);
+                                              unsigned long long *, int, hipStream_t, PathLog);
 template hipError_t launch_batch_solve<double>(double *, int32_t *, int32_t *, int, int, long long, int, int,
-                                               unsigned long long *, int, hipStream_t);
+                                               unsigned long long *, int, hipStream_t, PathLog);
 
 template <typename T>
 hipError_t launch_small_solve(T *rate, int32_t *next, int32_t *hops, int n, int k_begin, int k_end,

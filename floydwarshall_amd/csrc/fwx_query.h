@@ -13,8 +13,13 @@
 
 namespace fwxi {
 
+// Which of the three trace matrices holds the pivot of an entry the exact walk asks for (PathLog, fwx_kernels.h).
+enum WalkKind { WALK_FINAL = 0, WALK_AS_COLUMN = 1, WALK_AS_ROW = 2 };
+
 // Everything a query kernel needs to address entry (a, b) of a handle's matrix: partition p holds rows
 // [row0[p], row0[p + 1]) at pitch nd.  Passed by value (about 1.4 KB of kernel arguments).
+// The exact walk (exact_walk, fwx_api.hip) reads a table through three members only -- cell(a, b), pivot(cell, kind)
+// and edge(cell), the leaf test on the unsolved next-hops -- so that BatchTab below can stand in for it.
 struct EntryTab {
     int parts, nd;                             // nd = device pitch (fwx_matrix::nd), not the caller's n
     int row0[FWX_MAX_PARTS + 1];
@@ -26,6 +31,32 @@ struct EntryTab {
         while (p + 1 < parts && a >= row0[p + 1]) ++p;
         return (size_t)(a - row0[p]) * nd + b;
     }
+    struct Cell { int p; size_t off; };
+    __device__ __forceinline__ Cell cell(int a, int b) const
+    {
+        Cell c;
+        c.off = locate(a, b, c.p);
+        return c;
+    }
+    __device__ __forceinline__ int pivot(const Cell &c, int kind) const
+    {
+        return kind == WALK_FINAL ? last[c.p][c.off] : kind == WALK_AS_COLUMN ? at_col[c.p][c.off] : at_row[c.p][c.off];
+    }
+    __device__ __forceinline__ bool edge(const Cell &c) const { return next0[c.p][c.off] >= 0; }
+};
+
+// The same three reads for ONE matrix of a traced batch (fwx_dev_solve_batch_traced): order n, pitch n, the four
+// arrays already offset to the matrix (mat * stride).  Built per item by the batch kernel.
+struct BatchTab {
+    int n;
+    const int32_t *last, *at_col, *at_row, *next0;
+    typedef size_t Cell;
+    __device__ __forceinline__ Cell cell(int a, int b) const { return (size_t)a * n + b; }
+    __device__ __forceinline__ int pivot(Cell c, int kind) const
+    {
+        return kind == WALK_FINAL ? last[c] : kind == WALK_AS_COLUMN ? at_col[c] : at_row[c];
+    }
+    __device__ __forceinline__ bool edge(Cell c) const { return next0[c] >= 0; }
 };
 
 // One rate entry as a double.  queue() puts the copy on `s` (f32: into the first half of *rate_out); once
@@ -57,6 +88,13 @@ int run_follow(const EntryTab &tab, int n_real, hipStream_t s, int32_t *scratch,
 // q or its error, path_out + q * cap the list.
 int run_exact_batch(const EntryTab &tab, int n_real, hipStream_t s, int32_t count, const int32_t *src,
                     const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap);
+
+// The exact lists of `items` triples (mat, src, dst) of a traced batch, everything on the device, one launch on `s`,
+// nothing allocated or synchronised: len_out[q] = length or the error of item q, paths + q * cap its list;
+// stacks: items * 3 * (n + 2) ints.
+int launch_exact_batch(int count, int n, long long stride, const int32_t *next0, const fwx::PathLog &plog,
+                       int items, const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
+                       int32_t *paths, int cap, int32_t *stacks, hipStream_t s);
 
 }  // namespace fwxi
 

@@ -17,7 +17,8 @@ from ._lib import (FWX_ENGINE_AUTO, FWX_ENGINE_FUSED, FWX_ENGINE_PERK, FWX_F32, 
                    FWX_FUSED_BLOCK, FWX_UPDATE_SHARDS, FWX_XCHG_AUTO, FWX_XCHG_PEER, FWX_XCHG_RCCL,
                    FWX_ERR_RCCL, FwxError, FwxOpts, FwxPivots, FwxSlab, check, lib)
 
-__all__ = ["solve", "solve_batch", "dev_solve_batch", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
+__all__ = ["solve", "solve_batch", "dev_solve_batch", "solve_batch_lists", "dev_solve_batch_traced",
+           "dev_exact_paths_batch", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
            "dev_solve", "DeviceMatrix", "dev_relax", "dev_panel", "dev_panel_snap",
            "dev_relax_fused", "FusedWorkspace", "Trace", "FWX_FUSED_BLOCK", "device_count",
            "FwxError", "FWX_ENGINE_AUTO", "FWX_ENGINE_PERK", "FWX_ENGINE_FUSED",
@@ -143,6 +144,128 @@ def dev_solve_batch(rate_t, count, n, *, next_t=None, hops_t=None, stride=None, 
         vp(hops_t.data_ptr()) if hops_t is not None else None, stride, k_begin, k_end,
         vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)),
         "fwx_dev_solve_batch")
+
+
+# solve_batch_lists with cap=None: the first capacity tried, and the last (the lists of an input with arbitrage
+# grow with every pivot; past this bound the caller states the cap).
+BATCH_LISTS_FIRST_CAP = 64
+BATCH_LISTS_MAX_CAP = 1 << 16
+
+
+def solve_batch_lists(rate, nxt, hops=None, *, items=None, cap=None, device=-1, count_updates=False):
+    """solve_batch over the whole pivot range and, in the same call, the reference's exact `_path` lists
+    (fwx_solve_batch_lists_f64 / _f32): rate.shape == (count, n, n), nxt required, arrays solved in place.
+
+    items: (mat, src, dst) -- three equally long int32 sequences, item q asks for list (src[q], dst[q]) of matrix
+    mat[q]; None means all n * n pairs of every matrix, in the order (b, i, j).
+    cap: entries per list.  None: start at BATCH_LISTS_FIRST_CAP and, while an item reports
+    FWX_ERR_CAPACITY, double it and ask again for the items that did not fit (the batch is solved again from a
+    kept copy of the input), up to BATCH_LISTS_MAX_CAP; a list longer than that raises FwxError.  With
+    an explicit cap a list that does not fit raises FwxError at once, as does an item outside the batch.
+
+    Returns the lists as a list of tuples, one per item -- or (lists, U) with U the per-matrix uint64 array if
+    count_updates."""
+    if nxt is None:
+        raise ValueError("the exact lists need next")
+    if not (isinstance(rate, np.ndarray) and rate.ndim == 3 and rate.shape[1] == rate.shape[2]):
+        raise ValueError("rate must be a numpy array of shape (count, n, n)")
+    if rate.dtype not in (np.float32, np.float64) or not rate.flags.c_contiguous:
+        raise ValueError("rate must be C-contiguous float32 or float64")
+    for name, a in (("next", nxt), ("hops", hops)):
+        if a is not None and not (isinstance(a, np.ndarray) and a.shape == rate.shape
+                                  and a.dtype == np.int32 and a.flags.c_contiguous):
+            raise ValueError("%s must be a C-contiguous int32 array shaped like rate" % name)
+    count, n = rate.shape[0], rate.shape[1]
+    if items is None:
+        b, i, j = np.meshgrid(np.arange(count, dtype=np.int32), np.arange(n, dtype=np.int32),
+                              np.arange(n, dtype=np.int32), indexing="ij")
+        items = (b.reshape(-1), i.reshape(-1), j.reshape(-1))
+    mat, src, dst = (np.ascontiguousarray(a, dtype=np.int32) for a in items)
+    if not (mat.ndim == 1 and mat.shape == src.shape == dst.shape):
+        raise ValueError("items must be three equally long one-dimensional sequences (mat, src, dst)")
+    fn = lib().fwx_solve_batch_lists_f64 if rate.dtype == np.float64 else lib().fwx_solve_batch_lists_f32
+    grow = cap is None
+    cap = BATCH_LISTS_FIRST_CAP if grow else int(cap)
+    kept = (rate.copy(), nxt.copy(), None if hops is None else hops.copy()) if grow else None
+    each = np.zeros(count, dtype=np.uint64) if count_updates else None
+    o, _ = _opts(device, FWX_ENGINE_AUTO)
+    out = [None] * len(mat)
+    todo = np.arange(len(mat))
+    arrays = (rate, nxt, hops)
+    while True:
+        lens = np.empty(len(todo), dtype=np.int32)
+        paths = np.empty((len(todo), cap), dtype=np.int32)
+        m, s, d = (np.ascontiguousarray(a[todo]) for a in (mat, src, dst))
+        check(fn(count, n, _np_ptr(arrays[0]), _np_ptr(arrays[1]), _np_ptr(arrays[2]),
+                 _np_ptr(each) if arrays[0] is rate else None, len(todo), _np_ptr(m), _np_ptr(s), _np_ptr(d),
+                 _np_ptr(lens), _np_ptr(paths), cap, ctypes.byref(o)), "fwx_solve_batch_lists")
+        if count == 0 or n == 0:
+            lens[:] = _lib.FWX_ERR_INVALID       # nothing was solved: no item lies in the batch
+        short = lens == _lib.FWX_ERR_CAPACITY
+        bad = (lens < 0) & ~short
+        if bad.any():
+            raise FwxError(int(lens[bad][0]), "fwx_solve_batch_lists: item %d" % int(todo[bad][0]))
+        for q in np.nonzero(~short)[0]:
+            out[todo[q]] = tuple(int(v) for v in paths[q, :lens[q]])
+        if not short.any():
+            break
+        if not grow or cap >= BATCH_LISTS_MAX_CAP:
+            raise FwxError(_lib.FWX_ERR_CAPACITY, "fwx_solve_batch_lists: item %d does not fit cap %d"
+                           % (int(todo[short][0]), cap))
+        cap, todo = min(2 * cap, BATCH_LISTS_MAX_CAP), todo[short]
+        arrays = tuple(None if a is None else a.copy() for a in kept)     # solved again from the input
+    return (out, each) if count_updates else out
+
+
+def _trace_of(trace, need):
+    for t in (trace.last, trace.at_col, trace.at_row):
+        assert t.is_cuda and t.is_contiguous() and _dtype_name(t) == "int32" and t.numel() >= need
+    return ctypes.byref(trace.c_struct())
+
+
+def dev_solve_batch_traced(rate_t, count, n, trace, *, next_t, hops_t=None, stride=None, updates_t=None,
+                           stream=None):
+    """fwx_dev_solve_batch_traced: dev_solve_batch over the whole pivot range that also writes the path trace of
+    every matrix to `trace` (an object with last / at_col / at_row device int32 arrays, e.g. Trace), laid out like
+    next_t: matrix b at element b * stride, pitch n.  Every cell inside a matrix is written, the gaps never."""
+    stride = n * n if stride is None else int(stride)
+    need = (count - 1) * stride + n * n if count > 0 else 0
+    assert rate_t.is_cuda and rate_t.is_contiguous() and rate_t.numel() >= need
+    for t in (next_t, hops_t):
+        assert t is None or (t.is_cuda and t.is_contiguous() and _dtype_name(t) == "int32"
+                             and t.numel() >= need)
+    assert next_t is not None
+    assert updates_t is None or (updates_t.element_size() == 8 and updates_t.numel() >= count)
+    vp = ctypes.c_void_p
+    check(lib().fwx_dev_solve_batch_traced(
+        count, n, _tensor_dtype_code(rate_t), vp(rate_t.data_ptr()), vp(next_t.data_ptr()),
+        vp(hops_t.data_ptr()) if hops_t is not None else None, stride, _trace_of(trace, need),
+        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)),
+        "fwx_dev_solve_batch_traced")
+
+
+def dev_exact_paths_batch(next0_t, count, n, trace, mat_t, src_t, dst_t, cap, *, stride=None, stream=None):
+    """fwx_dev_exact_paths_batch: the exact `_path` lists of the items (mat_t[q], src_t[q], dst_t[q]) of a batch that
+    dev_solve_batch_traced solved; next0_t is the caller's copy of the UNSOLVED next-hop array (same layout).
+    Asynchronous on `stream`.  Returns (len_t, path_t): device int32 arrays of shape (items,) and (items, cap);
+    len_t[q] is the length of list q, FWX_ERR_CAPACITY or FWX_ERR_INVALID, item by item."""
+    stride = n * n if stride is None else int(stride)
+    need = (count - 1) * stride + n * n if count > 0 else 0
+    assert next0_t.is_cuda and next0_t.is_contiguous() and _dtype_name(next0_t) == "int32" and next0_t.numel() >= need
+    items = mat_t.numel()
+    for t in (mat_t, src_t, dst_t):
+        assert t.is_cuda and t.is_contiguous() and _dtype_name(t) == "int32" and t.numel() == items
+    len_t = _empty_like_device(mat_t, (items,), "int32")
+    path_t = _empty_like_device(mat_t, (items, cap), "int32")
+    scratch = _empty_like_device(mat_t, (max(items * 3 * (n + 2), 1),), "int32")
+    vp = ctypes.c_void_p
+    check(lib().fwx_dev_exact_paths_batch(
+        count, n, stride, vp(next0_t.data_ptr()), _trace_of(trace, need), items, vp(mat_t.data_ptr()),
+        vp(src_t.data_ptr()), vp(dst_t.data_ptr()), vp(len_t.data_ptr()), vp(path_t.data_ptr()), cap,
+        vp(scratch.data_ptr()), _stream_ptr(stream, mat_t)), "fwx_dev_exact_paths_batch")
+    if not _is_torch(mat_t):
+        len_t._scratch = scratch              # stays alive until the results are read
+    return len_t, path_t
 
 
 def solve_multi(rate, nxt=None, hops=None, *, devices=(0,), exchange=FWX_XCHG_AUTO,

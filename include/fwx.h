@@ -181,6 +181,61 @@ int fwx_dev_solve_batch(int32_t count, int32_t n, int32_t dtype, void *rate, int
 /* TEST HOOK: what FWX_BATCH_WAVE_MAX_N parses to right now.  Needs no device.  Not for production use. */
 int fwx_test_batch_wave_max_n(void);
 
+/* ---- batched small solves with the exact `_path` lists ----------------------------------------------------
+ * The reference returns, per entry, the list it concatenated when the entry last improved (`_path`,
+ * Algorithms.hs:55; see "Exact `_path` lists" below): under exact ties -- its 1.0 edges between the same currency
+ * on two exchanges make them the normal case -- that is not the walk of the final next-hops.  The traced batch
+ * solve keeps, per matrix, the three int32 arrays of the path trace (fwx_trace: last, at_col, at_row), laid out
+ * like next: matrix b at + b*stride, pitch n.  The solve writes every cell of the n x n part of each array (the
+ * caller need not initialise them) and never the gap.  Whole pivot range only; next is required, hops optional.
+ * fwx_dev_exact_paths_batch then rebuilds the lists of `items` triples (mat[q], src[q], dst[q]) from the trace and
+ * from next0, the caller's copy of the UNSOLVED next-hop array of the batch (same layout; fwx_dev_follow_paths
+ * takes the unsolved edge rates in the same way): one thread per item.  len_out[q] is the length of list q,
+ * FWX_ERR_CAPACITY when that list is longer than cap, FWX_ERR_INVALID for an item with mat outside [0, count) or
+ * src / dst outside [0, n) -- item by item, the other items are answered; path_out + q*cap receives list q.
+ * Capacity, as for fwx_matrix_query_exact: a list of L entries is returned whenever cap >= L, and
+ * FWX_ERR_CAPACITY exactly when L > cap.  An empty list (length 0) fits any cap >= 1.  The walk's stack is sized by
+ * n and never by cap: scratch holds items * FWX_EXACT_SCRATCH_INTS(n) int32.
+ * Domain: there is no domain check and no routing: a batch may mix matrices inside and outside the domain, and
+ * every list equals the reference's.
+ * Both device forms run on caller-owned DEVICE memory (the item arrays and outputs included), asynchronously on
+ * `stream`; they allocate nothing and synchronise nothing.  Tier choice by FWX_BATCH_WAVE_MAX_N as above.
+ *
+ * fwx_solve_batch_lists_f64 / _f32: HOST arrays.  What fwx_solve_batch_* does over the whole pivot range -- the
+ * arrays solved in place, updates_each, opts->updates_out -- and in the same call the lists of `items` triples
+ * (host arrays; len_out and path_out as above).  items == 0 is a plain whole-range batch solve.  The unsolved
+ * next-hops and the trace stay on the device in the pooled per-call context; the items are walked in chunks so that
+ * the lists, stacks and item arrays of one launch stay within 64 MiB of device memory.
+ * FWX_BATCH_LISTS_CHUNK (environment, read per call; digits only, >= 1, anything else means the default): items per
+ * launch, where that is fewer than the budget allows -- for tests and A/B runs.  No result depends on it.
+ *
+ * Statuses, all decided before any device call.  FWX_ERR_INVALID: count, n or items negative; rate, next or
+ * trace (or one of its three pointers; device forms) NULL; hops without next; stride < n*n; cap < 1 with
+ * items > 0; a NULL item array, output or scratch with items > 0; a bad struct_size; a pivot range in opts other
+ * than the whole one.  FWX_ERR_UNSUPPORTED: n > FWX_BATCH_MAX_N, or an engine other than FWX_ENGINE_AUTO.
+ * count == 0 or n == 0: FWX_OK, nothing is touched.  Then FWX_ERR_NO_DEVICE without a device, the arrays
+ * untouched.                                                                                              */
+struct fwx_trace;
+int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                               int64_t stride, const struct fwx_trace *trace,
+                               unsigned long long *d_updates_each, void *stream);
+#define FWX_EXACT_SCRATCH_INTS(n) (3 * ((n) + 2))        /* per item */
+int fwx_dev_exact_paths_batch(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                              const struct fwx_trace *trace, int32_t items, const int32_t *mat,
+                              const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                              int32_t cap, int32_t *scratch, void *stream);
+int fwx_solve_batch_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              const fwx_opts *opts);
+int fwx_solve_batch_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              const fwx_opts *opts);
+/* TEST HOOK: items per launch of fwx_solve_batch_lists_* for order n and capacity cap, as FWX_BATCH_LISTS_CHUNK and
+ * the budget give it right now (FWX_ERR_INVALID for n < 0 or cap < 1).  Needs no device.  Not for production use. */
+int64_t fwx_test_batch_lists_chunk(int32_t n, int32_t cap);
+
 /* Index form of the `_path` list that optimum returns (Algorithms.hs:74-75): follow next-hops
  * from src until dst.  Returns the number of vertices written to out (dst included, src not), 0 if
  * next[src][dst] == -1 (empty path, "no exchange"), or a negative fwx_status.  Host arrays.      */
