@@ -514,6 +514,59 @@ int dev_solve_batch(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *h
     return FWX_OK;
 }
 
+// Ragged batches (fwx_solve_ragged_*): what the orders alone decide.  FWX_ERR_INVALID for a negative order;
+// n_max is the largest order, whatever it is -- the caller compares it with FWX_BATCH_MAX_N.
+int ragged_orders(int32_t count, const int32_t *n_each, int32_t &n_max)
+{
+    n_max = 0;
+    for (int32_t b = 0; b < count; ++b) {
+        if (n_each[b] < 0) return FWX_ERR_INVALID;
+        n_max = std::max(n_max, n_each[b]);
+    }
+    return FWX_OK;
+}
+
+// fwx_ragged_plan for orders that ragged_orders accepted and that are all <= FWX_BATCH_MAX_N: the packed offsets
+// (count + 1 entries), the matrices with n >= 1 grouped by tier -- wave (n <= wave_max_n), 64-wide, 128-wide -- and
+// within a tier by descending order, ties by ascending index (a counting sort over the orders: the tier is monotone
+// in the order), the rest of `order` -1.  Any output may be null.
+void ragged_plan(int32_t count, const int32_t *n_each, int wave_max_n, int64_t *offset, int32_t *order,
+                 int32_t tier_count[3])
+{
+    auto tier_of = [&](int n) { return n <= wave_max_n ? 0 : n <= 64 ? 1 : 2; };
+    int64_t at[FWX_BATCH_MAX_N + 2] = {0};      // at[n]: matrices of order n, then where the next one of order n goes
+    int32_t tiers[3] = {0, 0, 0};
+    int64_t cells = 0;
+    for (int32_t b = 0; b < count; ++b) {
+        const int n = n_each[b];
+        if (offset) offset[b] = cells;
+        cells += (int64_t)n * n;
+        if (n >= 1) { ++at[n]; ++tiers[tier_of(n)]; }
+    }
+    if (offset) offset[count] = cells;
+    if (tier_count) { tier_count[0] = tiers[0]; tier_count[1] = tiers[1]; tier_count[2] = tiers[2]; }
+    if (!order) return;
+    int64_t pos = 0;
+    for (int tier = 0; tier < 3; ++tier)
+        for (int n = FWX_BATCH_MAX_N; n >= 1; --n)
+            if (tier_of(n) == tier) { const int64_t c = at[n]; at[n] = pos; pos += c; }
+    for (int32_t b = 0; b < count; ++b)
+        if (n_each[b] >= 1) order[at[n_each[b]]++] = b;
+    for (int64_t i = pos; i < count; ++i) order[i] = -1;
+}
+
+template <typename T>
+int dev_solve_ragged(int32_t count, T *rate, int32_t *next, int32_t *hops, const int32_t *d_n_each,
+                     const int64_t *d_offset, const int32_t *d_order, const int32_t tier_count[3],
+                     unsigned long long *d_updates_each, hipStream_t s, const fwx::PathLog &plog = fwx::PathLog())
+{
+    const hipError_t e = fwx::launch_ragged_solve<T>(rate, next, hops, count, d_n_each, d_offset, d_order, tier_count,
+                                                     d_updates_each, s, plog);
+    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
+    FWX_HIP(e);
+    return FWX_OK;
+}
+
 // What fwx_solve_batch_lists_* adds to a batch solve: the exact lists of `items` triples, host arrays.
 struct BatchLists {
     int32_t items;
@@ -526,12 +579,21 @@ struct BatchLists {
 // padding (the batch kernels load scalars), the arrays of the batch back to back on the device.
 // ls (fwx_solve_batch_lists_*): the solve also keeps the unsolved next-hops and the path trace in the context
 // and walks the items' lists from them, batch_lists_chunk items per launch.
+// ragged (fwx_solve_ragged_*, fwx_solve_ragged_lists_*): matrix b has order n_each[b] and the batch is packed, matrix
+// b at the sum of the squares before it; the n passed in is ignored and stands for the largest order from then on
+// (the walk's stacks and chunks are sized by it).  Whole pivot range only.  The plan -- offsets, orders, the tier
+// list -- is built here and goes to the context's workspace behind the counters, in one copy.
 template <typename T>
 int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
-                     const fwx_opts *o, const BatchLists *ls = nullptr)
+                     const fwx_opts *o, const BatchLists *ls = nullptr, bool ragged = false,
+                     const int32_t *n_each = nullptr)
 {
-    if (count < 0 || n < 0 || (ls && ls->items < 0)) return FWX_ERR_INVALID;
-    if (count == 0 || n == 0) return FWX_OK;
+    if (count < 0 || (!ragged && n < 0) || (ls && ls->items < 0)) return FWX_ERR_INVALID;
+    if (count == 0 || (!ragged && n == 0)) return FWX_OK;
+    if (ragged) {
+        if (!n_each || ragged_orders(count, n_each, n)) return FWX_ERR_INVALID;
+        if (n == 0) return FWX_OK;
+    }
     if (!rate || (hops && !next)) return FWX_ERR_INVALID;
     if (ls && (!next || (ls->items > 0 && (ls->cap < 1 || !ls->mat || !ls->src || !ls->dst || !ls->len_out ||
                                            !ls->path_out))))
@@ -540,12 +602,25 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     int rc = read_opts(o, n, op);
     if (rc) return rc;
     if (ls && (op.k_begin != 0 || op.k_end != n)) return FWX_ERR_INVALID;      // the trace covers whole solves only
+    if (ragged && o && (o->k_begin != 0 || o->k_end > 0)) return FWX_ERR_INVALID;   // one range does not fit all orders
     if ((rc = batch_range(n, op.k_begin, op.k_end))) return rc;
     if (op.engine != FWX_ENGINE_AUTO) return FWX_ERR_UNSUPPORTED;
     DeviceGuard g;
     if ((rc = g.enter(op.device))) return rc;
 
-    const size_t cells = (size_t)count * (size_t)n * (size_t)n;
+    // the ragged plan, packed for one copy: count offsets, then count orders and the tier list (count) as int32
+    std::vector<int64_t> plan;
+    int32_t tiers[3] = {0, 0, 0};
+    size_t cells = (size_t)count * (size_t)n * (size_t)n;
+    if (ragged) {
+        std::vector<int64_t> offs((size_t)count + 1);
+        plan.resize(2 * (size_t)count);
+        int32_t *h_n = (int32_t *)(plan.data() + count), *h_order = h_n + count;
+        ragged_plan(count, n_each, batch_wave_max_n(), offs.data(), h_order, tiers);
+        std::copy(offs.begin(), offs.end() - 1, plan.begin());
+        std::copy(n_each, n_each + count, h_n);
+        cells = (size_t)offs[(size_t)count];
+    }
     const bool counting = updates_each || op.updates_out;
     CtxLease lease;
     if ((rc = lease.open())) return rc;
@@ -560,11 +635,24 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     fail_point();
     if (hops && (rc = cx.reserve(CallCtx::HOPS, cells * sizeof(int32_t), &d_hops))) return rc;
     std::vector<unsigned long long> h_upd;
-    if (counting) {                              // one counter per matrix: the context's workspace
+    const size_t b_upd = counting ? (size_t)count * sizeof(unsigned long long) : 0;
+    const int64_t *d_offset = nullptr;
+    const int32_t *d_n_each = nullptr, *d_order = nullptr;
+    if (counting || ragged) {                    // one counter per matrix, then the plan: the context's workspace
         fail_point();
-        h_upd.resize((size_t)count);
-        if ((rc = cx.reserve(CallCtx::WS, (size_t)count * sizeof(unsigned long long), &d_upd))) return rc;
-        FWX_HIP(hipMemsetAsync(d_upd, 0, (size_t)count * sizeof(unsigned long long), s));
+        void *ws = nullptr;
+        if ((rc = cx.reserve(CallCtx::WS, b_upd + plan.size() * sizeof(int64_t), &ws))) return rc;
+        if (counting) {
+            h_upd.resize((size_t)count);
+            d_upd = ws;
+            FWX_HIP(hipMemsetAsync(d_upd, 0, b_upd, s));
+        }
+        if (ragged) {
+            d_offset = (const int64_t *)((char *)ws + b_upd);
+            d_n_each = (const int32_t *)(d_offset + count);
+            d_order = d_n_each + count;
+            FWX_HIP(hipMemcpyAsync((void *)d_offset, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        }
     }
 
     // pinned staging while the whole batch fits (see solve_host), straight copies above
@@ -606,9 +694,13 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
         FWX_HIP(hipMemcpyAsync(d_next0, d_next, b_idx, hipMemcpyDeviceToDevice, s));
     }
 
-    if ((rc = dev_solve_batch<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
-                                 op.k_begin, op.k_end, (unsigned long long *)d_upd, s, plog)))
-        return rc;
+    if (ragged)
+        rc = dev_solve_ragged<T>(count, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, d_n_each, d_offset, d_order,
+                                 tiers, (unsigned long long *)d_upd, s, plog);
+    else
+        rc = dev_solve_batch<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
+                                op.k_begin, op.k_end, (unsigned long long *)d_upd, s, plog);
+    if (rc) return rc;
 
     FWX_HIP(hipMemcpyAsync(staged ? (void *)st_rate : (void *)rate, d_rate, b_rate, hipMemcpyDeviceToHost, s));
     if (next) FWX_HIP(hipMemcpyAsync(staged ? (void *)st_next : (void *)next, d_next, b_idx, hipMemcpyDeviceToHost, s));
@@ -622,9 +714,13 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
         FWX_HIP(hipMemcpyAsync(d_mat, ls->mat + q0, c * 4, hipMemcpyHostToDevice, s));
         FWX_HIP(hipMemcpyAsync(d_src, ls->src + q0, c * 4, hipMemcpyHostToDevice, s));
         FWX_HIP(hipMemcpyAsync(d_dst, ls->dst + q0, c * 4, hipMemcpyHostToDevice, s));
-        if ((rc = fwxi::launch_exact_batch(count, n, (long long)n * n, d_next0, plog, (int)c, d_mat, d_src, d_dst,
-                                           d_len, d_paths, ls->cap, d_stacks, s)))
-            return rc;
+        if (ragged)
+            rc = fwxi::launch_exact_ragged(count, d_n_each, d_offset, n, d_next0, plog, (int)c, d_mat, d_src, d_dst,
+                                           d_len, d_paths, ls->cap, d_stacks, s);
+        else
+            rc = fwxi::launch_exact_batch(count, n, (long long)n * n, d_next0, plog, (int)c, d_mat, d_src, d_dst,
+                                          d_len, d_paths, ls->cap, d_stacks, s);
+        if (rc) return rc;
         FWX_HIP(hipMemcpyAsync(ls->len_out + q0, d_len, c * 4, hipMemcpyDeviceToHost, s));
         FWX_HIP(hipMemcpyAsync(ls->path_out + (size_t)q0 * cap, d_paths, c * cap * 4, hipMemcpyDeviceToHost, s));
     }
@@ -798,6 +894,19 @@ __global__ __launch_bounds__(64) void exact_paths_kernel(EntryTab t, int n_real,
                              stacks + (size_t)qi * 3 * exact_stack_triples(n_real), cap);
 }
 
+// One list of the order-n matrix that starts at element `off` of the four arrays of a traced batch, pitch n.
+__device__ __forceinline__ int walk_batch_item(size_t off, int n, const int32_t *next0, const fwx::PathLog &plog,
+                                               int src, int dst, int32_t *out, int32_t *stack, int cap)
+{
+    BatchTab t;
+    t.n = n;
+    t.last = plog.last + off;
+    t.at_col = plog.at_col + off;
+    t.at_row = plog.at_row + off;
+    t.next0 = next0 + off;
+    return exact_walk(t, n, src, dst, out, stack, cap);
+}
+
 // The same over a traced batch (fwx_dev_exact_paths_batch): item q is (mat[q], src[q], dst[q]), matrix m of the
 // batch at + m*stride in each of the four arrays, pitch n.  An item outside the batch gets FWX_ERR_INVALID, alone.
 __global__ __launch_bounds__(64) void exact_paths_batch_kernel(int count, int n, long long stride,
@@ -810,15 +919,8 @@ __global__ __launch_bounds__(64) void exact_paths_batch_kernel(int count, int n,
     if (qi >= items) return;
     const int m0 = mat[qi], s0 = src[qi], d0 = dst[qi];
     if (m0 < 0 || m0 >= count || s0 < 0 || d0 < 0 || s0 >= n || d0 >= n) { len_out[qi] = FWX_ERR_INVALID; return; }
-    const size_t off = (size_t)m0 * (size_t)stride;
-    BatchTab t;
-    t.n = n;
-    t.last = plog.last + off;
-    t.at_col = plog.at_col + off;
-    t.at_row = plog.at_row + off;
-    t.next0 = next0 + off;
-    len_out[qi] = exact_walk(t, n, s0, d0, paths + (size_t)qi * cap, stacks + (size_t)qi * 3 * exact_stack_triples(n),
-                             cap);
+    len_out[qi] = walk_batch_item((size_t)m0 * (size_t)stride, n, next0, plog, s0, d0, paths + (size_t)qi * cap,
+                                  stacks + (size_t)qi * 3 * exact_stack_triples(n), cap);
 }
 
 int launch_exact_batch(int count, int n, long long stride, const int32_t *next0, const fwx::PathLog &plog,
@@ -828,6 +930,37 @@ int launch_exact_batch(int count, int n, long long stride, const int32_t *next0,
     if (items <= 0) return FWX_OK;
     hipLaunchKernelGGL(exact_paths_batch_kernel, dim3((unsigned)(((size_t)items + 63) / 64)), dim3(64), 0, s, count,
                        n, stride, next0, plog, items, mat, src, dst, paths, stacks, cap, len_out);
+    FWX_HIP(hipGetLastError());
+    return FWX_OK;
+}
+
+// The same over a traced ragged batch (fwx_dev_exact_paths_ragged): matrix m has its own order n_each[m] and starts
+// at offset[m].  src / dst are checked against the order of the item's OWN matrix; an order-0 matrix has no valid
+// item.  The stacks are spaced by n_max, so an order above it (a plan that does not belong here) is refused too.
+__global__ __launch_bounds__(64) void exact_paths_ragged_kernel(int count, const int32_t *n_each,
+                                                                const int64_t *offset, int n_max,
+                                                                const int32_t *next0, fwx::PathLog plog, int items,
+                                                                const int32_t *mat, const int32_t *src,
+                                                                const int32_t *dst, int32_t *paths, int32_t *stacks,
+                                                                int cap, int32_t *len_out)
+{
+    const int qi = blockIdx.x * 64 + threadIdx.x;
+    if (qi >= items) return;
+    const int m0 = mat[qi], s0 = src[qi], d0 = dst[qi];
+    if (m0 < 0 || m0 >= count) { len_out[qi] = FWX_ERR_INVALID; return; }
+    const int n = n_each[m0];
+    if (n > n_max || s0 < 0 || d0 < 0 || s0 >= n || d0 >= n) { len_out[qi] = FWX_ERR_INVALID; return; }
+    len_out[qi] = walk_batch_item((size_t)offset[m0], n, next0, plog, s0, d0, paths + (size_t)qi * cap,
+                                  stacks + (size_t)qi * 3 * exact_stack_triples(n_max), cap);
+}
+
+int launch_exact_ragged(int count, const int32_t *n_each, const int64_t *offset, int n_max, const int32_t *next0,
+                        const fwx::PathLog &plog, int items, const int32_t *mat, const int32_t *src,
+                        const int32_t *dst, int32_t *len_out, int32_t *paths, int cap, int32_t *stacks, hipStream_t s)
+{
+    if (items <= 0) return FWX_OK;
+    hipLaunchKernelGGL(exact_paths_ragged_kernel, dim3((unsigned)(((size_t)items + 63) / 64)), dim3(64), 0, s, count,
+                       n_each, offset, n_max, next0, plog, items, mat, src, dst, paths, stacks, cap, len_out);
     FWX_HIP(hipGetLastError());
     return FWX_OK;
 }
@@ -1265,6 +1398,108 @@ int fwx_solve_batch_lists_f32(int32_t count, int32_t n, float *rate, int32_t *ne
 int64_t fwx_test_batch_lists_chunk(int32_t n, int32_t cap)
 {
     return n < 0 || cap < 1 ? (int64_t)FWX_ERR_INVALID : (int64_t)batch_lists_chunk(n, cap);
+}
+
+int fwx_ragged_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
+                    int32_t tier_count_out[3])
+{
+    return fwxi::guarded([&]() -> int {
+        int32_t n_max = 0;
+        if (count < 0 || (count > 0 && !n_each) || ragged_orders(count, n_each, n_max)) return FWX_ERR_INVALID;
+        if (n_max > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
+        ragged_plan(count, n_each, batch_wave_max_n(), offset_out, order_out, tier_count_out);
+        return FWX_OK;
+    });
+}
+
+int fwx_solve_ragged_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                         uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<double>(count, 0, rate, next, hops, updates_each, opts, nullptr, true, n_each);
+    });
+}
+
+int fwx_solve_ragged_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                         uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<float>(count, 0, rate, next, hops, updates_each, opts, nullptr, true, n_each);
+    });
+}
+
+int fwx_solve_ragged_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                               const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                               const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<double>(count, 0, rate, next, hops, updates_each, opts, &ls, true, n_each);
+    });
+}
+
+int fwx_solve_ragged_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                               const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                               const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<float>(count, 0, rate, next, hops, updates_each, opts, &ls, true, n_each);
+    });
+}
+
+// The device forms cannot read the orders: what they can decide is decided from the host arguments, and the kernels
+// leave a matrix alone whose order does not fit the tier it is listed in.
+int fwx_dev_solve_ragged(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                         const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                         const int32_t tier_count[3], const fwx_trace *trace, unsigned long long *d_updates_each,
+                         void *stream)
+{
+    return fwxi::guarded([&]() -> int {
+        if (count < 0 || !tier_count || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
+        const int64_t listed = (int64_t)tier_count[0] + tier_count[1] + tier_count[2];
+        if (tier_count[0] < 0 || tier_count[1] < 0 || tier_count[2] < 0 || listed > count) return FWX_ERR_INVALID;
+        if (listed == 0) return FWX_OK;
+        if (!rate || !d_n_each || !d_offset || !d_order || (hops && !next)) return FWX_ERR_INVALID;
+        if (trace && (!next || !trace->last || !trace->at_col || !trace->at_row)) return FWX_ERR_INVALID;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        fwx::PathLog plog;
+        if (trace) {
+            plog.last = trace->last;
+            plog.at_col = trace->at_col;
+            plog.at_row = trace->at_row;
+        }
+        hipStream_t s = (hipStream_t)stream;
+        if (dtype == FWX_F64)
+            return dev_solve_ragged<double>(count, (double *)rate, next, hops, d_n_each, d_offset, d_order, tier_count,
+                                            d_updates_each, s, plog);
+        return dev_solve_ragged<float>(count, (float *)rate, next, hops, d_n_each, d_offset, d_order, tier_count,
+                                       d_updates_each, s, plog);
+    });
+}
+
+int fwx_dev_exact_paths_ragged(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                               const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
+                               const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                               int32_t cap, int32_t *scratch, void *stream)
+{
+    return fwxi::guarded([&]() -> int {
+        if (count < 0 || n_max < 0 || items < 0) return FWX_ERR_INVALID;
+        if (count == 0 || n_max == 0 || items == 0) return FWX_OK;
+        if (!d_n_each || !d_offset || !next0 || !trace || !trace->last || !trace->at_col || !trace->at_row ||
+            cap < 1 || !mat || !src || !dst || !len_out || !path_out || !scratch)
+            return FWX_ERR_INVALID;
+        if (n_max > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        fwx::PathLog plog;
+        plog.last = trace->last;
+        plog.at_col = trace->at_col;
+        plog.at_row = trace->at_row;
+        return launch_exact_ragged(count, d_n_each, d_offset, n_max, next0, plog, items, mat, src, dst, len_out,
+                                   path_out, cap, scratch, (hipStream_t)stream);
+    });
 }
 
 int fwx_follow_path(int32_t n, const int32_t *next, int32_t src, int32_t dst, int32_t *out,

@@ -149,6 +149,17 @@ hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, 
                               int k_begin, int k_end, unsigned long long *updates_each, int wave_max_n,
                               hipStream_t s, PathLog plog = PathLog());
 
+// Ragged batch: `count` matrices of different orders, matrix id of order n_each[id] <= FWX_SMALL_N at element
+// offset[id] of rate (next / hops / the trace arrays alike), pitch n_each[id]; whole pivot range of each.  The three
+// index arrays are DEVICE arrays; order / tier_count (host) are what fwx_ragged_plan gives: the matrices grouped by
+// tier (wave, 64-wide, 128-wide workgroup).  Up to three launches on s, the 128-wide tier first, each chunked at
+// 2^21 workgroups; an empty tier launches nothing.  Nothing outside the n x n cells of a matrix is read or written.
+// updates_each: count counters or nullptr, counter id is incremented by U of matrix id.  plog as above.
+template <typename T>
+hipError_t launch_ragged_solve(T *rate, int32_t *next, int32_t *hops, int count, const int32_t *n_each,
+                               const int64_t *offset, const int32_t *order, const int32_t tier_count[3],
+                               unsigned long long *updates_each, hipStream_t s, PathLog plog = PathLog());
+
 template <typename T>
 hipError_t launch_snapshot_row(T *dst, const T *src, int32_t *hdst, const int32_t *hsrc, int n,
                                hipStream_t s);

@@ -908,19 +908,19 @@ __global__ __launch_bounds__(M * RG) void small_solve_batch(T *rate, int32_t *ne
 // and column k are fixed points of step k (their row / column operand is NaN), so hd of these entries does not
 // change inside the step and "the start of step k" is anywhere in it: the stores are issued at the top,
 // before the cross-lane reads, and drain behind them.  `last` is stored with the results.
+//
+// The body is shared by two kernels: wave_solve_batch (wave b on matrix b, at b*stride) and wave_solve_ragged (the
+// wave tier of the ragged batch: its own order and offset per wave).  n is wave-uniform in both; the matrix is at
+// + base in all arrays, its U goes to updates[b].
 // -------------------------------------------------------------------------------------------------
 template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
-__global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
-                                                        long long stride, int count, int k_begin,
-                                                        int k_end, unsigned long long *updates, PathLog plog)
+__device__ __forceinline__ void wave_solve_body(T *rate, int32_t *next, int32_t *hops, int n, size_t base,
+                                                long long b, int k_begin, int k_end,
+                                                unsigned long long *updates, PathLog plog)
 {
     constexpr int E = 4;                      // rows per lane: q, q + 4, q + 8, q + 12
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const long long b = (long long)blockIdx.x * 4 + wave;
-    if (b >= count) return;                   // wave-uniform
     const int c = lane & 15, q = lane >> 4;
-    const size_t base = (size_t)b * (size_t)stride;
 
     T x[E];
     int32_t nx[E], hp[E], hd[LOG ? E : 1];
@@ -1006,6 +1006,64 @@ __global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, 
     if (updates && mine && lane == 0) atomicAdd(&updates[b], (unsigned long long)mine);
 }
 
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
+__global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
+                                                        long long stride, int count, int k_begin,
+                                                        int k_end, unsigned long long *updates, PathLog plog)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const long long b = (long long)blockIdx.x * 4 + wave;
+    if (b >= count) return;                   // wave-uniform
+    wave_solve_body<T, HAS_NEXT, HAS_HOPS, LOG>(rate, next, hops, n, (size_t)b * (size_t)stride, b, k_begin, k_end,
+                                                updates, plog);
+}
+
+// -------------------------------------------------------------------------------------------------
+// Ragged batch: matrices of DIFFERENT orders in one call.  Matrix id has order n_each[id] and starts at element
+// offset[id] of rate (next, hops and the three trace arrays alike), pitch n_each[id]; U of matrix id is added to
+// updates[id].  `order` lists the matrices of ONE tier (fwx_ragged_plan groups them; the launcher passes the tier's
+// part of the list): launch item w takes matrix order[w].  Whole pivot range only.  Order and offset are read
+// through wave-uniform addresses (scalar loads), so n stays a scalar in both bodies: every row / pivot skip is
+// still a scalar test.  An id outside [0, count) or an order that does not fit the tier's tile (a plan that does not
+// belong to these arrays) makes the workgroup / wave leave before it touches memory or reaches a barrier.
+// -------------------------------------------------------------------------------------------------
+template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
+__global__ __launch_bounds__(M * RG) void small_solve_ragged(T *rate, int32_t *next, int32_t *hops, int count,
+                                                             const int32_t *n_each, const int64_t *offset,
+                                                             const int32_t *order, unsigned long long *updates,
+                                                             PathLog plog)
+{
+    const int id = order[blockIdx.x];
+    if ((unsigned)id >= (unsigned)count) return;              // workgroup-uniform, before any barrier
+    const int n = n_each[id];
+    if (n <= 0 || n > M) return;
+    const size_t off = (size_t)offset[id];
+    if constexpr (LOG) { plog.last += off; plog.at_col += off; plog.at_row += off; }
+    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(rate + off, HAS_NEXT ? next + off : nullptr,
+                                                        HAS_HOPS ? hops + off : nullptr, n, 0, n,
+                                                        updates ? updates + id : nullptr, plog);
+}
+
+// Wave tier: wave w of the launch (four per workgroup) on matrix order[w]; a wave past tier_count leaves at once.
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
+__global__ __launch_bounds__(256) void wave_solve_ragged(T *rate, int32_t *next, int32_t *hops, int count,
+                                                         const int32_t *n_each, const int64_t *offset,
+                                                         const int32_t *order, int tier_count,
+                                                         unsigned long long *updates, PathLog plog)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const long long w = (long long)blockIdx.x * 4 + wave;
+    if (w >= tier_count) return;              // wave-uniform
+    const int id = __builtin_amdgcn_readfirstlane(order[w]);
+    if ((unsigned)id >= (unsigned)count) return;
+    const int n = __builtin_amdgcn_readfirstlane(n_each[id]);
+    if (n <= 0 || n > FWX_BATCH_WAVE_N) return;
+    const int64_t off = offset[id];            // wave-uniform too: the base of every load and store of the body
+    const size_t base =((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) |
+                        (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)off);
+    wave_solve_body<T, HAS_NEXT, HAS_HOPS, LOG>(rate, next, hops, n, base, (long long)id, 0, n, updates, plog);
+}
+
 template <typename T>
 hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride,
                               int k_begin, int k_end, unsigned long long *updates_each, int wave_max_n,
@@ -1056,6 +1114,59 @@ template hipError_t launch_batch_solve<float>(float *, int32_t *, int32_t *, int
                                               unsigned long long *, int, hipStream_t, PathLog);
 template hipError_t launch_batch_solve<double>(double *, int32_t *, int32_t *, int, int, long long, int, int,
                                                unsigned long long *, int, hipStream_t, PathLog);
+
+template <typename T>
+hipError_t launch_ragged_solve(T *rate, int32_t *next, int32_t *hops, int count, const int32_t *n_each,
+                               const int64_t *offset, const int32_t *order, const int32_t tier_count[3],
+                               unsigned long long *updates_each, hipStream_t s, PathLog plog)
+{
+    const long long tiers[3] = {tier_count[0], tier_count[1], tier_count[2]};
+    if (count < 0 || tiers[0] < 0 || tiers[1] < 0 || tiers[2] < 0 || tiers[0] + tiers[1] + tiers[2] > count ||
+        (hops && !next))
+        return hipErrorInvalidValue;
+    if (tiers[0] + tiers[1] + tiers[2] == 0) return hipSuccess;
+    const bool lg = plog.last != nullptr;
+    if (!rate || !n_each || !offset || !order || (lg && (!next || !plog.at_col || !plog.at_row)))
+        return hipErrorInvalidValue;
+    constexpr int kChunk = 1 << 21;           // workgroups per launch, as launch_batch_solve
+#define FWX_RAGGED_WAVE(HN, HH, LG)                                                                \
+    hipLaunchKernelGGL((wave_solve_ragged<T, HN, HH, LG>), dim3((cnt + 3) / 4), dim3(256), 0, s, rate, next, hops, \
+                       count, n_each, offset, ord, cnt, updates_each, plog)
+#define FWX_RAGGED_WG(M, RG, HN, HH, LG)                                                           \
+    hipLaunchKernelGGL((small_solve_ragged<T, M, RG, HN, HH, LG>), dim3(cnt), dim3(M * RG), 0, s, rate, next, hops, \
+                       count, n_each, offset, ord, updates_each, plog)
+#define FWX_RAGGED_FIELDS(LAUNCH, ...)                                                             \
+    do {                                                                                           \
+        if (hops) { if (lg) LAUNCH(__VA_ARGS__ true, true, true); else LAUNCH(__VA_ARGS__ true, true, false); }   \
+        else if (next) { if (lg) LAUNCH(__VA_ARGS__ true, false, true); else LAUNCH(__VA_ARGS__ true, false, false); } \
+        else LAUNCH(__VA_ARGS__ false, false, false);                                              \
+    } while (0)
+    // the 128-wide tier first: its workgroups run longest
+    for (int tier = 2; tier >= 0; --tier) {
+        const long long first = tier == 2 ? tiers[0] + tiers[1] : tier == 1 ? tiers[0] : 0;
+        const long long per = tier == 0 ? 4LL * kChunk : kChunk;     // matrices per launch: four waves a workgroup
+        for (long long b0 = 0; b0 < tiers[tier]; b0 += per) {
+            const int cnt = (int)std::min<long long>(per, tiers[tier] - b0);
+            const int32_t *ord = order + first + b0;
+            if (tier == 0) FWX_RAGGED_FIELDS(FWX_RAGGED_WAVE);
+            else if (tier == 1) FWX_RAGGED_FIELDS(FWX_RAGGED_WG, 64, 16,);
+            else FWX_RAGGED_FIELDS(FWX_RAGGED_WG, 128, 8,);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+#undef FWX_RAGGED_FIELDS
+#undef FWX_RAGGED_WG
+#undef FWX_RAGGED_WAVE
+    return hipSuccess;
+}
+
+template hipError_t launch_ragged_solve<float>(float *, int32_t *, int32_t *, int, const int32_t *, const int64_t *,
+                                               const int32_t *, const int32_t *, unsigned long long *, hipStream_t,
+                                               PathLog);
+template hipError_t launch_ragged_solve<double>(double *, int32_t *, int32_t *, int, const int32_t *, const int64_t *,
+                                                const int32_t *, const int32_t *, unsigned long long *, hipStream_t,
+                                                PathLog);
 
 template <typename T>
 hipError_t launch_small_solve(T *rate, int32_t *next, int32_t *hops, int n, int k_begin, int k_end,

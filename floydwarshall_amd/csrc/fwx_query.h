@@ -95,6 +95,11 @@ int run_exact_batch(const EntryTab &tab, int n_real, hipStream_t s, int32_t coun
 int launch_exact_batch(int count, int n, long long stride, const int32_t *next0, const fwx::PathLog &plog,
                        int items, const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
                        int32_t *paths, int cap, int32_t *stacks, hipStream_t s);
+// The same over a traced ragged batch: matrix m of order n_each[m] at + offset[m] (device arrays), pitch n_each[m];
+// stacks: items * 3 * (n_max + 2) ints, n_max at least the largest order of the batch.
+int launch_exact_ragged(int count, const int32_t *n_each, const int64_t *offset, int n_max, const int32_t *next0,
+                        const fwx::PathLog &plog, int items, const int32_t *mat, const int32_t *src,
+                        const int32_t *dst, int32_t *len_out, int32_t *paths, int cap, int32_t *stacks, hipStream_t s);
 
 }  // namespace fwxi
 

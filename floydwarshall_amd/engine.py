@@ -18,7 +18,8 @@ from ._lib import (FWX_ENGINE_AUTO, FWX_ENGINE_FUSED, FWX_ENGINE_PERK, FWX_F32, 
                    FWX_ERR_RCCL, FwxError, FwxOpts, FwxPivots, FwxSlab, check, lib)
 
 __all__ = ["solve", "solve_batch", "dev_solve_batch", "solve_batch_lists", "dev_solve_batch_traced",
-           "dev_exact_paths_batch", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
+           "dev_exact_paths_batch", "ragged_plan", "solve_ragged", "solve_ragged_lists", "dev_solve_ragged",
+           "dev_exact_paths_ragged", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
            "dev_solve", "DeviceMatrix", "dev_relax", "dev_panel", "dev_panel_snap",
            "dev_relax_fused", "FusedWorkspace", "Trace", "FWX_FUSED_BLOCK", "device_count",
            "FwxError", "FWX_ENGINE_AUTO", "FWX_ENGINE_PERK", "FWX_ENGINE_FUSED",
@@ -263,6 +264,193 @@ def dev_exact_paths_batch(next0_t, count, n, trace, mat_t, src_t, dst_t, cap, *,
         count, n, stride, vp(next0_t.data_ptr()), _trace_of(trace, need), items, vp(mat_t.data_ptr()),
         vp(src_t.data_ptr()), vp(dst_t.data_ptr()), vp(len_t.data_ptr()), vp(path_t.data_ptr()), cap,
         vp(scratch.data_ptr()), _stream_ptr(stream, mat_t)), "fwx_dev_exact_paths_batch")
+    if not _is_torch(mat_t):
+        len_t._scratch = scratch              # stays alive until the results are read
+    return len_t, path_t
+
+
+def ragged_plan(n_each):
+    """fwx_ragged_plan: (offset, order, tier_count) for a ragged batch of the orders n_each -- the packed offsets
+    (int64, count + 1 entries, the total last), the matrices with n >= 1 grouped by tier (wave, 64-wide, 128-wide)
+    and by descending order within a tier (int32, count entries, -1 past the listed ones), and the three tier
+    sizes (int32).  Needs no device."""
+    n_each = np.ascontiguousarray(n_each, dtype=np.int32)
+    if n_each.ndim != 1:
+        raise ValueError("n_each must be a one-dimensional sequence of orders")
+    count = len(n_each)
+    offset = np.zeros(count + 1, dtype=np.int64)
+    order = np.full(count, -1, dtype=np.int32)
+    tiers = np.zeros(3, dtype=np.int32)
+    check(lib().fwx_ragged_plan(count, _np_ptr(n_each), _np_ptr(offset), _np_ptr(order), _np_ptr(tiers)),
+          "fwx_ragged_plan")
+    return offset, order, tiers
+
+
+def _pack_ragged(rates, nexts, hops):
+    """Checks a ragged batch given as sequences of square arrays and packs it: (n_each, rate, next, hops), the three
+    arrays one-dimensional with matrix b at the sum of the squares before it (next / hops None where not given)."""
+    rates = list(rates)
+    for r in rates:
+        if not (isinstance(r, np.ndarray) and r.ndim == 2 and r.shape[0] == r.shape[1]):
+            raise ValueError("every rate must be a square 2-D numpy array")
+    dtypes = {r.dtype for r in rates}
+    if len(dtypes) > 1:
+        raise ValueError("the matrices of a batch must have one dtype")
+    dtype = dtypes.pop() if dtypes else np.dtype(np.float64)
+    if dtype not in (np.float32, np.float64):
+        raise ValueError("rate must be float32 or float64")
+    if hops is not None and nexts is None:
+        raise ValueError("hops requires next")
+    packed = [np.concatenate([r.reshape(-1) for r in rates]) if rates else np.zeros(0, dtype=dtype)]
+    for name, seq in (("next", nexts), ("hops", hops)):
+        if seq is None:
+            packed.append(None)
+            continue
+        seq = list(seq)
+        if len(seq) != len(rates):
+            raise ValueError("%s must hold one array per matrix" % name)
+        for a, r in zip(seq, rates):
+            if not (isinstance(a, np.ndarray) and a.shape == r.shape and a.dtype == np.int32):
+                raise ValueError("every %s must be an int32 array shaped like its rate" % name)
+        packed.append(np.concatenate([a.reshape(-1) for a in seq]) if seq else np.zeros(0, dtype=np.int32))
+    n_each = np.array([r.shape[0] for r in rates], dtype=np.int32)
+    return n_each, packed[0], packed[1], packed[2]
+
+
+def _unpack_ragged(n_each, packed, into):
+    """Writes the packed arrays of a ragged batch back into the caller's matrices, in place."""
+    for flat, seq in zip(packed, into):
+        if flat is None or seq is None:
+            continue
+        at = 0
+        for n, a in zip(n_each, seq):
+            a[...] = flat[at:at + int(n) * int(n)].reshape(int(n), int(n))
+            at += int(n) * int(n)
+
+
+def solve_ragged(rates, nexts=None, hops=None, *, device=-1, count_updates=False):
+    """runAlgo on every matrix of a RAGGED batch (fwx_solve_ragged_f64 / _f32): rates is a sequence of square host
+    numpy arrays of one dtype and of any orders 0 ... FWX_BATCH_MAX_N, nexts / hops sequences of int32 arrays shaped
+    alike.  The batch is packed, solved with one launch per tier, and written back in place.  Every matrix comes back
+    as `solve` of that matrix alone would leave it.
+
+    Returns the per-matrix U as a uint64 array if count_updates else None."""
+    rates = list(rates)
+    nexts = None if nexts is None else list(nexts)
+    hops = None if hops is None else list(hops)
+    n_each, rate, nxt, hp = _pack_ragged(rates, nexts, hops)
+    o, _ = _opts(device, FWX_ENGINE_AUTO)
+    each = np.zeros(len(n_each), dtype=np.uint64) if count_updates else None
+    fn = lib().fwx_solve_ragged_f64 if rate.dtype == np.float64 else lib().fwx_solve_ragged_f32
+    check(fn(len(n_each), _np_ptr(n_each), _np_ptr(rate), _np_ptr(nxt), _np_ptr(hp), _np_ptr(each), ctypes.byref(o)),
+          "fwx_solve_ragged")
+    _unpack_ragged(n_each, (rate, nxt, hp), (rates, nexts, hops))
+    return each
+
+
+def solve_ragged_lists(rates, nexts, hops=None, *, items=None, cap=None, device=-1, count_updates=False):
+    """solve_ragged and, in the same call, the reference's exact `_path` lists (fwx_solve_ragged_lists_f64 / _f32);
+    nexts is required.  items, cap and the return value as in solve_batch_lists: items None means all n_b * n_b pairs
+    of every matrix in the order (b, i, j); cap None starts at BATCH_LISTS_FIRST_CAP and doubles, solving the batch
+    again from a kept copy of the input for the items that did not fit, up to BATCH_LISTS_MAX_CAP."""
+    if nexts is None:
+        raise ValueError("the exact lists need next")
+    rates, nexts = list(rates), list(nexts)
+    hops = None if hops is None else list(hops)
+    n_each, rate, nxt, hp = _pack_ragged(rates, nexts, hops)
+    count = len(n_each)
+    if items is None:
+        trip = [np.stack(np.meshgrid(np.array([b]), np.arange(n), np.arange(n), indexing="ij"), -1).reshape(-1, 3)
+                for b, n in enumerate(n_each)]
+        trip = np.concatenate(trip) if trip else np.zeros((0, 3), dtype=np.int32)
+        items = (trip[:, 0], trip[:, 1], trip[:, 2])
+    mat, src, dst = (np.ascontiguousarray(a, dtype=np.int32) for a in items)
+    if not (mat.ndim == 1 and mat.shape == src.shape == dst.shape):
+        raise ValueError("items must be three equally long one-dimensional sequences (mat, src, dst)")
+    fn = lib().fwx_solve_ragged_lists_f64 if rate.dtype == np.float64 else lib().fwx_solve_ragged_lists_f32
+    grow = cap is None
+    cap = BATCH_LISTS_FIRST_CAP if grow else int(cap)
+    kept = (rate.copy(), nxt.copy(), None if hp is None else hp.copy()) if grow else None
+    each = np.zeros(count, dtype=np.uint64) if count_updates else None
+    o, _ = _opts(device, FWX_ENGINE_AUTO)
+    out = [None] * len(mat)
+    todo = np.arange(len(mat))
+    arrays = (rate, nxt, hp)
+    while True:
+        lens = np.empty(len(todo), dtype=np.int32)
+        paths = np.empty((len(todo), cap), dtype=np.int32)
+        m, s, d = (np.ascontiguousarray(a[todo]) for a in (mat, src, dst))
+        check(fn(count, _np_ptr(n_each), _np_ptr(arrays[0]), _np_ptr(arrays[1]), _np_ptr(arrays[2]),
+                 _np_ptr(each) if arrays[0] is rate else None, len(todo), _np_ptr(m), _np_ptr(s), _np_ptr(d),
+                 _np_ptr(lens), _np_ptr(paths), cap, ctypes.byref(o)), "fwx_solve_ragged_lists")
+        if count == 0 or not n_each.any():
+            lens[:] = _lib.FWX_ERR_INVALID       # nothing was solved: no item lies in the batch
+        short = lens == _lib.FWX_ERR_CAPACITY
+        bad = (lens < 0) & ~short
+        if bad.any():
+            raise FwxError(int(lens[bad][0]), "fwx_solve_ragged_lists: item %d" % int(todo[bad][0]))
+        for q in np.nonzero(~short)[0]:
+            out[todo[q]] = tuple(int(v) for v in paths[q, :lens[q]])
+        if not short.any():
+            break
+        if not grow or cap >= BATCH_LISTS_MAX_CAP:
+            raise FwxError(_lib.FWX_ERR_CAPACITY, "fwx_solve_ragged_lists: item %d does not fit cap %d"
+                           % (int(todo[short][0]), cap))
+        cap, todo = min(2 * cap, BATCH_LISTS_MAX_CAP), todo[short]
+        arrays = tuple(None if a is None else a.copy() for a in kept)     # solved again from the input
+    _unpack_ragged(n_each, (rate, nxt, hp), (rates, nexts, hops))
+    return (out, each) if count_updates else out
+
+
+def _index_ptr(t, dtype_name, least):
+    assert t.is_cuda and t.is_contiguous() and _dtype_name(t) == dtype_name and t.numel() >= least
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def dev_solve_ragged(rate_t, n_each_t, offset_t, order_t, tier_count, *, next_t=None, hops_t=None, trace=None,
+                     updates_t=None, stream=None):
+    """fwx_dev_solve_ragged: a ragged batch in the device array rate_t (next_t / hops_t and the three arrays of
+    `trace` alike), matrix b of order n_each_t[b] at element offset_t[b]; n_each_t (int32), offset_t (int64) and
+    order_t (int32) are DEVICE arrays of count entries, order_t / tier_count a plan as ragged_plan gives it.  Gaps
+    between the matrices are never touched.  Asynchronous on `stream`.  updates_t: device array of count 64-bit
+    counters, counter b is incremented by U of matrix b."""
+    count = n_each_t.numel()
+    tiers = np.ascontiguousarray(tier_count, dtype=np.int32)
+    assert tiers.shape == (3,)
+    assert rate_t.is_cuda and rate_t.is_contiguous()
+    for t in (next_t, hops_t):
+        assert t is None or (t.is_cuda and t.is_contiguous() and _dtype_name(t) == "int32")
+    assert updates_t is None or (updates_t.element_size() == 8 and updates_t.numel() >= count)
+    vp = ctypes.c_void_p
+    check(lib().fwx_dev_solve_ragged(
+        count, _tensor_dtype_code(rate_t), vp(rate_t.data_ptr()),
+        vp(next_t.data_ptr()) if next_t is not None else None,
+        vp(hops_t.data_ptr()) if hops_t is not None else None,
+        _index_ptr(n_each_t, "int32", count), _index_ptr(offset_t, "int64", count),
+        _index_ptr(order_t, "int32", int(tiers.sum())), _np_ptr(tiers),
+        _trace_of(trace, 0) if trace is not None else None,
+        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)),
+        "fwx_dev_solve_ragged")
+
+
+def dev_exact_paths_ragged(next0_t, n_each_t, offset_t, n_max, trace, mat_t, src_t, dst_t, cap, *, stream=None):
+    """fwx_dev_exact_paths_ragged: the exact `_path` lists of the items (mat_t[q], src_t[q], dst_t[q]) of a ragged
+    batch that dev_solve_ragged solved with `trace`; next0_t is the caller's copy of the UNSOLVED next-hop array (same
+    offsets), n_max at least the largest order.  Returns (len_t, path_t) as dev_exact_paths_batch."""
+    count = n_each_t.numel()
+    assert next0_t.is_cuda and next0_t.is_contiguous() and _dtype_name(next0_t) == "int32"
+    items = mat_t.numel()
+    for t in (mat_t, src_t, dst_t):
+        assert t.is_cuda and t.is_contiguous() and _dtype_name(t) == "int32" and t.numel() == items
+    len_t = _empty_like_device(mat_t, (items,), "int32")
+    path_t = _empty_like_device(mat_t, (items, cap), "int32")
+    scratch = _empty_like_device(mat_t, (max(items * 3 * (n_max + 2), 1),), "int32")
+    vp = ctypes.c_void_p
+    check(lib().fwx_dev_exact_paths_ragged(
+        count, _index_ptr(n_each_t, "int32", count), _index_ptr(offset_t, "int64", count), n_max,
+        vp(next0_t.data_ptr()), _trace_of(trace, 0), items, vp(mat_t.data_ptr()), vp(src_t.data_ptr()),
+        vp(dst_t.data_ptr()), vp(len_t.data_ptr()), vp(path_t.data_ptr()), cap, vp(scratch.data_ptr()),
+        _stream_ptr(stream, mat_t)), "fwx_dev_exact_paths_ragged")
     if not _is_torch(mat_t):
         len_t._scratch = scratch              # stays alive until the results are read
     return len_t, path_t

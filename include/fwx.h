@@ -236,6 +236,75 @@ int fwx_solve_batch_lists_f32(int32_t count, int32_t n, float *rate, int32_t *ne
  * the budget give it right now (FWX_ERR_INVALID for n < 0 or cap < 1).  Needs no device.  Not for production use. */
 int64_t fwx_test_batch_lists_chunk(int32_t n, int32_t cap);
 
+/* ---- ragged batched small solves: matrices of DIFFERENT orders in one call --------------------------------
+ * A price history does not have one order: the vertex set grows as exchanges and currencies first appear, and venue
+ * groups differ in size.  A ragged batch is `count` matrices; matrix b has order n_each[b], 0 <= n_each[b] <=
+ * FWX_BATCH_MAX_N, pitch n_each[b], and starts at element offset[b] of rate; next, hops and the three trace arrays
+ * use the same offsets.  These are the semantics of the uniform batch above applied per matrix: the full list rule,
+ * no domain check and no routing, every matrix bit-identical to the reference loop on that matrix alone, and no
+ * matrix pays for the largest order of the batch.  Only the whole pivot range is supported.
+ *
+ * fwx_ragged_plan: the schedule, from the orders alone; needs no device.  offset_out (count + 1 entries) receives the
+ * PACKED offsets, offset[b] = sum of n_a * n_a over a < b, and the total at [count].  order_out (count entries)
+ * receives the indices of the matrices with n_b >= 1 grouped by tier -- the wave tier (n_b <= FWX_BATCH_WAVE_MAX_N,
+ * the setting above, read by the plan and only by the plan), then the 64-wide workgroup tier (n_b <= 64), then the
+ * 128-wide one -- and within a tier sorted by descending order, ties by ascending index, so that the longest
+ * workgroups start first; the entries past the three counts are -1.  tier_count_out: matrices per tier.  Matrices of
+ * order 0 appear in no tier.  Any of the three outputs may be NULL.  FWX_ERR_INVALID: count < 0, n_each NULL with
+ * count > 0, a negative order.  FWX_ERR_UNSUPPORTED: an order above FWX_BATCH_MAX_N.  No result bit of a solve
+ * depends on the split.
+ *
+ * fwx_solve_ragged_f64 / _f32: HOST arrays, the batch packed (the offsets of fwx_ragged_plan), solved in place with
+ * up to three launches -- one per non-empty tier, the 128-wide tier first -- on one stream.  updates_each: optional,
+ * count entries, U of each matrix (0 for order 0).  opts as for fwx_solve_batch_*, except that a pivot range other
+ * than the whole one (k_begin != 0 or k_end > 0) is FWX_ERR_INVALID.
+ * fwx_solve_ragged_lists_f64 / _f32: the same and, in the same call, the exact `_path` lists of `items` triples, as
+ * fwx_solve_batch_lists_*; the items are walked in chunks sized by the largest order present.
+ *
+ * fwx_dev_solve_ragged: caller-owned DEVICE memory -- the three index arrays d_n_each, d_offset (count entries each)
+ * and d_order included -- asynchronous on `stream`, nothing allocated or synchronised.  The offsets need not be
+ * packed: nothing outside the n_b x n_b cells of a matrix is read or written, so the caller may leave gaps between
+ * matrices and place them in any order (they must not overlap).  d_order / tier_count (HOST, three entries) are a
+ * plan as fwx_ragged_plan gives it for these orders; a matrix listed in a tier whose tile does not hold its order is
+ * left untouched.  trace (or NULL): the path trace as in fwx_dev_solve_batch_traced, at the same offsets; next is
+ * then required and every cell of every n_b x n_b part of the three arrays is written.  d_updates_each: optional,
+ * count uint64, entry b INCREMENTED by U of matrix b.
+ * fwx_dev_exact_paths_ragged: the lists of `items` triples from such a trace and from next0, the caller's copy of the
+ * unsolved next-hops (same offsets), one thread per item, as fwx_dev_exact_paths_batch.  An item with mat outside
+ * [0, count), or with src / dst outside [0, n_mat) -- n_mat the order of THAT item's matrix, not n_max; no item of an
+ * order-0 matrix is valid -- gets FWX_ERR_INVALID alone.  Capacity rule and stack bound as above; n_max is at least
+ * the largest order of the batch and scratch holds items * FWX_EXACT_SCRATCH_INTS(n_max) int32.
+ *
+ * Statuses, all decided before any device call.  FWX_ERR_INVALID: a negative count, items or order; n_each NULL; rate
+ * NULL when some order is positive; hops without next; the lists arguments as in fwx_solve_batch_lists_*; a bad
+ * struct_size; a pivot range; in the device forms a bad dtype, a NULL tier_count, a negative tier count or a sum of
+ * the three above count, a NULL index array, a trace without next or with a NULL pointer.  FWX_ERR_UNSUPPORTED: an
+ * order (n_max in the walk) above FWX_BATCH_MAX_N, or an engine other than FWX_ENGINE_AUTO.  count == 0, or every
+ * order 0 (device form: all three tier counts 0; walk: n_max == 0 or items == 0): FWX_OK, nothing is touched.  Then
+ * FWX_ERR_NO_DEVICE without a device, the arrays untouched.                                                   */
+int fwx_ragged_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
+                    int32_t tier_count_out[3]);
+int fwx_solve_ragged_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                         uint64_t *updates_each, const fwx_opts *opts);
+int fwx_solve_ragged_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                         uint64_t *updates_each, const fwx_opts *opts);
+int fwx_dev_solve_ragged(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                         const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                         const int32_t tier_count[3], const struct fwx_trace *trace,
+                         unsigned long long *d_updates_each, void *stream);
+int fwx_dev_exact_paths_ragged(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                               const int32_t *next0, const struct fwx_trace *trace, int32_t items,
+                               const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
+                               int32_t *path_out, int32_t cap, int32_t *scratch, void *stream);
+int fwx_solve_ragged_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                               const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                               const fwx_opts *opts);
+int fwx_solve_ragged_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                               const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                               const fwx_opts *opts);
+
 /* Index form of the `_path` list that optimum returns (Algorithms.hs:74-75): follow next-hops
  * from src until dst.  Returns the number of vertices written to out (dst included, src not), 0 if
  * next[src][dst] == -1 (empty path, "no exchange"), or a negative fwx_status.  Host arrays.      */
