@@ -805,6 +805,9 @@ int panel_impl(const fwx_slab *b, T *w, int32_t *w_hops, unsigned long long *d_u
                                             b->hops ? b->hops + (size_t)t * n : nullptr, n, s));
         a.prow = w + (size_t)t * n;
         a.phops = b->hops ? w_hops + (size_t)t * n : nullptr;
+        // the list rule in full (an empty ikPath takes next[k][j]): next-hop row k at time k is the block's own
+        // row t, which step k leaves alone
+        a.pnext = b->next ? b->next + (size_t)t * n : nullptr;
         a.k = k0 + t;
         FWX_HIP(fwx::launch_relax<T>(a, s));
     }

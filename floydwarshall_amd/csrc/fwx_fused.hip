@@ -2561,8 +2561,33 @@ hipError_t launch_fused_main(const FusedArgs<T> &full, int r_lo, int r_hi, hipSt
 template <typename T>
 hipError_t launch_fused_relax(const FusedArgs<T> &a, hipStream_t s, int skip_lo, int skip_hi)
 {
-    hipError_t e = launch_fused_colpanel<T>(a, s);   // skipped rows get snapshots nobody reads
-    if (e != hipSuccess) return e;
+    if (skip_hi <= skip_lo) {
+        hipError_t e = launch_fused_colpanel<T>(a, s);
+        if (e != hipSuccess) return e;
+        return launch_fused_main<T>(a, 0, a.rows, s, 0, 0, FusedCols());
+    }
+    // The skipped rows belong to an earlier look-ahead step: they are past this pass already, and a column panel
+    // over them would take their at_col snapshots from that later state.  Column panels above and below them only
+    // (each writes its own rows' part of ct / cnt / cht and of at_col); nothing of the skipped rows is read or written.
+    if (skip_lo < 0 || skip_hi > a.rows || skip_lo % 8 != 0 || skip_hi % 8 != 0) return hipErrorInvalidValue;
+    const int part[2][2] = {{0, skip_lo}, {skip_hi, a.rows}};
+    for (int h = 0; h < 2; ++h) {
+        const int lo = part[h][0], hi = part[h][1];
+        if (hi <= lo) continue;
+        const size_t off = (size_t)lo * a.n;
+        FusedArgs<T> c = a;
+        c.rate = a.rate + off;
+        c.next = a.next ? a.next + off : nullptr;
+        c.hops = a.hops ? a.hops + off : nullptr;
+        c.rows = hi - lo;
+        c.row0 = a.row0 + lo;
+        c.ct = a.ct + lo;
+        c.cnt = a.cnt ? a.cnt + lo : nullptr;
+        c.cht = a.cht ? a.cht + lo : nullptr;
+        if (a.plog.last) { c.plog.last = a.plog.last + off; c.plog.at_col = a.plog.at_col + off; }
+        hipError_t e = launch_fused_colpanel<T>(c, s);
+        if (e != hipSuccess) return e;
+    }
     return launch_fused_main<T>(a, 0, a.rows, s, skip_lo, skip_hi, FusedCols());
 }
 

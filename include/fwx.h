@@ -599,7 +599,9 @@ int fwx_dev_relax_skip(const fwx_slab *slab, const fwx_pivots *piv, int32_t serp
  * [block->row0, block->row0 + block->rows) at time k = block->row0.  Evolves them in place through
  * those pivots and writes the time-k snapshot of each pivot row to w_rate (rows x n) (and its hops
  * row to w_hops if the slab carries hops).  Afterwards the block rows are at time row0+rows and
- * every other row of the matrix must be relaxed with fwx_dev_relax(pivots = w_rate).            */
+ * every other row of the matrix must be relaxed with fwx_dev_relax(pivots = w_rate).  Inside the
+ * block the list rule holds in full, outside the domain too: an update with an empty ikPath takes
+ * next[k][j] from the block's own row k, which step k leaves alone.                              */
 int fwx_dev_panel(const fwx_slab *block, void *w_rate, int32_t *w_hops,
                   unsigned long long *d_updates, void *stream);
 
@@ -663,7 +665,9 @@ int fwx_dev_panel_snap(const fwx_slab *block, void *w_rate, int32_t *w_hops, con
 int fwx_dev_relax_fused(const fwx_slab *slab, const fwx_pivots *piv, const fwx_fused_scratch *scratch,
                         const fwx_trace *trace, unsigned long long *d_updates, int32_t flags,
                         void *stream);
-/* Same, leaving the slab rows [skip_lo, skip_hi) (multiples of 8) to an earlier look-ahead step. */
+/* Same, leaving the slab rows [skip_lo, skip_hi) (multiples of 8) to an earlier look-ahead step:
+ * nothing of those rows is read or written -- rate, next, hops and their rows of the trace (at_col
+ * included) stay as that step left them.                                                         */
 int fwx_dev_relax_fused_skip(const fwx_slab *slab, const fwx_pivots *piv,
                              const fwx_fused_scratch *scratch, const fwx_trace *trace,
                              unsigned long long *d_updates, int32_t flags, int32_t skip_lo,

@@ -137,6 +137,51 @@ def path_from_trace(last, at_col, at_row, next0, a, b):
     return out
 
 
+def pass_reference(rate, nxt, hops, k0, k1):
+    """Everything ONE pass over the pivots [k0, k1) produces, from the whole-matrix state (rate, nxt, hops; nxt /
+    hops may be None) at time k0: the oracle stepped one pivot at a time (oracle.relax).  The inputs are left alone.
+
+    Returns a namespace with
+      rate, next, hops   the state at time k1
+      W, WH, WN          the snapshot panels: row t is row k0 + t of rate / hops / next at the start of step k0 + t
+      mask               (k1 - k0) x n x n bool: the entries step k0 + t updated.  An update is a strict x < cand,
+                         so an entry was updated exactly when its rate bits changed
+      u_rows             U per row: the updates of the pass in each row (int64, n entries)
+      last, at_col, at_row   the path trace of this one pass, from all -1: last[i][j] = the last pivot of the pass
+                         that updated (i, j) or -1; at_col[i][k] = last[i][k] at the start of step k; at_row[k][j] =
+                         last[k][j] at the start of step k (cells of other columns / rows stay -1)."""
+    import types
+    import oracle
+    n, bt = rate.shape[0], k1 - k0
+    assert 0 <= k0 <= k1 <= n
+    r = rate.copy()
+    nx = None if nxt is None else nxt.copy()
+    hp = None if hops is None else hops.copy()
+    it = np.uint64 if r.dtype.itemsize == 8 else np.uint32
+    out = types.SimpleNamespace(
+        W=np.empty((bt, n), dtype=r.dtype),
+        WH=None if hp is None else np.empty((bt, n), dtype=np.int32),
+        WN=None if nx is None else np.empty((bt, n), dtype=np.int32),
+        mask=np.zeros((bt, n, n), dtype=bool),
+        last=np.full((n, n), -1, dtype=np.int32), at_col=np.full((n, n), -1, dtype=np.int32),
+        at_row=np.full((n, n), -1, dtype=np.int32))
+    for t, k in enumerate(range(k0, k1)):
+        out.W[t] = r[k]
+        if hp is not None:
+            out.WH[t] = hp[k]
+        if nx is not None:
+            out.WN[t] = nx[k]
+        out.at_col[:, k] = out.last[:, k]
+        out.at_row[k, :] = out.last[k, :]
+        before = r.view(it).copy()
+        oracle.relax(r, nx, hp, k, k + 1)
+        out.mask[t] = r.view(it) != before
+        out.last[out.mask[t]] = k
+    out.rate, out.next, out.hops = r, nx, hp
+    out.u_rows = out.mask.sum(axis=(0, 2)).astype(np.int64)
+    return out
+
+
 # ---- BASELINE config 5 (N = 32768 f32, rate + next + hops): oracle slices around launch boundaries -----
 CONFIG5_SLICES = ((0, 256), (16256, 16512), (32512, 32768))
 
