@@ -1256,6 +1256,14 @@ int fwx_test_perk_pivots(uint64_t *launches, int reset)
 
 int fwx_test_perk_fold(void) { return perk_fold_compare() ? 1 : 0; }
 
+int fwx_test_perk_wide(uint64_t *wide_launches, int reset)
+{
+    const uint64_t v = reset ? g_perk_wide_launches.exchange(0, std::memory_order_relaxed)
+                             : g_perk_wide_launches.load(std::memory_order_relaxed);
+    if (wide_launches) *wide_launches = v;
+    return perk_wide() ? 1 : 0;
+}
+
 const char *fwx_test_kernel_form_name(int form)
 {
     static const char *const names[] = {

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 #include <errno.h>
 #include <stddef.h>
@@ -484,6 +485,17 @@ inline int perk_pivots()
     return FWX_PERK_PIVOTS_DEFAULT;
 }
 
+// The wide pass of the multi-pivot schedule (round 19): where it would issue two consecutive 8-pivot sweeps inside a
+// block, an uncounted f32 solve at the width 8 issues one 16-pivot sweep.  FWX_PERK_WIDE=0 turns it off -- launch
+// for launch the schedule before it -- and anything else, or unset, leaves it on; read on every call.  It has no
+// effect at any other width (FWX_PERK_PIVOTS keeps its parse: 16 is no width), on a counted call or on f64.  For
+// tests and A/B runs in one binary.  No result bit depends on it.
+inline bool perk_wide()
+{
+    const char *e = getenv("FWX_PERK_WIDE");
+    return !(e && !strcmp(e, "0"));
+}
+
 // The fold of relax_kt's non-counting f32 sweeps: FWX_PERK_FOLD=compare forces the compare form in every tile, read on
 // every call; anything else, or unset: automatic (each wave takes the max form where the operands it has loaded
 // are all NaN or sign-clear).  For tests and A/B runs in one binary.  No result bit depends on it (DESIGN.md
@@ -531,7 +543,10 @@ inline long long batch_lists_chunk(int n, int cap)
 
 // Launches of the multi-pivot schedule by pivots per launch: [0] relax_k (ragged single pivots), [1] / [2] /
 // [3] relax_kt with 2 / 4 / 8, [4] panel launches.  Test hook fwx_test_perk_pivots (fwx.h); relaxed host atomics.
+// A 16-pivot sweep applies two 8-pivot groups and adds 2 to [3], so that the five counters read the same with the
+// wide pass on and off; the number of 16-pivot launches themselves is g_perk_wide_launches (fwx_test_perk_wide).
 inline std::atomic<uint64_t> g_perk_launches[5];
+inline std::atomic<uint64_t> g_perk_wide_launches;
 
 // Snapshot panels (W and Ct of one 64-pivot block) of the multi-pivot schedule: perk_kt_ws_bytes.  A blocking
 // entry point that holds a per-call context passes that context's workspace.  fwx_dev_relax* has no workspace
@@ -601,6 +616,8 @@ private:
 // time-k0 matrix, which it does not modify), then the block's pivots `np` at a time, one relax_kt launch
 // each, all on `s`.  A ragged end of a block goes down the powers of two; a last single pivot is a relax_k
 // launch on the live row -- exact, because between launches the matrix is a consistent time-k state.
+// An uncounted f32 call at np == 8 starts the ladder at 16 (perk_wide): the panels hold the snapshots of all 64
+// pivots of the block, so the second 8-pivot sweep of a pair need not re-read the matrix.
 template <typename T>
 inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine, int np,
                           unsigned long long *d_updates, hipStream_t s, void *ws)
@@ -626,23 +643,26 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
     const int rev = FWX_XCD_SERPENTINE && a.temporal_bytes >= 0 ? 2 : 1;
     Throttle thr;
     int sweeps = 0;                                // launches alternate direction, whatever their width
-    auto after = [&](hipError_t e, int slot) -> int {
+    auto after = [&](hipError_t e, int slot, int groups = 1) -> int {
         if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
         FWX_HIP(e);
-        g_perk_launches[slot].fetch_add(1, std::memory_order_relaxed);
+        g_perk_launches[slot].fetch_add((uint64_t)groups, std::memory_order_relaxed);
+        if (groups == 2) g_perk_wide_launches.fetch_add(1, std::memory_order_relaxed);
         return thr.tick(s);
     };
+    const int g_top = np == 8 && !d_updates && std::is_same<T, float>::value && perk_wide() ? 16 : np;
     for (int k0 = k_begin; k0 < k_end; k0 += FWX_FUSED_B) {
         const int bt = std::min(FWX_FUSED_B, k_end - k0);
         int t = 0;
         if (bt >= 2) {
             pa.k0 = k0; pa.bt = bt;
             if (const int rc = after(fwx::launch_fused_panels<T>(pa, w, nullptr, s), 4)) return rc;
-            for (int g = np; g >= 2; g >>= 1)
+            for (int g = g_top; g >= 2; g >>= 1)
                 for (; bt - t >= g; t += g) {
                     a.k = k0 + t; a.np = g; a.w = w + (size_t)t * n; a.ct = ct + (size_t)t * ld;
                     a.flip = serpentine ? rev * (sweeps++ & 1) : 0;
-                    if (const int rc = after(fwx::launch_relax_kt<T>(a, s), g == 8 ? 3 : g == 4 ? 2 : 1)) return rc;
+                    if (const int rc = after(fwx::launch_relax_kt<T>(a, s), g >= 8 ? 3 : g == 4 ? 2 : 1, g == 16 ? 2 : 1))
+                        return rc;
                 }
         }
         for (; t < bt; ++t) {

@@ -115,11 +115,13 @@ template <typename T> hipError_t launch_relax(const RelaxArgs<T> &a, hipStream_t
 // elements, rate and w 16-byte aligned.
 #define FWX_PERK_KT_RPB 8          // rows per workgroup and loads in flight per thread: 8 x 8 is 8-10 % faster per
 #define FWX_PERK_KT_UNROLL 8       //   pivot than relax_k's 4 x 4 at NP = 8 (profiles/r07_tune_relax_pivots.txt)
+#define FWX_PERK_KT16_RPB 16       // the 16-pivot sweep (non-counting f32 only): its geometry
+#define FWX_PERK_KT16_UNROLL 8     //   (profiles/r19_tune_relax_pivots.txt)
 template <typename T> struct RelaxKtArgs {
     T *rate;                       // n x n
     const T *w;                    // w[t*n + j]      = row k+t at time k+t          (t < np)
     const T *ct;                   // ct[t*ct_ld + i] = column k+t at time k+t, NaN at i == k+t
-    int ct_ld, n, k, np;           // np: 2, 4 or 8
+    int ct_ld, n, k, np;           // np: 2, 4 or 8; 16 for f32 with updates == nullptr
     int flip;                      // as RelaxArgs
     long long temporal_bytes = -1;
     int store_bytes = 0;

@@ -6,7 +6,7 @@
 // predicated stores.  No MFMA: (max, x) with a strict compare is not a dense contraction.
 //
 // Kernel 1  relax_k      one launch per pivot k over a slab of rows (HBM-bound streaming read)
-//           relax_kt     2, 4 or 8 neighbouring pivots per launch from time-k snapshots (rates only, whole
+//           relax_kt     2, 4, 8 or 16 neighbouring pivots per launch from time-k snapshots (rates only, whole
 //                        matrix in place): the same stream, read once per launch instead of once per pivot
 // Kernel 2  snapshot_row copies pivot row k into the snapshot panel (panel phase, multi-GPU)
 //
@@ -378,6 +378,13 @@ __global__ __launch_bounds__(256, MINW) void relax_k(T *rate, int32_t *next, int
 // chunk (the max form has no row-by-row tail).  These kernels of the production geometry ask for four waves per SIMD
 // in their launch bound where a store group is at most four lanes (relax_kt_min_waves, below).
 //
+// Round 19: NP = 16, non-counting f32 only (relax_kt_wide; the schedule: relax_range_kt, FWX_PERK_WIDE).  The same
+// kernel text: the NaN patch at column k + t for all 16 t, 64 registers of W, a staged row of Ct is four 16-byte
+// reads, the vote reads the RPB * NP > 64 staged values back from LDS, the max form is 64 multiplies, 28 v_max3_f32
+// and 4 v_max_f32 per row-vector, the compare form 16 steps.  Nothing but r[i][j] is read of the live matrix, so the
+// race-freedom argument holds for 16 consecutive snapshots as for 8.  Two waves per SIMD, 16 rows per workgroup, 8
+// in flight (profiles/r19_relax_kt16_isa.txt, r19_tune_relax_pivots.txt).
+//
 // The prologue issues every load a workgroup starts with back to back -- its pivot-column value, the NP
 // vectors of W and the first UNROLL rows of the stream, all from addresses valid in every lane -- and
 // patches the NaNs in with selects, so the barrier waits for one overlapped group of loads (round 10;
@@ -408,13 +415,16 @@ template <int N> __device__ __forceinline__ float max_of(const float (&c)[N])
 // spill.  Not where a group is 8 lanes (FWX_PERK_STORE_BYTES=128): that kernel spills 8 bytes under the bound and
 // takes 133 VGPRs without it.  Not in the other geometries (tools/tune_relax.hip), which are timed as the compiler
 // makes them (profiles/r14_relax_kt_isa.txt).
-template <typename T, int RPB, int UNROLL, bool COUNT, int GL> constexpr int relax_kt_min_waves()
+// The 16-pivot kernels (round 19) hold 64 registers of W and ask for two waves: under a bound of three or four every
+// geometry spills (profiles/r19_relax_kt16_isa.txt).
+template <typename T, int RPB, int UNROLL, bool COUNT, int GL, int NP = 8> constexpr int relax_kt_min_waves()
 {
+    if (NP > 8) return 2;
     return !COUNT && relax_kt_max_form<T>() && RPB == FWX_PERK_KT_RPB && UNROLL == FWX_PERK_KT_UNROLL && GL < 8 ? 4 : 1;
 }
 
 template <typename T, int W, int RPB, int UNROLL, bool COUNT, int GL, int NP>
-__global__ __launch_bounds__(256, (relax_kt_min_waves<T, RPB, UNROLL, COUNT, GL>()))
+__global__ __launch_bounds__(256, (relax_kt_min_waves<T, RPB, UNROLL, COUNT, GL, NP>()))
 void relax_kt(T *rate, const T *w, const T *ct, int ct_ld, int n, int k,
                                                 int nstrips, int flip, unsigned long long *updates,
                                                 int nt_below, unsigned strip_magic, int fold_compare)
@@ -1277,15 +1287,27 @@ template <typename T> hipError_t launch_relax(const RelaxArgs<T> &a, hipStream_t
 template hipError_t launch_relax<float>(const RelaxArgs<float> &, hipStream_t);
 template hipError_t launch_relax<double>(const RelaxArgs<double> &, hipStream_t);
 
+// The geometries in which the 16-pivot sweep exists: non-counting f32 (the only instantiation with a max form; a
+// counting call and f64 stay 8 wide, round 19), 8 or 16 rows per workgroup, 4 or 8 rows in flight.
+template <typename T, int RPB, int UNROLL> constexpr bool relax_kt_wide()
+{
+    return relax_kt_max_form<T>() && (RPB == 8 || RPB == 16) && (UNROLL == 4 || UNROLL == 8);
+}
+
 // relax_kt with the geometry (RPB, UNROLL); the tile order, the cache-policy split and the store group
-// are chosen exactly as launch_relax_cfg chooses them for relax_k.
-template <typename T, int RPB, int UNROLL>
+// are chosen exactly as launch_relax_cfg chooses them for relax_k.  np == 16 is taken only where the kernel exists
+// (relax_kt_wide, uncounted).  NARROW / WIDE: which kernels this instantiation carries, np 2, 4 and 8 / np 16; the
+// library asks for one of the two in each of its two geometries, tools/tune_relax.hip for both.
+template <typename T, int RPB, int UNROLL, bool NARROW = true, bool WIDE = relax_kt_wide<T, RPB, UNROLL>()>
 static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
 {
     constexpr int W = 16 / (int)sizeof(T), SW = 256 * W;
+    static_assert(!WIDE || relax_kt_wide<T, RPB, UNROLL>(), "no 16-pivot kernel in this geometry");
     if (a.n <= 0) return hipSuccess;
+    const bool narrow = NARROW && (a.np == 2 || a.np == 4 || a.np == 8);
+    const bool wide = WIDE && a.np == 16 && !a.updates;
     if (a.n % W || (uintptr_t)a.rate % 16 || (uintptr_t)a.w % 16 || a.ct_ld < a.n || a.k < 0 ||
-        a.k + a.np > a.n || (a.np != 2 && a.np != 4 && a.np != 8))
+        a.k + a.np > a.n || !(narrow || wide))
         return hipErrorInvalidValue;
     const int nstrips = (a.n + SW - 1) / SW;
     const int nchunks = (a.n + RPB - 1) / RPB;
@@ -1309,9 +1331,14 @@ static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
                        a.ct_ld, a.n, a.k, nstrips, flip, a.updates, nt_below, strip_magic, a.fold_compare ? 1 : 0)
 #define FWX_LAUNCH_KT_NP(CN, GL)                                                                   \
     do {                                                                                           \
-        if (a.np == 8) FWX_LAUNCH_KT(CN, GL, 8);                                                   \
-        else if (a.np == 4) FWX_LAUNCH_KT(CN, GL, 4);                                              \
-        else FWX_LAUNCH_KT(CN, GL, 2);                                                             \
+        if constexpr (WIDE && !CN) {                                                               \
+            if (a.np == 16) FWX_LAUNCH_KT(CN, GL, 16);                                             \
+        }                                                                                          \
+        if constexpr (NARROW) {                                                                    \
+            if (a.np == 8) FWX_LAUNCH_KT(CN, GL, 8);                                               \
+            else if (a.np == 4) FWX_LAUNCH_KT(CN, GL, 4);                                          \
+            else if (a.np == 2) FWX_LAUNCH_KT(CN, GL, 2);                                          \
+        }                                                                                          \
     } while (0)
 #define FWX_LAUNCH_KT_GL(CN)                                                                       \
     do {                                                                                           \
@@ -1332,7 +1359,12 @@ static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
 
 template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s)
 {
-    return launch_relax_kt_cfg<T, FWX_PERK_KT_RPB, FWX_PERK_KT_UNROLL>(a, s);
+    if (a.np == 16) {
+        if constexpr (relax_kt_wide<T, FWX_PERK_KT16_RPB, FWX_PERK_KT16_UNROLL>())
+            return launch_relax_kt_cfg<T, FWX_PERK_KT16_RPB, FWX_PERK_KT16_UNROLL, false, true>(a, s);
+        return hipErrorInvalidValue;
+    }
+    return launch_relax_kt_cfg<T, FWX_PERK_KT_RPB, FWX_PERK_KT_UNROLL, true, false>(a, s);
 }
 
 template hipError_t launch_relax_kt<float>(const RelaxKtArgs<float> &, hipStream_t);

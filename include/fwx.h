@@ -132,8 +132,15 @@ const char *fwx_test_kernel_form_name(int form);
 /* TEST HOOK for the per-k engine's multi-pivot schedule: returns what FWX_PERK_PIVOTS parses to right now
  * (1, 2, 4 or 8; the default on anything else).  launches (if not NULL) receives five counters of the
  * launches that schedule has made in this process -- single-pivot, 2-, 4- and 8-pivot sweeps, panel
- * launches -- which are cleared if reset.  Needs no device.  Not for production use.                  */
+ * launches -- which are cleared if reset.  A 16-pivot sweep of the wide pass (FWX_PERK_WIDE, below) applies two
+ * 8-pivot groups and adds 2 to the 8-pivot counter, so the five read the same with the wide pass on and off.
+ * Needs no device.  Not for production use.                                                             */
 int fwx_test_perk_pivots(uint64_t *launches, int reset);
+/* TEST HOOK for the wide pass of that schedule: returns what FWX_PERK_WIDE parses to right now: 0 = off (the value
+ * `0`, exactly), 1 = on (anything else, or unset).  *wide_launches (if not NULL) receives the number of 16-pivot
+ * sweeps launched in this process -- each of them also counted as 2 by fwx_test_perk_pivots -- which is cleared if
+ * reset.  Needs no device.  Not for production use.                                                     */
+int fwx_test_perk_wide(uint64_t *wide_launches, int reset);
 /* TEST HOOK: what FWX_PERK_FOLD parses to right now: 1 = compare (the value `compare`, exactly), 0 = automatic
  * (anything else, or unset).  Needs no device.  Not for production use.                              */
 int fwx_test_perk_fold(void);
@@ -575,6 +582,9 @@ typedef struct fwx_pivots {
  * 8; 1 = one launch per pivot): per block of 64 pivots one panel launch takes the time-k snapshots of
  * the block's rows and columns, then every launch folds 2, 4 or 8 neighbouring pivots from those
  * snapshots into each entry it streams, so the matrix is read once per launch, not once per pivot.
+ * At the width 8 an f32 call without d_updates folds 16 pivots per launch wherever two 8-pivot launches of one
+ * block would follow each other (FWX_PERK_WIDE, environment, read per call: `0` turns that off, anything else, or
+ * unset, leaves it on; FWX_PERK_PIVOTS itself takes 1 | 2 | 4 | 8 only, and a counted or f64 call stays 8 wide).
  * The result is bit for bit the same.  FWX_PERK_FOLD (environment, read per call): `compare` makes every
  * such f32 launch fold with a compare and a select per pivot, as every counting and every f64 launch does;
  * anything else, or unset, is automatic -- a wave whose loaded pivot operands are all NaN or sign-clear takes

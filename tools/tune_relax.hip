@@ -204,8 +204,10 @@ static int stores_sweep(float *d, int n, int per, int rounds)
 // issued as production issues it: per 64 pivots one fused_panels launch, then 64 / NP sweeps, serpentine in
 // groups of 8, the default temporal tail.  Reported per window: us per pivot over the whole window (panel
 // launches included) and us per sweep launch (the window minus its panel launches, which are timed on
-// their own, back to back on an otherwise idle chip, and reported separately).
-//   tune_relax 16384 0 256 3 pivots
+// their own, back to back on an otherwise idle chip, and reported separately).  NP = 16 (round 19): the 16-pivot
+// sweep of the non-counting f32 kernel in its candidate geometries, 64 / 16 sweeps per block.  An optional last
+// argument keeps only the variants with at least that many pivots per launch (`8`: the 8- and 16-wide ones).
+//   tune_relax 16384 0 256 3 pivots [min NP]
 struct KtCfg { const char *name; int np; hipError_t (*fn)(const fwx::RelaxKtArgs<float> &, hipStream_t); bool cmp = false; };
 template <int RPB, int UNROLL>
 static hipError_t run_kt(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
@@ -213,18 +215,26 @@ static hipError_t run_kt(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
     return fwx::launch_relax_kt_cfg<float, RPB, UNROLL>(a, s);
 }
 
-static int pivots_sweep(float *d, int n, int per, int rounds)
+static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
 {
-    std::vector<KtCfg> vars = {{"NP1 relax_k", 1, nullptr}};
+    std::vector<KtCfg> vars;
+    if (min_np <= 1) vars.push_back({"NP1 relax_k", 1, nullptr});
     for (int np : {2, 4, 8}) {
+        if (np < min_np) continue;
         vars.push_back({"RPB4 U4", np, run_kt<4, 4>});
         vars.push_back({"RPB8 U4", np, run_kt<8, 4>});
         vars.push_back({"RPB8 U8", np, run_kt<8, 8>});
         vars.push_back({"RPB8 U8 cmp", np, run_kt<8, 8>, true});   // the compare form forced in every tile
         vars.push_back({"RPB16 U8", np, run_kt<16, 8>});
     }
+    const KtCfg state_path = {"RPB8 U8", 8, run_kt<8, 8>};        // what the window states are made with
+    vars.push_back({"RPB8 U4", 16, run_kt<8, 4>});
+    vars.push_back({"RPB8 U8", 16, run_kt<8, 8>});
+    vars.push_back({"RPB16 U4", 16, run_kt<16, 4>});
+    vars.push_back({"RPB16 U8", 16, run_kt<16, 8>});
+    vars.push_back({"RPB16 U8 cmp", 16, run_kt<16, 8>, true});
     const int k0s[3] = {0, 4096, 12000}, nw = 3, nv = (int)vars.size();
-    if (n % 64 || per % 8) { printf("pivots mode: n must be a multiple of 64 and per of 8\n"); return 1; }
+    if (n % 64 || per % 16) { printf("pivots mode: n must be a multiple of 64 and per of 16\n"); return 1; }
     const size_t bytes = (size_t)n * n * sizeof(float);
     float *snap[3], *work, *w, *ct;
     for (int i = 0; i < nw; ++i) CK(hipMalloc(&snap[i], bytes));
@@ -243,7 +253,7 @@ static int pivots_sweep(float *d, int n, int per, int rounds)
     int sweeps = 0;
     // pivots [kb, ke) with variant v; returns the number of sweep launches.  Timing only: a 64-block is
     // rounded DOWN to whole groups of np pivots (production sends a ragged end down the powers of two), so
-    // the window starts and `per` must be multiples of 8 for the states to be the per-k states
+    // the window starts and `per` must be multiples of 16 (the widest group) for the states to be the per-k states
     auto run = [&](const KtCfg &v, int kb, int ke) {
         int launches = 0;
         if (v.np == 1) {
@@ -269,7 +279,7 @@ static int pivots_sweep(float *d, int n, int per, int rounds)
     // window states: the NP = 8 path from the pristine matrix (bit for bit the per-k states)
     CK(hipMemcpy(work, d, bytes, hipMemcpyDeviceToDevice));
     for (int i = 0, k = 0; i < nw; ++i) {
-        if (k0s[i] > k) run(vars[nv - 3], k, std::min(n, k0s[i]));
+        if (k0s[i] > k) run(state_path, k, std::min(n, k0s[i]));
         k = std::min(n, k0s[i]);
         CK(hipMemcpy(snap[i], work, bytes, hipMemcpyDeviceToDevice));
     }
@@ -389,7 +399,7 @@ int main(int argc, char **argv)
 
     if (argc > 5 && !strcmp(argv[5], "policy")) return policy_sweep(d, n, warm, per, rounds);
     if (argc > 5 && !strcmp(argv[5], "stores")) return stores_sweep(d, n, per, rounds);
-    if (argc > 5 && !strcmp(argv[5], "pivots")) return pivots_sweep(d, n, per, rounds);
+    if (argc > 5 && !strcmp(argv[5], "pivots")) return pivots_sweep(d, n, per, rounds, argc > 6 ? atoi(argv[6]) : 1);
 
     if (argc > 5 && !strcmp(argv[5], "fused")) {
         // PMC probe mode for the fused engine: `passes` passes of 64 pivots (panel, colpanel, main
