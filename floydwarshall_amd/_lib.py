@@ -30,6 +30,7 @@ FWX_ENGINE_AUTO, FWX_ENGINE_PERK, FWX_ENGINE_FUSED = 0, 1, 2
 FWX_UPDATE_SHARDS = 256
 FWX_FUSED_BLOCK = 64
 FWX_BATCH_MAX_N = 128
+FWX_BATCH_MID_MAX_N = 256
 FWX_FLAG_NONNEG = 1
 FWX_XCHG_AUTO, FWX_XCHG_PEER, FWX_XCHG_RCCL = 0, 1, 2
 FWX_XCHG_CALLBACK = 3
@@ -104,6 +105,12 @@ SIGNATURES = {
     "fwx_dev_solve_batch": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32,
                                            c_vp, c_vp]),
     "fwx_test_batch_wave_max_n": (ctypes.c_int, []),
+    "fwx_solve_batch_mid_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_batch_mid_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_dev_solve_batch_mid": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32,
+                                               c_vp, c_vp]),
+    "fwx_test_batch_mid_min_n": (ctypes.c_int, []),
+    "fwx_test_batch_mid_block": (ctypes.c_int, []),
     "fwx_dev_solve_batch_traced": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64,
                                                   ctypes.POINTER(FwxTrace), c_vp, c_vp]),
     "fwx_dev_exact_paths_batch": (ctypes.c_int, [c_i32, c_i32, ctypes.c_int64, c_vp, ctypes.POINTER(FwxTrace), c_i32,

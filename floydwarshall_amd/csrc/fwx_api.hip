@@ -494,21 +494,26 @@ int solve_host(int32_t n, T *rate, int32_t *next, int32_t *hops, const fwx_opts 
 }
 
 // What the batch entry points decide before any device call (fwx.h): the pivot range against n, then the
-// order against FWX_BATCH_MAX_N.  k_end <= 0 means n.
-int batch_range(int32_t n, int32_t k_begin, int32_t &k_end)
+// order against the entry point's limit (FWX_BATCH_MAX_N; FWX_BATCH_MID_MAX_N for the _mid forms).  k_end <= 0
+// means n.
+int batch_range(int32_t n, int32_t k_begin, int32_t &k_end, int32_t max_n = FWX_BATCH_MAX_N)
 {
     if (k_end <= 0) k_end = n;
     if (k_begin < 0 || k_begin > k_end || k_end > n) return FWX_ERR_INVALID;
-    return n > FWX_BATCH_MAX_N ? FWX_ERR_UNSUPPORTED : FWX_OK;
+    return n > max_n ? FWX_ERR_UNSUPPORTED : FWX_OK;
 }
 
 template <typename T>
 int dev_solve_batch(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, int64_t stride,
                     int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, hipStream_t s,
-                    const fwx::PathLog &plog = fwx::PathLog())
+                    const fwx::PathLog &plog = fwx::PathLog(), bool mid = false)
 {
-    const hipError_t e = fwx::launch_batch_solve<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
-                                                    d_updates_each, batch_wave_max_n(), s, plog);
+    // mid (the _mid entry points): orders from FWX_BATCH_MID_MIN_N up run the mid tier, smaller ones the tiers
+    // of the plain batch -- the same bits either way
+    const hipError_t e = mid && n >= batch_mid_min_n()
+        ? fwx::launch_batch_mid<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end, d_updates_each, s)
+        : fwx::launch_batch_solve<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
+                                     d_updates_each, batch_wave_max_n(), s, plog);
     if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
     FWX_HIP(e);
     return FWX_OK;
@@ -583,10 +588,12 @@ struct BatchLists {
 // b at the sum of the squares before it; the n passed in is ignored and stands for the largest order from then on
 // (the walk's stacks and chunks are sized by it).  Whole pivot range only.  The plan -- offsets, orders, the tier
 // list -- is built here and goes to the context's workspace behind the counters, in one copy.
+// mid (fwx_solve_batch_mid_*): the limit on n is FWX_BATCH_MID_MAX_N and dev_solve_batch routes by
+// FWX_BATCH_MID_MIN_N; everything else is the plain batch solve (no lists, not ragged).
 template <typename T>
 int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
                      const fwx_opts *o, const BatchLists *ls = nullptr, bool ragged = false,
-                     const int32_t *n_each = nullptr)
+                     const int32_t *n_each = nullptr, bool mid = false)
 {
     if (count < 0 || (!ragged && n < 0) || (ls && ls->items < 0)) return FWX_ERR_INVALID;
     if (count == 0 || (!ragged && n == 0)) return FWX_OK;
@@ -603,7 +610,7 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     if (rc) return rc;
     if (ls && (op.k_begin != 0 || op.k_end != n)) return FWX_ERR_INVALID;      // the trace covers whole solves only
     if (ragged && o && (o->k_begin != 0 || o->k_end > 0)) return FWX_ERR_INVALID;   // one range does not fit all orders
-    if ((rc = batch_range(n, op.k_begin, op.k_end))) return rc;
+    if ((rc = batch_range(n, op.k_begin, op.k_end, mid ? FWX_BATCH_MID_MAX_N : FWX_BATCH_MAX_N))) return rc;
     if (op.engine != FWX_ENGINE_AUTO) return FWX_ERR_UNSUPPORTED;
     DeviceGuard g;
     if ((rc = g.enter(op.device))) return rc;
@@ -699,7 +706,7 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
                                  tiers, (unsigned long long *)d_upd, s, plog);
     else
         rc = dev_solve_batch<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
-                                op.k_begin, op.k_end, (unsigned long long *)d_upd, s, plog);
+                                op.k_begin, op.k_end, (unsigned long long *)d_upd, s, plog, mid);
     if (rc) return rc;
 
     FWX_HIP(hipMemcpyAsync(staged ? (void *)st_rate : (void *)rate, d_rate, b_rate, hipMemcpyDeviceToHost, s));
@@ -1338,6 +1345,48 @@ int fwx_dev_solve_batch(int32_t count, int32_t n, int32_t dtype, void *rate, int
 }
 
 int fwx_test_batch_wave_max_n(void) { return batch_wave_max_n(); }
+
+int fwx_solve_batch_mid_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                            uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, nullptr, false, nullptr, true);
+    });
+}
+
+int fwx_solve_batch_mid_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                            uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, nullptr, false, nullptr, true);
+    });
+}
+
+int fwx_dev_solve_batch_mid(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                            int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
+                            void *stream)
+{
+    return fwxi::guarded([&]() -> int {
+        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
+        if (count == 0 || n == 0) return FWX_OK;
+        if (!rate || (hops && !next) || stride < (int64_t)n * n) return FWX_ERR_INVALID;
+        const int rc = batch_range(n, k_begin, k_end, FWX_BATCH_MID_MAX_N);
+        if (rc) return rc;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        hipStream_t s = (hipStream_t)stream;
+        if (dtype == FWX_F64)
+            return dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, k_begin, k_end,
+                                           d_updates_each, s, fwx::PathLog(), true);
+        return dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, k_begin, k_end,
+                                      d_updates_each, s, fwx::PathLog(), true);
+    });
+}
+
+static_assert(FWX_BATCH_MID_MAX_N == FWX_MID_N, "fwx.h states the largest order of the mid tier");
+
+int fwx_test_batch_mid_min_n(void) { return batch_mid_min_n(); }
+
+int fwx_test_batch_mid_block(void) { return FWX_MID_B; }
 
 int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
                                int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,

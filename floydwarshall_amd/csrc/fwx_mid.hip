@@ -1,0 +1,209 @@
+// fwx_mid.hip -- the mid tier of the batched solves: `count` matrices of one order n <= FWX_MID_N (256), one
+// workgroup per matrix, the matrix RESIDENT IN GLOBAL MEMORY (a 256 x 256 matrix with next and hops is 1 MiB: it
+// fits neither registers nor the CU's 160 KiB of LDS).  Pivots are taken FWX_MID_B at a time from time-k snapshots
+// held in LDS -- the fused engine's exactness argument inside one workgroup.
+//
+// For each block of pivots [k0, k0 + bt), bt <= B, the first block at k_begin:
+//   1. panel.  The pivot rows (bt x n) and pivot columns (n x bt, stored transposed) of rate / next / hops are
+//      loaded into LDS: W / WN / WH [t][j] = entry (k0+t, j), C / CN / CH [t][i] = entry (i, k0+t).  The diagonal
+//      entry (k0+t, k0+t) is not read: both panels hold NaN there, which IS the three skips of the panel phase and
+//      two of the sweep's (i == k: C[t][k] is NaN; j == k: W[t][k] is NaN; a diagonal target is NaN and NaN < x is
+//      false).  Then for t = 0 .. bt-2, k = k0 + t: row t of W and row t of C as they stand are the time-k
+//      snapshots and are frozen; pivot k is applied to the rows t' > t of W (operands C[t][k0+t'], W[t][j]) and of C
+//      (operands C[t][i], W[t][k0+t']) -- one multiply, one strict compare, the list rule, hops added.  A cross
+//      entry (k0+a, k0+b) lives in both panels; while both copies are unfrozen they see the same operands and stay
+//      equal, and once one is frozen it is that panel's snapshot.  The matrix in global memory is not modified and
+//      nothing is counted.
+//   2. sweep.  Every entry (i, j), i != j, is read from global memory once and folds the candidates
+//      C[t][i] * W[t][j] in ascending t with the strict <.  Only the LAST winning t matters for next and hops
+//      (every win overwrites both), so the fold keeps x, that t and a count; on a win next = CN[t][i] if that is >= 0
+//      else WN[t][j] (Algorithms.hs:55: an empty ikPath takes the head of kjPath), hops = CH[t][i] + WH[t][j], and
+//      the entry is written back -- otherwise nothing is stored.  Every successful compare counts one towards U.
+//   3. ONE workgroup barrier between the sweep and the next block's panel loads: workgroup-scope visibility of the
+//      sweep's global stores (the whole workgroup runs on one CU), and the panels in LDS are free again.
+// No communication between workgroups, no grid barrier, no spin-wait; every barrier is reached by all 1024 threads
+// and its trip count is a function of (n, k_begin, k_end, B) alone.
+//
+// Geometry: 1024 threads; thread (rg, c) = (tid / CW, tid % CW) with CW = n rounded up to a multiple of 64, so a wave
+// never straddles two row groups (rg is wave-uniform) and at most 63 columns plus one wave idle.  In the sweep a
+// thread keeps W[0..B)[c] in registers and walks the rows rg, rg + RGS, ...: C[t][i] is then a wave-uniform LDS
+// read (a broadcast) and the global loads / stores of a wave are one row segment.  Scalar element accesses only:
+// any pitch n, no alignment beyond the element.  The gap between matrices is never read or written, the
+// diagonal's rate neither.
+#include "fwx_kernels.h"
+
+#include <algorithm>
+
+namespace fwx {
+namespace {
+
+template <typename T> __device__ __forceinline__ T mid_nan();
+template <> __device__ __forceinline__ float mid_nan<float>() { return __builtin_nanf(""); }
+template <> __device__ __forceinline__ double mid_nan<double>() { return __builtin_nan(""); }
+
+constexpr int kMidThreads = 1024;
+constexpr int kMidB = FWX_MID_B;
+static_assert(kMidB >= 1 && kMidB <= 16 && (kMidB & (kMidB - 1)) == 0,
+              "a power of two (the column loads split an index by it); 16 fills the LDS of a CU in f64 with next and hops");
+// Pitch of the six LDS panels, in elements.  The column panels are filled by lanes that run over t first (a
+// wave reads 4 rows x 16 pivots: whole cache lines of the pivot columns) and therefore store kMidPitch elements
+// apart: at 260 the 16 pivots of a row land 4 dwords apart (2-way conflicts at the worst) where a pitch of 256 would
+// put them all on one bank.
+constexpr int kMidPitch = FWX_MID_N + 4;
+constexpr int kMidRows = 4;                   // sweep: global loads in flight per thread
+
+template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+__global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
+                                                               long long stride, int k_begin, int k_end,
+                                                               unsigned long long *updates)
+{
+    constexpr int B = kMidB, P = kMidPitch;
+    __shared__ T W[B][P], C[B][P];
+    __shared__ int32_t WN[HAS_NEXT ? B : 1][HAS_NEXT ? P : 1], CN[HAS_NEXT ? B : 1][HAS_NEXT ? P : 1];
+    __shared__ int32_t WH[HAS_HOPS ? B : 1][HAS_HOPS ? P : 1], CH[HAS_HOPS ? B : 1][HAS_HOPS ? P : 1];
+    __shared__ unsigned int s_cnt;
+
+    const size_t off = (size_t)blockIdx.x * (size_t)stride;
+    rate += off;
+    if constexpr (HAS_NEXT) next += off;
+    if constexpr (HAS_HOPS) hops += off;
+
+    const int tid = threadIdx.x;
+    const int cw = (n + 63) & ~63;                            // 64 .. 256
+    const int rgs = kMidThreads / cw;                         // 16 .. 4 row groups
+    const int rg = __builtin_amdgcn_readfirstlane(tid / cw);  // wave-uniform: cw is a multiple of 64
+    const int c = tid - rg * cw;
+    const bool live = rg < rgs && c < n;                      // 1024 / 192 leaves one wave over
+    if (tid == 0) s_cnt = 0;
+
+    unsigned int mine = 0;                                    // a WAVE total (scalar)
+    for (int k0 = k_begin; k0 < k_end; k0 += B) {
+        const int bt = min(B, k_end - k0);
+        // ---- 1. panel: load -------------------------------------------------------------------------------
+        if (live) {
+            for (int t = rg; t < bt; t += rgs) {              // pivot rows: lane c on column c
+                const int k = k0 + t, e = k * n + c;
+                W[t][c] = c == k ? mid_nan<T>() : rate[e];
+                if constexpr (HAS_NEXT) WN[t][c] = next[e];
+                if constexpr (HAS_HOPS) WH[t][c] = hops[e];
+            }
+        }
+        for (int e = tid; e < n * B; e += kMidThreads) {      // pivot columns: lane on (i, t), t fastest
+            const int t = e & (B - 1), i = e / B;
+            if (t < bt) {
+                const int k = k0 + t, g = i * n + k;
+                C[t][i] = i == k ? mid_nan<T>() : rate[g];
+                if constexpr (HAS_NEXT) CN[t][i] = next[g];
+                if constexpr (HAS_HOPS) CH[t][i] = hops[g];
+            }
+        }
+        __syncthreads();
+        // ---- 1. panel: pivots k0 .. k0+bt-2 on the rows of both panels that are not yet frozen ------------
+        for (int t = 0; t + 1 < bt; ++t) {
+            if (live) {
+                const T wc = W[t][c], cc = C[t][c];
+                int32_t wnc = -1, cnc = -1, whc = 0, chc = 0;
+                if constexpr (HAS_NEXT) { wnc = WN[t][c]; cnc = CN[t][c]; }
+                if constexpr (HAS_HOPS) { whc = WH[t][c]; chc = CH[t][c]; }
+                for (int u = t + 1 + rg; u < bt; u += rgs) {  // u is wave-uniform: the other operand is a broadcast
+                    const int ku = k0 + u;
+                    // row k0+u of the matrix: entry (ku, c) against (ku, k) * (k, c)
+                    const T cand_w = C[t][ku] * wc;
+                    if (W[u][c] < cand_w) {
+                        W[u][c] = cand_w;
+                        if constexpr (HAS_NEXT) { const int32_t h = CN[t][ku]; WN[u][c] = h >= 0 ? h : wnc; }
+                        if constexpr (HAS_HOPS) WH[u][c] = CH[t][ku] + whc;
+                    }
+                    // column k0+u of the matrix: entry (c, ku) against (c, k) * (k, ku)
+                    const T cand_c = cc * W[t][ku];
+                    if (C[u][c] < cand_c) {
+                        C[u][c] = cand_c;
+                        if constexpr (HAS_NEXT) CN[u][c] = cnc >= 0 ? cnc : WN[t][ku];
+                        if constexpr (HAS_HOPS) CH[u][c] = chc + WH[t][ku];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        // ---- 2. sweep --------------------------------------------------------------------------------------
+        if (rg < rgs) {                                       // wave-uniform
+            T w[B];
+#pragma unroll
+            for (int t = 0; t < B; ++t) w[t] = (t < bt && c < n) ? W[t][c] : mid_nan<T>();
+            for (int i0 = rg; i0 < n; i0 += rgs * kMidRows) {
+                T x[kMidRows];
+#pragma unroll
+                for (int m = 0; m < kMidRows; ++m) {
+                    const int i = i0 + m * rgs;
+                    // +inf: no candidate compares greater (a lane without an entry, or the diagonal's)
+                    x[m] = (T)__builtin_huge_val();
+                    if (i < n && c < n && i != c) x[m] = rate[i * n + c];
+                }
+#pragma unroll
+                for (int m = 0; m < kMidRows; ++m) {
+                    const int i = i0 + m * rgs;
+                    if (i >= n) break;                        // scalar
+                    T v = x[m];
+                    int tb = -1;
+#pragma unroll
+                    for (int t = 0; t < B; ++t) {
+                        const T cand = C[t][i] * w[t];        // Algorithms.hs:61; NaN where a skip applies
+                        const bool p = v < cand;              // :55 (false on NaN)
+                        v = p ? cand : v;
+                        tb = p ? t : tb;
+                        mine += (unsigned int)__builtin_popcountll(__ballot(p));
+                    }
+                    if (tb >= 0) {
+                        const int e = i * n + c;
+                        rate[e] = v;
+                        if constexpr (HAS_NEXT) { const int32_t h = CN[tb][i]; next[e] = h >= 0 ? h : WN[tb][c]; }
+                        if constexpr (HAS_HOPS) hops[e] = CH[tb][i] + WH[tb][c];
+                    }
+                }
+            }
+        }
+        // ---- 3. the sweep's stores before the next block's loads; the panels free again ---------------------
+        __syncthreads();
+    }
+    if (updates) {
+        if (mine && (tid & 63) == 0) atomicAdd(&s_cnt, mine);
+        __syncthreads();
+        if (tid == 0 && s_cnt) atomicAdd(&updates[blockIdx.x], (unsigned long long)s_cnt);
+    }
+}
+
+}  // namespace
+
+template <typename T>
+hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
+                            int k_end, unsigned long long *updates_each, hipStream_t s)
+{
+    if (count <= 0 || n <= 0 || k_end <= k_begin) return hipSuccess;
+    if (n > FWX_MID_N || (hops && !next) || k_begin < 0 || k_end > n || stride < (long long)n * n)
+        return hipErrorInvalidValue;
+    constexpr int kChunk = 1 << 21;           // workgroups per launch, as launch_batch_solve
+    for (long long b0 = 0; b0 < count; b0 += kChunk) {
+        const int cnt = (int)std::min<long long>(kChunk, count - b0);
+        const size_t off = (size_t)b0 * (size_t)stride;
+        T *r = rate + off;
+        int32_t *nx = next ? next + off : nullptr, *hp = hops ? hops + off : nullptr;
+        unsigned long long *u = updates_each ? updates_each + b0 : nullptr;
+#define FWX_BATCH_MID(HN, HH)                                                                      \
+    hipLaunchKernelGGL((mid_solve_batch<T, HN, HH>), dim3(cnt), dim3(kMidThreads), 0, s, r, nx, hp, n, stride, \
+                       k_begin, k_end, u)
+        if (hops) FWX_BATCH_MID(true, true);
+        else if (next) FWX_BATCH_MID(true, false);
+        else FWX_BATCH_MID(false, false);
+#undef FWX_BATCH_MID
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template hipError_t launch_batch_mid<float>(float *, int32_t *, int32_t *, int, int, long long, int, int,
+                                            unsigned long long *, hipStream_t);
+template hipError_t launch_batch_mid<double>(double *, int32_t *, int32_t *, int, int, long long, int, int,
+                                             unsigned long long *, hipStream_t);
+
+}  // namespace fwx

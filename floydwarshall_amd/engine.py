@@ -106,6 +106,18 @@ def solve_batch(rate, nxt=None, hops=None, *, device=-1, k_begin=0, k_end=0, cou
     shaped alike.  Every matrix comes back as `solve` of that matrix alone would leave it.
 
     Returns the per-matrix U as a uint64 array of `count` entries if count_updates else None."""
+    return _solve_batch("fwx_solve_batch", rate, nxt, hops, device, k_begin, k_end, count_updates)
+
+
+def solve_batch_mid(rate, nxt=None, hops=None, *, device=-1, k_begin=0, k_end=0, count_updates=False):
+    """solve_batch with the limit at n <= FWX_BATCH_MID_MAX_N (fwx_solve_batch_mid_f64 / _f32): orders from
+    FWX_BATCH_MID_MIN_N (environment, default 129) up run the mid tier -- one workgroup per matrix, the matrix
+    resident in device memory -- and smaller ones are forwarded to solve_batch's tiers.  Same arrays, same
+    results, same return value."""
+    return _solve_batch("fwx_solve_batch_mid", rate, nxt, hops, device, k_begin, k_end, count_updates)
+
+
+def _solve_batch(stem, rate, nxt, hops, device, k_begin, k_end, count_updates):
     if not (isinstance(rate, np.ndarray) and rate.ndim == 3 and rate.shape[1] == rate.shape[2]):
         raise ValueError("rate must be a numpy array of shape (count, n, n)")
     if rate.dtype not in (np.float32, np.float64) or not rate.flags.c_contiguous:
@@ -119,9 +131,8 @@ def solve_batch(rate, nxt=None, hops=None, *, device=-1, k_begin=0, k_end=0, cou
     count, n = rate.shape[0], rate.shape[1]
     o, _ = _opts(device, FWX_ENGINE_AUTO, k_begin, k_end)
     each = np.zeros(count, dtype=np.uint64) if count_updates else None
-    fn = lib().fwx_solve_batch_f64 if rate.dtype == np.float64 else lib().fwx_solve_batch_f32
-    check(fn(count, n, _np_ptr(rate), _np_ptr(nxt), _np_ptr(hops), _np_ptr(each), ctypes.byref(o)),
-          "fwx_solve_batch")
+    fn = getattr(lib(), stem + ("_f64" if rate.dtype == np.float64 else "_f32"))
+    check(fn(count, n, _np_ptr(rate), _np_ptr(nxt), _np_ptr(hops), _np_ptr(each), ctypes.byref(o)), stem)
     return each
 
 
@@ -131,6 +142,19 @@ def dev_solve_batch(rate_t, count, n, *, next_t=None, hops_t=None, stride=None, 
     matrix b at element b * stride (default n * n; the gap is never touched), next_t / hops_t alike, solved
     in place by one launch, asynchronously on `stream` (default: as dev_relax).  updates_t: device array
     of `count` 64-bit counters, counter b is incremented by U of matrix b."""
+    _dev_solve_batch("fwx_dev_solve_batch", rate_t, count, n, next_t, hops_t, stride, k_begin, k_end, updates_t,
+                     stream)
+
+
+def dev_solve_batch_mid(rate_t, count, n, *, next_t=None, hops_t=None, stride=None, k_begin=0, k_end=0,
+                        updates_t=None, stream=None):
+    """fwx_dev_solve_batch_mid: dev_solve_batch with the limit at n <= FWX_BATCH_MID_MAX_N; routing by
+    FWX_BATCH_MID_MIN_N as solve_batch_mid.  Same arrays, same results."""
+    _dev_solve_batch("fwx_dev_solve_batch_mid", rate_t, count, n, next_t, hops_t, stride, k_begin, k_end, updates_t,
+                     stream)
+
+
+def _dev_solve_batch(name, rate_t, count, n, next_t, hops_t, stride, k_begin, k_end, updates_t, stream):
     stride = n * n if stride is None else int(stride)
     need = (count - 1) * stride + n * n if count > 0 else 0
     assert rate_t.is_cuda and rate_t.is_contiguous() and rate_t.numel() >= need
@@ -139,12 +163,11 @@ def dev_solve_batch(rate_t, count, n, *, next_t=None, hops_t=None, stride=None, 
                              and t.numel() >= need)
     assert updates_t is None or (updates_t.element_size() == 8 and updates_t.numel() >= count)
     vp = ctypes.c_void_p
-    check(lib().fwx_dev_solve_batch(
+    check(getattr(lib(), name)(
         count, n, _tensor_dtype_code(rate_t), vp(rate_t.data_ptr()),
         vp(next_t.data_ptr()) if next_t is not None else None,
         vp(hops_t.data_ptr()) if hops_t is not None else None, stride, k_begin, k_end,
-        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)),
-        "fwx_dev_solve_batch")
+        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)), name)
 
 
 # solve_batch_lists with cap=None: the first capacity tried, and the last (the lists of an input with arbitrage

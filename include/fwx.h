@@ -188,6 +188,51 @@ int fwx_dev_solve_batch(int32_t count, int32_t n, int32_t dtype, void *rate, int
 /* TEST HOOK: what FWX_BATCH_WAVE_MAX_N parses to right now.  Needs no device.  Not for production use. */
 int fwx_test_batch_wave_max_n(void);
 
+/* ---- batched mid-size solves: many matrices of one order n <= FWX_BATCH_MID_MAX_N in ONE launch ------------
+ * The calls above stop at n = 128, where a matrix with next and hops still fits the registers and LDS of one
+ * workgroup.  A market of 20 exchanges x 12 currencies has 240 vertices; a price history or a what-if sweep over
+ * such a market is a batch of mid-size matrices.  These entry points take the batch up to n = 256: one workgroup per
+ * matrix, the matrix resident in device memory, 16 pivots per pass from time-k snapshots held in LDS.  Every matrix
+ * gets the full semantics above, the list rule included; there is no domain check and no routing by content, and
+ * each matrix comes back bit-identical to the reference loop on that matrix alone -- rate, next, hops and U.
+ *
+ * The contract is that of fwx_solve_batch_* / fwx_dev_solve_batch, with the limit at FWX_BATCH_MID_MAX_N:
+ * count matrices of order n, matrix b at rate + b*n*n (next / hops alike, both optional, hops needs next);
+ * HOST arrays, solved in place.  updates_each: optional, count entries, U of each matrix.
+ * count == 0 or n == 0: FWX_OK, nothing is touched.  FWX_ERR_INVALID: count < 0, n < 0, rate NULL, hops
+ * without next, a bad struct_size or pivot range.  FWX_ERR_UNSUPPORTED: n > FWX_BATCH_MID_MAX_N, or
+ * opts->engine other than FWX_ENGINE_AUTO.  All of these are decided before any device call; then
+ * FWX_ERR_NO_DEVICE without a device, the arrays untouched.  opts: device, k_begin / k_end (one range for every
+ * matrix), stream / use_stream and updates_out (the SUM of U over the batch) are honoured; serpentine is ignored.
+ * Routing: FWX_BATCH_MID_MIN_N (environment, read per call; an integer 1 ... 129, default 129, anything else
+ * means the default): orders below it are forwarded to fwx_solve_batch_* / fwx_dev_solve_batch (tier choice by
+ * FWX_BATCH_WAVE_MAX_N as above), orders from it up to 256 run the mid tier.  No result bit depends on it; it
+ * exists so that tests and A/B runs can put n <= 128 through the mid tier.
+ * When to use it: see the measurements beside the device form below.                                       */
+#define FWX_BATCH_MID_MAX_N 256
+int fwx_solve_batch_mid_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                            uint64_t *updates_each, const fwx_opts *opts);
+int fwx_solve_batch_mid_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                            uint64_t *updates_each, const fwx_opts *opts);
+/* The same on caller-owned DEVICE memory, asynchronous on `stream`, nothing allocated or synchronised;
+ * stride = elements between consecutive matrices (>= n*n, else FWX_ERR_INVALID; the gap is never read or
+ * written; no alignment beyond the element is assumed); pivots [k_begin, k_end) of every matrix, k_end <= 0
+ * means n; dtype: fwx_dtype; d_updates_each: optional device array of count uint64, INCREMENTED by each
+ * matrix's U.  Statuses as above (n > FWX_BATCH_MID_MAX_N: FWX_ERR_UNSUPPORTED).
+ * When it pays (MI355X, f64 + next + hops, profiles/r20_batch_mid.txt): one call against `count` blocking
+ * fwx_dev_solve calls.  A workgroup solves its matrix alone on one CU -- 0.33 ms at n = 129, 0.62 ms at 192,
+ * 1.28 ms at 256, and no longer for up to 256 matrices -- where one fwx_dev_solve call takes 0.26 - 0.48 ms.  The
+ * batch call overtakes the loop at count = 1 for n = 129, between 2 and 4 matrices for n = 192 and n = 256 (at
+ * count = 4: 2.1x and 1.3x), and is 68 - 286x faster at count = 256.  For one or two matrices of order 192 and
+ * up, call fwx_dev_solve: this entry point does not route them there, because it may not block or allocate.      */
+int fwx_dev_solve_batch_mid(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                            int64_t stride, int32_t k_begin, int32_t k_end,
+                            unsigned long long *d_updates_each, void *stream);
+/* TEST HOOK: what FWX_BATCH_MID_MIN_N parses to right now.  Needs no device.  Not for production use. */
+int fwx_test_batch_mid_min_n(void);
+/* TEST HOOK: the pivots per pass of the mid tier (B).  Needs no device.  Not for production use. */
+int fwx_test_batch_mid_block(void);
+
 /* ---- batched small solves with the exact `_path` lists ----------------------------------------------------
  * The reference returns, per entry, the list it concatenated when the entry last improved (`_path`,
  * Algorithms.hs:55; see "Exact `_path` lists" below): under exact ties -- its 1.0 edges between the same currency
