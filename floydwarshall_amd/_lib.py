@@ -120,6 +120,14 @@ SIGNATURES = {
     "fwx_solve_batch_lists_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                                  c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
     "fwx_test_batch_lists_chunk": (ctypes.c_int64, [c_i32, c_i32]),
+    "fwx_dev_solve_batch_mid_traced": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64,
+                                                      ctypes.POINTER(FwxTrace), c_vp, c_vp]),
+    "fwx_dev_exact_paths_batch_mid": (ctypes.c_int, [c_i32, c_i32, ctypes.c_int64, c_vp, ctypes.POINTER(FwxTrace),
+                                                     c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "fwx_solve_batch_mid_lists_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                     c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_batch_mid_lists_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                     c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
     "fwx_ragged_plan": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp]),
     "fwx_solve_ragged_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
     "fwx_solve_ragged_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),

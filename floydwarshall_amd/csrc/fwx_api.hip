@@ -511,7 +511,8 @@ int dev_solve_batch(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *h
     // mid (the _mid entry points): orders from FWX_BATCH_MID_MIN_N up run the mid tier, smaller ones the tiers
     // of the plain batch -- the same bits either way
     const hipError_t e = mid && n >= batch_mid_min_n()
-        ? fwx::launch_batch_mid<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end, d_updates_each, s)
+        ? fwx::launch_batch_mid<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end, d_updates_each, s,
+                                   plog)
         : fwx::launch_batch_solve<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
                                      d_updates_each, batch_wave_max_n(), s, plog);
     if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
@@ -589,7 +590,8 @@ struct BatchLists {
 // (the walk's stacks and chunks are sized by it).  Whole pivot range only.  The plan -- offsets, orders, the tier
 // list -- is built here and goes to the context's workspace behind the counters, in one copy.
 // mid (fwx_solve_batch_mid_*): the limit on n is FWX_BATCH_MID_MAX_N and dev_solve_batch routes by
-// FWX_BATCH_MID_MIN_N; everything else is the plain batch solve (no lists, not ragged).
+// FWX_BATCH_MID_MIN_N; everything else is the plain batch solve.  With ls (fwx_solve_batch_mid_lists_*) the mid tier
+// writes the trace itself and the walk is the same launch_exact_batch.  Not ragged.
 template <typename T>
 int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
                      const fwx_opts *o, const BatchLists *ls = nullptr, bool ragged = false,
@@ -863,6 +865,8 @@ __global__ void follow_path_kernel(EntryTab t, int n_real, int src, int dst, int
 // wrote; it keeps a corrupted one inside the scratch.
 __host__ __device__ constexpr size_t exact_stack_triples(int n_real) { return (size_t)n_real + 2; }
 static_assert(FWX_EXACT_SCRATCH_INTS(128) == 3 * exact_stack_triples(128), "fwx.h states the walk's scratch per item");
+static_assert(FWX_EXACT_SCRATCH_INTS(FWX_BATCH_MID_MAX_N) == 3 * exact_stack_triples(FWX_BATCH_MID_MAX_N),
+              "... at the mid tier's largest order too (fwx_dev_exact_paths_batch_mid)");
 
 template <typename Tab>
 __device__ int exact_walk(const Tab &t, int n_real, int src, int dst, int32_t *out, int32_t *stack, int cap)
@@ -1388,9 +1392,11 @@ int fwx_test_batch_mid_min_n(void) { return batch_mid_min_n(); }
 
 int fwx_test_batch_mid_block(void) { return FWX_MID_B; }
 
-int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                               int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
-                               void *stream)
+// fwx_dev_solve_batch_traced (max_n = FWX_BATCH_MAX_N) and fwx_dev_solve_batch_mid_traced (FWX_BATCH_MID_MAX_N, mid):
+// one contract, the limit apart.
+static int dev_solve_batch_traced_any(int32_t max_n, bool mid, int32_t count, int32_t n, int32_t dtype, void *rate,
+                                      int32_t *next, int32_t *hops, int64_t stride, const fwx_trace *trace,
+                                      unsigned long long *d_updates_each, void *stream)
 {
     return fwxi::guarded([&]() -> int {
         if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
@@ -1398,7 +1404,7 @@ int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *ra
         if (!rate || !next || !trace || !trace->last || !trace->at_col || !trace->at_row ||
             stride < (int64_t)n * n)
             return FWX_ERR_INVALID;
-        if (n > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
+        if (n > max_n) return FWX_ERR_UNSUPPORTED;
         if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
         fwx::PathLog plog;
         plog.last = trace->last;
@@ -1406,15 +1412,33 @@ int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *ra
         plog.at_row = trace->at_row;
         hipStream_t s = (hipStream_t)stream;
         if (dtype == FWX_F64)
-            return dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, 0, n, d_updates_each, s, plog);
-        return dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, 0, n, d_updates_each, s, plog);
+            return dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, 0, n, d_updates_each, s, plog,
+                                           mid);
+        return dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, 0, n, d_updates_each, s, plog, mid);
     });
 }
 
-int fwx_dev_exact_paths_batch(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
-                              const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
-                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                              int32_t *scratch, void *stream)
+int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                               int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
+                               void *stream)
+{
+    return dev_solve_batch_traced_any(FWX_BATCH_MAX_N, false, count, n, dtype, rate, next, hops, stride, trace,
+                                      d_updates_each, stream);
+}
+
+int fwx_dev_solve_batch_mid_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                                   int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
+                                   void *stream)
+{
+    return dev_solve_batch_traced_any(FWX_BATCH_MID_MAX_N, true, count, n, dtype, rate, next, hops, stride, trace,
+                                      d_updates_each, stream);
+}
+
+// fwx_dev_exact_paths_batch and fwx_dev_exact_paths_batch_mid: one walk, the limit apart.
+static int dev_exact_paths_batch_any(int32_t max_n, int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                                     const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                                     const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                     int32_t *scratch, void *stream)
 {
     return fwxi::guarded([&]() -> int {
         if (count < 0 || n < 0 || items < 0) return FWX_ERR_INVALID;
@@ -1422,7 +1446,7 @@ int fwx_dev_exact_paths_batch(int32_t count, int32_t n, int64_t stride, const in
         if (!next0 || !trace || !trace->last || !trace->at_col || !trace->at_row || stride < (int64_t)n * n ||
             cap < 1 || !mat || !src || !dst || !len_out || !path_out || !scratch)
             return FWX_ERR_INVALID;
-        if (n > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
+        if (n > max_n) return FWX_ERR_UNSUPPORTED;
         if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
         fwx::PathLog plog;
         plog.last = trace->last;
@@ -1431,6 +1455,24 @@ int fwx_dev_exact_paths_batch(int32_t count, int32_t n, int64_t stride, const in
         return launch_exact_batch(count, n, (long long)stride, next0, plog, items, mat, src, dst, len_out, path_out,
                                   cap, scratch, (hipStream_t)stream);
     });
+}
+
+int fwx_dev_exact_paths_batch(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                              const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_batch_any(FWX_BATCH_MAX_N, count, n, stride, next0, trace, items, mat, src, dst, len_out,
+                                     path_out, cap, scratch, stream);
+}
+
+int fwx_dev_exact_paths_batch_mid(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                                  const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                  int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_batch_any(FWX_BATCH_MID_MAX_N, count, n, stride, next0, trace, items, mat, src, dst,
+                                     len_out, path_out, cap, scratch, stream);
 }
 
 int fwx_solve_batch_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
@@ -1452,6 +1494,28 @@ int fwx_solve_batch_lists_f32(int32_t count, int32_t n, float *rate, int32_t *ne
     return fwxi::guarded([&]() -> int {
         const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
         return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, &ls);
+    });
+}
+
+int fwx_solve_batch_mid_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                                  uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                  const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true);
+    });
+}
+
+int fwx_solve_batch_mid_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                                  uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                  const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true);
     });
 }
 

@@ -154,14 +154,16 @@ hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, 
 // Mid tier of the batched solves (fwx_mid.hip): `count` matrices of one order n <= FWX_MID_N, same layout and
 // counters as launch_batch_solve, one workgroup per matrix, the matrix resident in global memory and FWX_MID_B
 // pivots per pass from time-k snapshot panels in LDS.  Any n from 1 up, any stride >= n*n, scalar accesses only.
-// No path trace.  One launch per 2^21 matrices.
+// plog (optional; plog.last != nullptr): the path trace as launch_batch_solve lays it out -- every cell of the n x n
+// part written by the kernel itself, the gap never; needs next and the whole pivot range [0, n)
+// (hipErrorInvalidValue otherwise).  One launch per 2^21 matrices.
 #define FWX_MID_N 256
 #ifndef FWX_MID_B                  // a power of two up to 16 (build variants: -DFWX_MID_B=8)
 #define FWX_MID_B 16
 #endif
 template <typename T>
 hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
-                            int k_end, unsigned long long *updates_each, hipStream_t s);
+                            int k_end, unsigned long long *updates_each, hipStream_t s, PathLog plog = PathLog());
 
 // Ragged batch: `count` matrices of different orders, matrix id of order n_each[id] <= FWX_SMALL_N at element
 // offset[id] of rate (next / hops / the trace arrays alike), pitch n_each[id]; whole pivot range of each.  The three

@@ -21,6 +21,17 @@
 //      the entry is written back -- otherwise nothing is stored.  Every successful compare counts one towards U.
 //   3. ONE workgroup barrier between the sweep and the next block's panel loads: workgroup-scope visibility of the
 //      sweep's global stores (the whole workgroup runs on one CU), and the panels in LDS are free again.
+// The path trace (HAS_LAST; PathLog in fwx_kernels.h, whole pivot range only) rides on the same three phases and
+// lives in GLOBAL memory throughout -- no LDS copy, so every dtype and field set has one code path and the f64 +
+// next + hops form keeps its 133 128 bytes of LDS (two more int32 panels would make 166 408 > 163 840):
+//   0. before the first block the workgroup fills last with -1 (every cell, the diagonal's too), one barrier.
+//   1. panel load copies last of the pivot rows to at_row and of the pivot columns to at_col -- last as it stands at
+//      BLOCK START; a panel-phase win of pivot k0+t on W[u][j] then stores at_row[k0+u][j] = k0+t, one on C[u][i]
+//      stores at_col[i][k0+u] = k0+t.  When row u is frozen the cells hold last of the entry at the start of step
+//      k0+u, which is what the walk reads.  A cell is written by different waves at different t: the barrier between
+//      pivots orders those stores (one CU, one L1, in-order vector memory; the argument of 3. below).
+//   2. sweep: a win stores last = k0 + (the last winning t) with next and hops.
+// Over the whole range every cell of at_row / at_col is written by exactly one panel load.
 // No communication between workgroups, no grid barrier, no spin-wait; every barrier is reached by all 1024 threads
 // and its trip count is a function of (n, k_begin, k_end, B) alone.
 //
@@ -52,11 +63,12 @@ static_assert(kMidB >= 1 && kMidB <= 16 && (kMidB & (kMidB - 1)) == 0,
 constexpr int kMidPitch = FWX_MID_N + 4;
 constexpr int kMidRows = 4;                   // sweep: global loads in flight per thread
 
-template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
 __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
                                                                long long stride, int k_begin, int k_end,
-                                                               unsigned long long *updates)
+                                                               unsigned long long *updates, PathLog plog)
 {
+    static_assert(HAS_NEXT || !HAS_LAST, "the trace goes with next");
     constexpr int B = kMidB, P = kMidPitch;
     __shared__ T W[B][P], C[B][P];
     __shared__ int32_t WN[HAS_NEXT ? B : 1][HAS_NEXT ? P : 1], CN[HAS_NEXT ? B : 1][HAS_NEXT ? P : 1];
@@ -67,6 +79,8 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
     rate += off;
     if constexpr (HAS_NEXT) next += off;
     if constexpr (HAS_HOPS) hops += off;
+    int32_t *last = nullptr, *at_row = nullptr, *at_col = nullptr;
+    if constexpr (HAS_LAST) { last = plog.last + off; at_row = plog.at_row + off; at_col = plog.at_col + off; }
 
     const int tid = threadIdx.x;
     const int cw = (n + 63) & ~63;                            // 64 .. 256
@@ -75,6 +89,10 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
     const int c = tid - rg * cw;
     const bool live = rg < rgs && c < n;                      // 1024 / 192 leaves one wave over
     if (tid == 0) s_cnt = 0;
+    if constexpr (HAS_LAST) {                                 // 0. the caller initialises nothing
+        for (int e = tid; e < n * n; e += kMidThreads) last[e] = -1;
+        __syncthreads();
+    }
 
     unsigned int mine = 0;                                    // a WAVE total (scalar)
     for (int k0 = k_begin; k0 < k_end; k0 += B) {
@@ -86,6 +104,7 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
                 W[t][c] = c == k ? mid_nan<T>() : rate[e];
                 if constexpr (HAS_NEXT) WN[t][c] = next[e];
                 if constexpr (HAS_HOPS) WH[t][c] = hops[e];
+                if constexpr (HAS_LAST) at_row[e] = last[e];
             }
         }
         for (int e = tid; e < n * B; e += kMidThreads) {      // pivot columns: lane on (i, t), t fastest
@@ -95,6 +114,7 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
                 C[t][i] = i == k ? mid_nan<T>() : rate[g];
                 if constexpr (HAS_NEXT) CN[t][i] = next[g];
                 if constexpr (HAS_HOPS) CH[t][i] = hops[g];
+                if constexpr (HAS_LAST) at_col[g] = last[g];
             }
         }
         __syncthreads();
@@ -113,6 +133,7 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
                         W[u][c] = cand_w;
                         if constexpr (HAS_NEXT) { const int32_t h = CN[t][ku]; WN[u][c] = h >= 0 ? h : wnc; }
                         if constexpr (HAS_HOPS) WH[u][c] = CH[t][ku] + whc;
+                        if constexpr (HAS_LAST) at_row[ku * n + c] = k0 + t;
                     }
                     // column k0+u of the matrix: entry (c, ku) against (c, k) * (k, ku)
                     const T cand_c = cc * W[t][ku];
@@ -120,6 +141,7 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
                         C[u][c] = cand_c;
                         if constexpr (HAS_NEXT) CN[u][c] = cnc >= 0 ? cnc : WN[t][ku];
                         if constexpr (HAS_HOPS) CH[u][c] = chc + WH[t][ku];
+                        if constexpr (HAS_LAST) at_col[c * n + ku] = k0 + t;
                     }
                 }
             }
@@ -158,6 +180,7 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
                         rate[e] = v;
                         if constexpr (HAS_NEXT) { const int32_t h = CN[tb][i]; next[e] = h >= 0 ? h : WN[tb][c]; }
                         if constexpr (HAS_HOPS) hops[e] = CH[tb][i] + WH[tb][c];
+                        if constexpr (HAS_LAST) last[e] = k0 + tb;
                     }
                 }
             }
@@ -176,9 +199,12 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
 
 template <typename T>
 hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
-                            int k_end, unsigned long long *updates_each, hipStream_t s)
+                            int k_end, unsigned long long *updates_each, hipStream_t s, PathLog plog)
 {
-    if (count <= 0 || n <= 0 || k_end <= k_begin) return hipSuccess;
+    if (count <= 0 || n <= 0) return hipSuccess;
+    const bool traced = plog.last != nullptr;
+    if (traced && (!next || !plog.at_col || !plog.at_row || k_begin != 0 || k_end != n)) return hipErrorInvalidValue;
+    if (k_end <= k_begin) return hipSuccess;
     if (n > FWX_MID_N || (hops && !next) || k_begin < 0 || k_end > n || stride < (long long)n * n)
         return hipErrorInvalidValue;
     constexpr int kChunk = 1 << 21;           // workgroups per launch, as launch_batch_solve
@@ -188,12 +214,16 @@ hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, in
         T *r = rate + off;
         int32_t *nx = next ? next + off : nullptr, *hp = hops ? hops + off : nullptr;
         unsigned long long *u = updates_each ? updates_each + b0 : nullptr;
-#define FWX_BATCH_MID(HN, HH)                                                                      \
-    hipLaunchKernelGGL((mid_solve_batch<T, HN, HH>), dim3(cnt), dim3(kMidThreads), 0, s, r, nx, hp, n, stride, \
-                       k_begin, k_end, u)
-        if (hops) FWX_BATCH_MID(true, true);
-        else if (next) FWX_BATCH_MID(true, false);
-        else FWX_BATCH_MID(false, false);
+        PathLog pl;
+        if (traced) { pl.last = plog.last + off; pl.at_col = plog.at_col + off; pl.at_row = plog.at_row + off; }
+#define FWX_BATCH_MID(HN, HH, HL)                                                                  \
+    hipLaunchKernelGGL((mid_solve_batch<T, HN, HH, HL>), dim3(cnt), dim3(kMidThreads), 0, s, r, nx, hp, n, stride, \
+                       k_begin, k_end, u, pl)
+        if (traced && hops) FWX_BATCH_MID(true, true, true);
+        else if (traced) FWX_BATCH_MID(true, false, true);
+        else if (hops) FWX_BATCH_MID(true, true, false);
+        else if (next) FWX_BATCH_MID(true, false, false);
+        else FWX_BATCH_MID(false, false, false);
 #undef FWX_BATCH_MID
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -202,8 +232,8 @@ hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, in
 }
 
 template hipError_t launch_batch_mid<float>(float *, int32_t *, int32_t *, int, int, long long, int, int,
-                                            unsigned long long *, hipStream_t);
+                                            unsigned long long *, hipStream_t, PathLog);
 template hipError_t launch_batch_mid<double>(double *, int32_t *, int32_t *, int, int, long long, int, int,
-                                             unsigned long long *, hipStream_t);
+                                             unsigned long long *, hipStream_t, PathLog);
 
 }  // namespace fwx

@@ -18,7 +18,8 @@ from ._lib import (FWX_ENGINE_AUTO, FWX_ENGINE_FUSED, FWX_ENGINE_PERK, FWX_F32, 
                    FWX_ERR_RCCL, FwxError, FwxOpts, FwxPivots, FwxSlab, check, lib)
 
 __all__ = ["solve", "solve_batch", "dev_solve_batch", "solve_batch_lists", "dev_solve_batch_traced",
-           "dev_exact_paths_batch", "ragged_plan", "solve_ragged", "solve_ragged_lists", "dev_solve_ragged",
+           "dev_exact_paths_batch", "solve_batch_mid", "dev_solve_batch_mid", "solve_batch_mid_lists",
+           "dev_solve_batch_mid_traced", "dev_exact_paths_batch_mid", "ragged_plan", "solve_ragged", "solve_ragged_lists", "dev_solve_ragged",
            "dev_exact_paths_ragged", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
            "dev_solve", "DeviceMatrix", "dev_relax", "dev_panel", "dev_panel_snap",
            "dev_relax_fused", "FusedWorkspace", "Trace", "FWX_FUSED_BLOCK", "device_count",
@@ -189,6 +190,16 @@ def solve_batch_lists(rate, nxt, hops=None, *, items=None, cap=None, device=-1, 
 
     Returns the lists as a list of tuples, one per item -- or (lists, U) with U the per-matrix uint64 array if
     count_updates."""
+    return _solve_batch_lists("fwx_solve_batch_lists", rate, nxt, hops, items, cap, device, count_updates)
+
+
+def solve_batch_mid_lists(rate, nxt, hops=None, *, items=None, cap=None, device=-1, count_updates=False):
+    """solve_batch_lists with the limit at n <= FWX_BATCH_MID_MAX_N (fwx_solve_batch_mid_lists_f64 / _f32); routing
+    by FWX_BATCH_MID_MIN_N as solve_batch_mid.  Same arrays, same lists, same return value."""
+    return _solve_batch_lists("fwx_solve_batch_mid_lists", rate, nxt, hops, items, cap, device, count_updates)
+
+
+def _solve_batch_lists(stem, rate, nxt, hops, items, cap, device, count_updates):
     if nxt is None:
         raise ValueError("the exact lists need next")
     if not (isinstance(rate, np.ndarray) and rate.ndim == 3 and rate.shape[1] == rate.shape[2]):
@@ -207,7 +218,7 @@ def solve_batch_lists(rate, nxt, hops=None, *, items=None, cap=None, device=-1, 
     mat, src, dst = (np.ascontiguousarray(a, dtype=np.int32) for a in items)
     if not (mat.ndim == 1 and mat.shape == src.shape == dst.shape):
         raise ValueError("items must be three equally long one-dimensional sequences (mat, src, dst)")
-    fn = lib().fwx_solve_batch_lists_f64 if rate.dtype == np.float64 else lib().fwx_solve_batch_lists_f32
+    fn = getattr(lib(), stem + ("_f64" if rate.dtype == np.float64 else "_f32"))
     grow = cap is None
     cap = BATCH_LISTS_FIRST_CAP if grow else int(cap)
     kept = (rate.copy(), nxt.copy(), None if hops is None else hops.copy()) if grow else None
@@ -222,20 +233,20 @@ def solve_batch_lists(rate, nxt, hops=None, *, items=None, cap=None, device=-1, 
         m, s, d = (np.ascontiguousarray(a[todo]) for a in (mat, src, dst))
         check(fn(count, n, _np_ptr(arrays[0]), _np_ptr(arrays[1]), _np_ptr(arrays[2]),
                  _np_ptr(each) if arrays[0] is rate else None, len(todo), _np_ptr(m), _np_ptr(s), _np_ptr(d),
-                 _np_ptr(lens), _np_ptr(paths), cap, ctypes.byref(o)), "fwx_solve_batch_lists")
+                 _np_ptr(lens), _np_ptr(paths), cap, ctypes.byref(o)), stem)
         if count == 0 or n == 0:
             lens[:] = _lib.FWX_ERR_INVALID       # nothing was solved: no item lies in the batch
         short = lens == _lib.FWX_ERR_CAPACITY
         bad = (lens < 0) & ~short
         if bad.any():
-            raise FwxError(int(lens[bad][0]), "fwx_solve_batch_lists: item %d" % int(todo[bad][0]))
+            raise FwxError(int(lens[bad][0]), "%s: item %d" % (stem, int(todo[bad][0])))
         for q in np.nonzero(~short)[0]:
             out[todo[q]] = tuple(int(v) for v in paths[q, :lens[q]])
         if not short.any():
             break
         if not grow or cap >= BATCH_LISTS_MAX_CAP:
-            raise FwxError(_lib.FWX_ERR_CAPACITY, "fwx_solve_batch_lists: item %d does not fit cap %d"
-                           % (int(todo[short][0]), cap))
+            raise FwxError(_lib.FWX_ERR_CAPACITY, "%s: item %d does not fit cap %d"
+                           % (stem, int(todo[short][0]), cap))
         cap, todo = min(2 * cap, BATCH_LISTS_MAX_CAP), todo[short]
         arrays = tuple(None if a is None else a.copy() for a in kept)     # solved again from the input
     return (out, each) if count_updates else out
@@ -252,6 +263,19 @@ def dev_solve_batch_traced(rate_t, count, n, trace, *, next_t, hops_t=None, stri
     """fwx_dev_solve_batch_traced: dev_solve_batch over the whole pivot range that also writes the path trace of
     every matrix to `trace` (an object with last / at_col / at_row device int32 arrays, e.g. Trace), laid out like
     next_t: matrix b at element b * stride, pitch n.  Every cell inside a matrix is written, the gaps never."""
+    _dev_solve_batch_traced("fwx_dev_solve_batch_traced", rate_t, count, n, trace, next_t, hops_t, stride, updates_t,
+                            stream)
+
+
+def dev_solve_batch_mid_traced(rate_t, count, n, trace, *, next_t, hops_t=None, stride=None, updates_t=None,
+                               stream=None):
+    """fwx_dev_solve_batch_mid_traced: dev_solve_batch_traced with the limit at n <= FWX_BATCH_MID_MAX_N; routing by
+    FWX_BATCH_MID_MIN_N as solve_batch_mid.  Same arrays, same trace."""
+    _dev_solve_batch_traced("fwx_dev_solve_batch_mid_traced", rate_t, count, n, trace, next_t, hops_t, stride,
+                            updates_t, stream)
+
+
+def _dev_solve_batch_traced(name, rate_t, count, n, trace, next_t, hops_t, stride, updates_t, stream):
     stride = n * n if stride is None else int(stride)
     need = (count - 1) * stride + n * n if count > 0 else 0
     assert rate_t.is_cuda and rate_t.is_contiguous() and rate_t.numel() >= need
@@ -261,11 +285,10 @@ def dev_solve_batch_traced(rate_t, count, n, trace, *, next_t, hops_t=None, stri
     assert next_t is not None
     assert updates_t is None or (updates_t.element_size() == 8 and updates_t.numel() >= count)
     vp = ctypes.c_void_p
-    check(lib().fwx_dev_solve_batch_traced(
+    check(getattr(lib(), name)(
         count, n, _tensor_dtype_code(rate_t), vp(rate_t.data_ptr()), vp(next_t.data_ptr()),
         vp(hops_t.data_ptr()) if hops_t is not None else None, stride, _trace_of(trace, need),
-        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)),
-        "fwx_dev_solve_batch_traced")
+        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)), name)
 
 
 def dev_exact_paths_batch(next0_t, count, n, trace, mat_t, src_t, dst_t, cap, *, stride=None, stream=None):
@@ -273,6 +296,18 @@ def dev_exact_paths_batch(next0_t, count, n, trace, mat_t, src_t, dst_t, cap, *,
     dev_solve_batch_traced solved; next0_t is the caller's copy of the UNSOLVED next-hop array (same layout).
     Asynchronous on `stream`.  Returns (len_t, path_t): device int32 arrays of shape (items,) and (items, cap);
     len_t[q] is the length of list q, FWX_ERR_CAPACITY or FWX_ERR_INVALID, item by item."""
+    return _dev_exact_paths_batch("fwx_dev_exact_paths_batch", next0_t, count, n, trace, mat_t, src_t, dst_t, cap,
+                                  stride, stream)
+
+
+def dev_exact_paths_batch_mid(next0_t, count, n, trace, mat_t, src_t, dst_t, cap, *, stride=None, stream=None):
+    """fwx_dev_exact_paths_batch_mid: dev_exact_paths_batch over a batch that dev_solve_batch_mid_traced solved,
+    n <= FWX_BATCH_MID_MAX_N."""
+    return _dev_exact_paths_batch("fwx_dev_exact_paths_batch_mid", next0_t, count, n, trace, mat_t, src_t, dst_t, cap,
+                                  stride, stream)
+
+
+def _dev_exact_paths_batch(name, next0_t, count, n, trace, mat_t, src_t, dst_t, cap, stride, stream):
     stride = n * n if stride is None else int(stride)
     need = (count - 1) * stride + n * n if count > 0 else 0
     assert next0_t.is_cuda and next0_t.is_contiguous() and _dtype_name(next0_t) == "int32" and next0_t.numel() >= need
@@ -283,10 +318,10 @@ def dev_exact_paths_batch(next0_t, count, n, trace, mat_t, src_t, dst_t, cap, *,
     path_t = _empty_like_device(mat_t, (items, cap), "int32")
     scratch = _empty_like_device(mat_t, (max(items * 3 * (n + 2), 1),), "int32")
     vp = ctypes.c_void_p
-    check(lib().fwx_dev_exact_paths_batch(
+    check(getattr(lib(), name)(
         count, n, stride, vp(next0_t.data_ptr()), _trace_of(trace, need), items, vp(mat_t.data_ptr()),
         vp(src_t.data_ptr()), vp(dst_t.data_ptr()), vp(len_t.data_ptr()), vp(path_t.data_ptr()), cap,
-        vp(scratch.data_ptr()), _stream_ptr(stream, mat_t)), "fwx_dev_exact_paths_batch")
+        vp(scratch.data_ptr()), _stream_ptr(stream, mat_t)), name)
     if not _is_torch(mat_t):
         len_t._scratch = scratch              # stays alive until the results are read
     return len_t, path_t

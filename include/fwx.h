@@ -288,6 +288,34 @@ int fwx_solve_batch_lists_f32(int32_t count, int32_t n, float *rate, int32_t *ne
  * the budget give it right now (FWX_ERR_INVALID for n < 0 or cap < 1).  Needs no device.  Not for production use. */
 int64_t fwx_test_batch_lists_chunk(int32_t n, int32_t cap);
 
+/* ---- batched mid-size solves with the exact `_path` lists -------------------------------------------------
+ * The three families above with the limit at FWX_BATCH_MID_MAX_N (256): a batch of 20 x 12 markets gets the lists
+ * the reference would print, not only rate, next and hops.  The contracts are those of fwx_dev_solve_batch_traced,
+ * fwx_dev_exact_paths_batch and fwx_solve_batch_lists_*, word for word -- the statuses decided before any device
+ * call (FWX_ERR_UNSUPPORTED: n > FWX_BATCH_MID_MAX_N), whole pivot range only, next required, hops optional, every
+ * cell of the n x n part of the three trace arrays written by the solve and the gap never, the capacity rule, items
+ * judged one by one, scratch of items * FWX_EXACT_SCRATCH_INTS(n) int32, chunks by FWX_BATCH_LISTS_CHUNK.
+ * Routing by FWX_BATCH_MID_MIN_N as for fwx_solve_batch_mid_*: orders below it run the traced tiers above, orders
+ * from it up the mid tier, which keeps the trace in device memory beside the matrix (no LDS copy: the f64 + next +
+ * hops form already fills the CU's LDS).  No cell of any output, the trace arrays included, depends on it.  The
+ * entry points above keep refusing n > FWX_BATCH_MAX_N.
+ * Cost (MI355X, f64 + next + hops on market inputs): profiles/r21_batch_mid_lists.txt.                        */
+int fwx_dev_solve_batch_mid_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next,
+                                   int32_t *hops, int64_t stride, const struct fwx_trace *trace,
+                                   unsigned long long *d_updates_each, void *stream);
+int fwx_dev_exact_paths_batch_mid(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                                  const struct fwx_trace *trace, int32_t items, const int32_t *mat,
+                                  const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                                  int32_t cap, int32_t *scratch, void *stream);
+int fwx_solve_batch_mid_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                                  uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                  const fwx_opts *opts);
+int fwx_solve_batch_mid_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                                  uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                  const fwx_opts *opts);
+
 /* ---- ragged batched small solves: matrices of DIFFERENT orders in one call --------------------------------
  * A price history does not have one order: the vertex set grows as exchanges and currencies first appear, and venue
  * groups differ in size.  A ragged batch is `count` matrices; matrix b has order n_each[b], 0 <= n_each[b] <=
