@@ -139,6 +139,17 @@ SIGNATURES = {
                                                   c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
     "fwx_solve_ragged_lists_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                                   c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
+    "fwx_ragged_mid_plan": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "fwx_solve_ragged_mid_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_ragged_mid_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_dev_solve_ragged_mid": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                ctypes.POINTER(FwxTrace), c_vp, c_vp]),
+    "fwx_dev_exact_paths_ragged_mid": (ctypes.c_int, [c_i32, c_vp, c_vp, c_i32, c_vp, ctypes.POINTER(FwxTrace), c_i32,
+                                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "fwx_solve_ragged_mid_lists_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                      c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_ragged_mid_lists_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                      c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
     "fwx_follow_path": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i32, c_vp, c_i32]),
     "fwx_matrix_create": (ctypes.c_int, [ctypes.POINTER(c_vp), c_i32, c_i32, c_i32, c_i32, c_i32]),
     "fwx_matrix_upload": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),

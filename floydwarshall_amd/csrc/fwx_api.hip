@@ -532,16 +532,19 @@ int ragged_orders(int32_t count, const int32_t *n_each, int32_t &n_max)
     return FWX_OK;
 }
 
-// fwx_ragged_plan for orders that ragged_orders accepted and that are all <= FWX_BATCH_MAX_N: the packed offsets
-// (count + 1 entries), the matrices with n >= 1 grouped by tier -- wave (n <= wave_max_n), 64-wide, 128-wide -- and
-// within a tier by descending order, ties by ascending index (a counting sort over the orders: the tier is monotone
-// in the order), the rest of `order` -1.  Any output may be null.
-void ragged_plan(int32_t count, const int32_t *n_each, int wave_max_n, int64_t *offset, int32_t *order,
-                 int32_t tier_count[3])
+// fwx_ragged_plan (ntiers = 3; the orders all <= FWX_BATCH_MAX_N) and fwx_ragged_mid_plan (ntiers = 4; all <=
+// FWX_BATCH_MID_MAX_N) for orders that ragged_orders accepted: the packed offsets (count + 1 entries), the matrices
+// with n >= 1 grouped by tier -- wave (n <= wave_max_n), 64-wide, 128-wide and, with four tiers, mid (n >= mid_min_n,
+// which wins where the wave tier claims the order too) -- and within a tier by descending order, ties by ascending
+// index (a counting sort over the orders: the tier is monotone in the order), the rest of `order` -1.  tier_count
+// has ntiers entries.  Any output may be null.
+void ragged_plan(int32_t count, const int32_t *n_each, int wave_max_n, int ntiers, int mid_min_n, int64_t *offset,
+                 int32_t *order, int32_t *tier_count)
 {
-    auto tier_of = [&](int n) { return n <= wave_max_n ? 0 : n <= 64 ? 1 : 2; };
-    int64_t at[FWX_BATCH_MAX_N + 2] = {0};      // at[n]: matrices of order n, then where the next one of order n goes
-    int32_t tiers[3] = {0, 0, 0};
+    const int max_n = ntiers == 4 ? FWX_BATCH_MID_MAX_N : FWX_BATCH_MAX_N;
+    auto tier_of = [&](int n) { return ntiers == 4 && n >= mid_min_n ? 3 : n <= wave_max_n ? 0 : n <= 64 ? 1 : 2; };
+    int64_t at[FWX_BATCH_MID_MAX_N + 2] = {0};  // at[n]: matrices of order n, then where the next one of order n goes
+    int32_t tiers[4] = {0, 0, 0, 0};
     int64_t cells = 0;
     for (int32_t b = 0; b < count; ++b) {
         const int n = n_each[b];
@@ -550,11 +553,11 @@ void ragged_plan(int32_t count, const int32_t *n_each, int wave_max_n, int64_t *
         if (n >= 1) { ++at[n]; ++tiers[tier_of(n)]; }
     }
     if (offset) offset[count] = cells;
-    if (tier_count) { tier_count[0] = tiers[0]; tier_count[1] = tiers[1]; tier_count[2] = tiers[2]; }
+    if (tier_count) std::copy(tiers, tiers + ntiers, tier_count);
     if (!order) return;
     int64_t pos = 0;
-    for (int tier = 0; tier < 3; ++tier)
-        for (int n = FWX_BATCH_MAX_N; n >= 1; --n)
+    for (int tier = 0; tier < ntiers; ++tier)
+        for (int n = max_n; n >= 1; --n)
             if (tier_of(n) == tier) { const int64_t c = at[n]; at[n] = pos; pos += c; }
     for (int32_t b = 0; b < count; ++b)
         if (n_each[b] >= 1) order[at[n_each[b]]++] = b;
@@ -571,6 +574,23 @@ int dev_solve_ragged(int32_t count, T *rate, int32_t *next, int32_t *hops, const
     if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
     FWX_HIP(e);
     return FWX_OK;
+}
+
+// The four-tier plan (fwx_dev_solve_ragged_mid, fwx_solve_ragged_mid_*): the mid tier first -- its workgroups run
+// longest -- then the three small tiers as dev_solve_ragged launches them, all on s.
+template <typename T>
+int dev_solve_ragged_mid(int32_t count, T *rate, int32_t *next, int32_t *hops, const int32_t *d_n_each,
+                         const int64_t *d_offset, const int32_t *d_order, const int32_t tier_count[4],
+                         unsigned long long *d_updates_each, hipStream_t s, const fwx::PathLog &plog = fwx::PathLog())
+{
+    const long long small = (long long)tier_count[0] + tier_count[1] + tier_count[2];
+    const hipError_t e = fwx::launch_ragged_mid<T>(rate, next, hops, count, d_n_each, d_offset, d_order + small,
+                                                   tier_count[3], d_updates_each, s, plog);
+    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
+    FWX_HIP(e);
+    if (small == 0) return FWX_OK;
+    return dev_solve_ragged<T>(count, rate, next, hops, d_n_each, d_offset, d_order, tier_count, d_updates_each, s,
+                               plog);
 }
 
 // What fwx_solve_batch_lists_* adds to a batch solve: the exact lists of `items` triples, host arrays.
@@ -591,7 +611,10 @@ struct BatchLists {
 // list -- is built here and goes to the context's workspace behind the counters, in one copy.
 // mid (fwx_solve_batch_mid_*): the limit on n is FWX_BATCH_MID_MAX_N and dev_solve_batch routes by
 // FWX_BATCH_MID_MIN_N; everything else is the plain batch solve.  With ls (fwx_solve_batch_mid_lists_*) the mid tier
-// writes the trace itself and the walk is the same launch_exact_batch.  Not ragged.
+// writes the trace itself and the walk is the same launch_exact_batch.
+// ragged && mid (fwx_solve_ragged_mid_*, fwx_solve_ragged_mid_lists_*): the ragged batch with the limit at
+// FWX_BATCH_MID_MAX_N and the four-tier plan (FWX_BATCH_MID_MIN_N read here, by the plan); the workspace layout and
+// the walk are the ragged ones.
 template <typename T>
 int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
                      const fwx_opts *o, const BatchLists *ls = nullptr, bool ragged = false,
@@ -619,13 +642,13 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
 
     // the ragged plan, packed for one copy: count offsets, then count orders and the tier list (count) as int32
     std::vector<int64_t> plan;
-    int32_t tiers[3] = {0, 0, 0};
+    int32_t tiers[4] = {0, 0, 0, 0};
     size_t cells = (size_t)count * (size_t)n * (size_t)n;
     if (ragged) {
         std::vector<int64_t> offs((size_t)count + 1);
         plan.resize(2 * (size_t)count);
         int32_t *h_n = (int32_t *)(plan.data() + count), *h_order = h_n + count;
-        ragged_plan(count, n_each, batch_wave_max_n(), offs.data(), h_order, tiers);
+        ragged_plan(count, n_each, batch_wave_max_n(), mid ? 4 : 3, batch_mid_min_n(), offs.data(), h_order, tiers);
         std::copy(offs.begin(), offs.end() - 1, plan.begin());
         std::copy(n_each, n_each + count, h_n);
         cells = (size_t)offs[(size_t)count];
@@ -703,7 +726,10 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
         FWX_HIP(hipMemcpyAsync(d_next0, d_next, b_idx, hipMemcpyDeviceToDevice, s));
     }
 
-    if (ragged)
+    if (ragged && mid)
+        rc = dev_solve_ragged_mid<T>(count, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, d_n_each, d_offset,
+                                     d_order, tiers, (unsigned long long *)d_upd, s, plog);
+    else if (ragged)
         rc = dev_solve_ragged<T>(count, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, d_n_each, d_offset, d_order,
                                  tiers, (unsigned long long *)d_upd, s, plog);
     else
@@ -1531,7 +1557,7 @@ int fwx_ragged_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, i
         int32_t n_max = 0;
         if (count < 0 || (count > 0 && !n_each) || ragged_orders(count, n_each, n_max)) return FWX_ERR_INVALID;
         if (n_max > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
-        ragged_plan(count, n_each, batch_wave_max_n(), offset_out, order_out, tier_count_out);
+        ragged_plan(count, n_each, batch_wave_max_n(), 3, 0, offset_out, order_out, tier_count_out);
         return FWX_OK;
     });
 }
@@ -1575,16 +1601,21 @@ int fwx_solve_ragged_lists_f32(int32_t count, const int32_t *n_each, float *rate
 }
 
 // The device forms cannot read the orders: what they can decide is decided from the host arguments, and the kernels
-// leave a matrix alone whose order does not fit the tier it is listed in.
-int fwx_dev_solve_ragged(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                         const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
-                         const int32_t tier_count[3], const fwx_trace *trace, unsigned long long *d_updates_each,
-                         void *stream)
+// leave a matrix alone whose order does not fit the tier it is listed in.  fwx_dev_solve_ragged (ntiers = 3) and
+// fwx_dev_solve_ragged_mid (ntiers = 4): one contract, the number of tiers apart.
+static int dev_solve_ragged_any(int ntiers, int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                                const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                                const int32_t *tier_count, const fwx_trace *trace,
+                                unsigned long long *d_updates_each, void *stream)
 {
     return fwxi::guarded([&]() -> int {
         if (count < 0 || !tier_count || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
-        const int64_t listed = (int64_t)tier_count[0] + tier_count[1] + tier_count[2];
-        if (tier_count[0] < 0 || tier_count[1] < 0 || tier_count[2] < 0 || listed > count) return FWX_ERR_INVALID;
+        int64_t listed = 0;
+        for (int t = 0; t < ntiers; ++t) {
+            if (tier_count[t] < 0) return FWX_ERR_INVALID;
+            listed += tier_count[t];
+        }
+        if (listed > count) return FWX_ERR_INVALID;
         if (listed == 0) return FWX_OK;
         if (!rate || !d_n_each || !d_offset || !d_order || (hops && !next)) return FWX_ERR_INVALID;
         if (trace && (!next || !trace->last || !trace->at_col || !trace->at_row)) return FWX_ERR_INVALID;
@@ -1596,6 +1627,13 @@ int fwx_dev_solve_ragged(int32_t count, int32_t dtype, void *rate, int32_t *next
             plog.at_row = trace->at_row;
         }
         hipStream_t s = (hipStream_t)stream;
+        if (ntiers == 4) {
+            if (dtype == FWX_F64)
+                return dev_solve_ragged_mid<double>(count, (double *)rate, next, hops, d_n_each, d_offset, d_order,
+                                                    tier_count, d_updates_each, s, plog);
+            return dev_solve_ragged_mid<float>(count, (float *)rate, next, hops, d_n_each, d_offset, d_order,
+                                               tier_count, d_updates_each, s, plog);
+        }
         if (dtype == FWX_F64)
             return dev_solve_ragged<double>(count, (double *)rate, next, hops, d_n_each, d_offset, d_order, tier_count,
                                             d_updates_each, s, plog);
@@ -1604,10 +1642,29 @@ int fwx_dev_solve_ragged(int32_t count, int32_t dtype, void *rate, int32_t *next
     });
 }
 
-int fwx_dev_exact_paths_ragged(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
-                               const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
-                               const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
-                               int32_t cap, int32_t *scratch, void *stream)
+int fwx_dev_solve_ragged(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                         const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                         const int32_t tier_count[3], const fwx_trace *trace, unsigned long long *d_updates_each,
+                         void *stream)
+{
+    return dev_solve_ragged_any(3, count, dtype, rate, next, hops, d_n_each, d_offset, d_order, tier_count, trace,
+                                d_updates_each, stream);
+}
+
+int fwx_dev_solve_ragged_mid(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                             const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                             const int32_t tier_count[4], const fwx_trace *trace,
+                             unsigned long long *d_updates_each, void *stream)
+{
+    return dev_solve_ragged_any(4, count, dtype, rate, next, hops, d_n_each, d_offset, d_order, tier_count, trace,
+                                d_updates_each, stream);
+}
+
+// fwx_dev_exact_paths_ragged and fwx_dev_exact_paths_ragged_mid: one walk, the limit apart.
+static int dev_exact_paths_ragged_any(int32_t max_n, int32_t count, const int32_t *d_n_each, const int64_t *d_offset,
+                                      int32_t n_max, const int32_t *next0, const fwx_trace *trace, int32_t items,
+                                      const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
+                                      int32_t *path_out, int32_t cap, int32_t *scratch, void *stream)
 {
     return fwxi::guarded([&]() -> int {
         if (count < 0 || n_max < 0 || items < 0) return FWX_ERR_INVALID;
@@ -1615,7 +1672,7 @@ int fwx_dev_exact_paths_ragged(int32_t count, const int32_t *d_n_each, const int
         if (!d_n_each || !d_offset || !next0 || !trace || !trace->last || !trace->at_col || !trace->at_row ||
             cap < 1 || !mat || !src || !dst || !len_out || !path_out || !scratch)
             return FWX_ERR_INVALID;
-        if (n_max > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
+        if (n_max > max_n) return FWX_ERR_UNSUPPORTED;
         if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
         fwx::PathLog plog;
         plog.last = trace->last;
@@ -1623,6 +1680,74 @@ int fwx_dev_exact_paths_ragged(int32_t count, const int32_t *d_n_each, const int
         plog.at_row = trace->at_row;
         return launch_exact_ragged(count, d_n_each, d_offset, n_max, next0, plog, items, mat, src, dst, len_out,
                                    path_out, cap, scratch, (hipStream_t)stream);
+    });
+}
+
+int fwx_dev_exact_paths_ragged(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                               const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
+                               const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                               int32_t cap, int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_ragged_any(FWX_BATCH_MAX_N, count, d_n_each, d_offset, n_max, next0, trace, items, mat, src,
+                                      dst, len_out, path_out, cap, scratch, stream);
+}
+
+int fwx_dev_exact_paths_ragged_mid(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                                   const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
+                                   const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                                   int32_t cap, int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_ragged_any(FWX_BATCH_MID_MAX_N, count, d_n_each, d_offset, n_max, next0, trace, items, mat,
+                                      src, dst, len_out, path_out, cap, scratch, stream);
+}
+
+int fwx_ragged_mid_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
+                        int32_t tier_count_out[4])
+{
+    return fwxi::guarded([&]() -> int {
+        int32_t n_max = 0;
+        if (count < 0 || (count > 0 && !n_each) || ragged_orders(count, n_each, n_max)) return FWX_ERR_INVALID;
+        if (n_max > FWX_BATCH_MID_MAX_N) return FWX_ERR_UNSUPPORTED;
+        ragged_plan(count, n_each, batch_wave_max_n(), 4, batch_mid_min_n(), offset_out, order_out, tier_count_out);
+        return FWX_OK;
+    });
+}
+
+int fwx_solve_ragged_mid_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                             uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<double>(count, 0, rate, next, hops, updates_each, opts, nullptr, true, n_each, true);
+    });
+}
+
+int fwx_solve_ragged_mid_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                             uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<float>(count, 0, rate, next, hops, updates_each, opts, nullptr, true, n_each, true);
+    });
+}
+
+int fwx_solve_ragged_mid_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                   const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<double>(count, 0, rate, next, hops, updates_each, opts, &ls, true, n_each, true);
+    });
+}
+
+int fwx_solve_ragged_mid_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                   const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<float>(count, 0, rate, next, hops, updates_each, opts, &ls, true, n_each, true);
     });
 }
 

@@ -526,6 +526,8 @@ inline int batch_wave_max_n()
 // FWX_BATCH_MID_MIN_N are forwarded to the tiers above, orders from it up to FWX_BATCH_MID_MAX_N run the mid
 // tier (fwx_mid.hip).  An integer 1 ... FWX_BATCH_MAX_N + 1, read on every call; any other value: the default,
 // FWX_BATCH_MAX_N + 1 (only what the small tiers cannot take).  No result bit depends on it.
+// fwx_ragged_mid_plan and the host forms fwx_solve_ragged_mid_* read it too, as the boundary of the plan's fourth tier
+// (the plan reads it and only the plan: the device form takes the tier counts it is given).
 #define FWX_BATCH_MID_MIN_N_DEFAULT (FWX_BATCH_MAX_N + 1)
 inline int batch_mid_min_n()
 {

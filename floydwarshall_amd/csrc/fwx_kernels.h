@@ -176,6 +176,16 @@ hipError_t launch_ragged_solve(T *rate, int32_t *next, int32_t *hops, int count,
                                const int64_t *offset, const int32_t *order, const int32_t tier_count[3],
                                unsigned long long *updates_each, hipStream_t s, PathLog plog = PathLog());
 
+// The fourth tier of a ragged batch (fwx_mid.hip): the `listed` matrices whose ids stand in `order` (device; the
+// mid tier's part of what fwx_ragged_mid_plan gives), each of an order 1 ... FWX_MID_N, one workgroup per matrix on
+// launch_batch_mid's body.  Index arrays, layout, counters and plog as launch_ragged_solve.  An id outside
+// [0, count) or an order outside 1 ... FWX_MID_N leaves its workgroup idle; a small order is solved like any other.
+// One launch per 2^21 matrices.
+template <typename T>
+hipError_t launch_ragged_mid(T *rate, int32_t *next, int32_t *hops, int count, const int32_t *n_each,
+                             const int64_t *offset, const int32_t *order, long long listed,
+                             unsigned long long *updates_each, hipStream_t s, PathLog plog = PathLog());
+
 template <typename T>
 hipError_t launch_snapshot_row(T *dst, const T *src, int32_t *hdst, const int32_t *hsrc, int n,
                                hipStream_t s);

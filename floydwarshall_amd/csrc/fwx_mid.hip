@@ -1,4 +1,6 @@
-// fwx_mid.hip -- the mid tier of the batched solves: `count` matrices of one order n <= FWX_MID_N (256), one
+// fwx_mid.hip -- the mid tier of the batched solves: `count` matrices of order n <= FWX_MID_N (256) -- one order for
+// the whole batch (mid_solve_batch) or an order and an offset per matrix (mid_solve_ragged, the fourth tier of the
+// ragged batch); both run the one body described here -- one
 // workgroup per matrix, the matrix RESIDENT IN GLOBAL MEMORY (a 256 x 256 matrix with next and hops is 1 MiB: it
 // fits neither registers nor the CU's 160 KiB of LDS).  Pivots are taken FWX_MID_B at a time from time-k snapshots
 // held in LDS -- the fused engine's exactness argument inside one workgroup.
@@ -33,7 +35,9 @@
 //   2. sweep: a win stores last = k0 + (the last winning t) with next and hops.
 // Over the whole range every cell of at_row / at_col is written by exactly one panel load.
 // No communication between workgroups, no grid barrier, no spin-wait; every barrier is reached by all 1024 threads
-// and its trip count is a function of (n, k_begin, k_end, B) alone.
+// and its trip count is a function of (n, k_begin, k_end, B) alone.  The ragged kernel's two early exits (an id
+// outside the batch, an order outside 1 .. FWX_MID_N) are workgroup-uniform and come before the first barrier: a
+// plan that does not belong to the arrays idles workgroups, it cannot hang or misplace one.
 //
 // Geometry: 1024 threads; thread (rg, c) = (tid / CW, tid % CW) with CW = n rounded up to a multiple of 64, so a wave
 // never straddles two row groups (rg is wave-uniform) and at most 63 columns plus one wave idle.  In the sweep a
@@ -63,10 +67,14 @@ static_assert(kMidB >= 1 && kMidB <= 16 && (kMidB & (kMidB - 1)) == 0,
 constexpr int kMidPitch = FWX_MID_N + 4;
 constexpr int kMidRows = 4;                   // sweep: global loads in flight per thread
 
+// The whole solve of ONE matrix by the workgroup that calls it: rate / next / hops / the three trace arrays of plog
+// point at the matrix's first element (pitch n), pivots [k_begin, k_end), U added to updates[slot] (updates may be nullptr).  n and
+// the range are workgroup-uniform.  Shared by mid_solve_batch (matrix blockIdx.x of a uniform batch) and
+// mid_solve_ragged (its own order and offset per workgroup); inlined into both, everything passed by value.
 template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
-__global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
-                                                               long long stride, int k_begin, int k_end,
-                                                               unsigned long long *updates, PathLog plog)
+__device__ __forceinline__ void mid_solve_body(T *rate, int32_t *next, int32_t *hops, int32_t *last, int32_t *at_row,
+                                               int32_t *at_col, int n, int k_begin, int k_end,
+                                               unsigned long long *updates, unsigned int slot)
 {
     static_assert(HAS_NEXT || !HAS_LAST, "the trace goes with next");
     constexpr int B = kMidB, P = kMidPitch;
@@ -74,13 +82,6 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
     __shared__ int32_t WN[HAS_NEXT ? B : 1][HAS_NEXT ? P : 1], CN[HAS_NEXT ? B : 1][HAS_NEXT ? P : 1];
     __shared__ int32_t WH[HAS_HOPS ? B : 1][HAS_HOPS ? P : 1], CH[HAS_HOPS ? B : 1][HAS_HOPS ? P : 1];
     __shared__ unsigned int s_cnt;
-
-    const size_t off = (size_t)blockIdx.x * (size_t)stride;
-    rate += off;
-    if constexpr (HAS_NEXT) next += off;
-    if constexpr (HAS_HOPS) hops += off;
-    int32_t *last = nullptr, *at_row = nullptr, *at_col = nullptr;
-    if constexpr (HAS_LAST) { last = plog.last + off; at_row = plog.at_row + off; at_col = plog.at_col + off; }
 
     const int tid = threadIdx.x;
     const int cw = (n + 63) & ~63;                            // 64 .. 256
@@ -191,8 +192,49 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t 
     if (updates) {
         if (mine && (tid & 63) == 0) atomicAdd(&s_cnt, mine);
         __syncthreads();
-        if (tid == 0 && s_cnt) atomicAdd(&updates[blockIdx.x], (unsigned long long)s_cnt);
+        if (tid == 0 && s_cnt) atomicAdd(&updates[slot], (unsigned long long)s_cnt);
     }
+}
+
+// Uniform batch: workgroup b on matrix b, at b * stride.
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
+__global__ __launch_bounds__(kMidThreads) void mid_solve_batch(T *rate, int32_t *next, int32_t *hops, int n,
+                                                               long long stride, int k_begin, int k_end,
+                                                               unsigned long long *updates, PathLog plog)
+{
+    const size_t off = (size_t)blockIdx.x * (size_t)stride;
+    mid_solve_body<T, HAS_NEXT, HAS_HOPS, HAS_LAST>(rate + off, HAS_NEXT ? next + off : nullptr,
+                                                    HAS_HOPS ? hops + off : nullptr,
+                                                    HAS_LAST ? plog.last + off : nullptr,
+                                                    HAS_LAST ? plog.at_row + off : nullptr,
+                                                    HAS_LAST ? plog.at_col + off : nullptr, n, k_begin, k_end,
+                                                    updates, blockIdx.x);
+}
+
+// Ragged batch, mid tier: workgroup w of the launch on matrix id = order[w], of order n_each[id], at element
+// offset[id] of every array, pitch n_each[id], whole pivot range; U goes to updates[id].  `order` is the mid tier's part
+// of a four-tier plan (fwx_ragged_mid_plan).  The three index loads go through workgroup-uniform addresses (scalar
+// loads), so n stays a scalar and every trip count of the body one as well.  An id outside [0, count) or an order
+// outside [1, FWX_MID_N] (a plan that does not belong to these arrays) makes the whole workgroup leave here -- both
+// tests are workgroup-uniform and come before the body's first barrier and first memory access, so all 1024 threads
+// leave or none does.  The tile holds every order from 1 up: a small matrix listed here is solved, not skipped.
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
+__global__ __launch_bounds__(kMidThreads) void mid_solve_ragged(T *rate, int32_t *next, int32_t *hops, int count,
+                                                                const int32_t *n_each, const int64_t *offset,
+                                                                const int32_t *order, unsigned long long *updates,
+                                                                PathLog plog)
+{
+    const int id = order[blockIdx.x];
+    if ((unsigned)id >= (unsigned)count) return;              // workgroup-uniform, before any barrier
+    const int n = n_each[id];
+    if (n <= 0 || n > FWX_MID_N) return;
+    const size_t off = (size_t)offset[id];
+    mid_solve_body<T, HAS_NEXT, HAS_HOPS, HAS_LAST>(rate + off, HAS_NEXT ? next + off : nullptr,
+                                                    HAS_HOPS ? hops + off : nullptr,
+                                                    HAS_LAST ? plog.last + off : nullptr,
+                                                    HAS_LAST ? plog.at_row + off : nullptr,
+                                                    HAS_LAST ? plog.at_col + off : nullptr, n, 0, n,
+                                                    updates, (unsigned int)id);
 }
 
 }  // namespace
@@ -230,6 +272,40 @@ hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, in
     }
     return hipSuccess;
 }
+
+template <typename T>
+hipError_t launch_ragged_mid(T *rate, int32_t *next, int32_t *hops, int count, const int32_t *n_each,
+                             const int64_t *offset, const int32_t *order, long long listed,
+                             unsigned long long *updates_each, hipStream_t s, PathLog plog)
+{
+    if (count < 0 || listed < 0 || listed > count || (hops && !next)) return hipErrorInvalidValue;
+    if (listed == 0) return hipSuccess;
+    const bool traced = plog.last != nullptr;
+    if (!rate || !n_each || !offset || !order || (traced && (!next || !plog.at_col || !plog.at_row)))
+        return hipErrorInvalidValue;
+    constexpr int kChunk = 1 << 21;           // workgroups per launch, as launch_batch_mid
+    for (long long b0 = 0; b0 < listed; b0 += kChunk) {
+        const int cnt = (int)std::min<long long>(kChunk, listed - b0);
+        const int32_t *ord = order + b0;
+#define FWX_RAGGED_MID(HN, HH, HL)                                                                 \
+    hipLaunchKernelGGL((mid_solve_ragged<T, HN, HH, HL>), dim3(cnt), dim3(kMidThreads), 0, s, rate, next, hops, count, \
+                       n_each, offset, ord, updates_each, plog)
+        if (traced && hops) FWX_RAGGED_MID(true, true, true);
+        else if (traced) FWX_RAGGED_MID(true, false, true);
+        else if (hops) FWX_RAGGED_MID(true, true, false);
+        else if (next) FWX_RAGGED_MID(true, false, false);
+        else FWX_RAGGED_MID(false, false, false);
+#undef FWX_RAGGED_MID
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template hipError_t launch_ragged_mid<float>(float *, int32_t *, int32_t *, int, const int32_t *, const int64_t *,
+                                             const int32_t *, long long, unsigned long long *, hipStream_t, PathLog);
+template hipError_t launch_ragged_mid<double>(double *, int32_t *, int32_t *, int, const int32_t *, const int64_t *,
+                                              const int32_t *, long long, unsigned long long *, hipStream_t, PathLog);
 
 template hipError_t launch_batch_mid<float>(float *, int32_t *, int32_t *, int, int, long long, int, int,
                                             unsigned long long *, hipStream_t, PathLog);

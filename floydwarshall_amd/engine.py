@@ -20,7 +20,8 @@ from ._lib import (FWX_ENGINE_AUTO, FWX_ENGINE_FUSED, FWX_ENGINE_PERK, FWX_F32, 
 __all__ = ["solve", "solve_batch", "dev_solve_batch", "solve_batch_lists", "dev_solve_batch_traced",
            "dev_exact_paths_batch", "solve_batch_mid", "dev_solve_batch_mid", "solve_batch_mid_lists",
            "dev_solve_batch_mid_traced", "dev_exact_paths_batch_mid", "ragged_plan", "solve_ragged", "solve_ragged_lists", "dev_solve_ragged",
-           "dev_exact_paths_ragged", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
+           "dev_exact_paths_ragged", "ragged_mid_plan", "solve_ragged_mid", "solve_ragged_mid_lists",
+           "dev_solve_ragged_mid", "dev_exact_paths_ragged_mid", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
            "dev_solve", "DeviceMatrix", "dev_relax", "dev_panel", "dev_panel_snap",
            "dev_relax_fused", "FusedWorkspace", "Trace", "FWX_FUSED_BLOCK", "device_count",
            "FwxError", "FWX_ENGINE_AUTO", "FWX_ENGINE_PERK", "FWX_ENGINE_FUSED",
@@ -332,15 +333,24 @@ def ragged_plan(n_each):
     (int64, count + 1 entries, the total last), the matrices with n >= 1 grouped by tier (wave, 64-wide, 128-wide)
     and by descending order within a tier (int32, count entries, -1 past the listed ones), and the three tier
     sizes (int32).  Needs no device."""
+    return _ragged_plan("fwx_ragged_plan", 3, n_each)
+
+
+def ragged_mid_plan(n_each):
+    """fwx_ragged_mid_plan: ragged_plan for orders up to FWX_BATCH_MID_MAX_N, with FOUR tiers -- wave, 64-wide,
+    128-wide, mid (orders from FWX_BATCH_MID_MIN_N up) -- and four tier sizes.  Needs no device."""
+    return _ragged_plan("fwx_ragged_mid_plan", 4, n_each)
+
+
+def _ragged_plan(name, ntiers, n_each):
     n_each = np.ascontiguousarray(n_each, dtype=np.int32)
     if n_each.ndim != 1:
         raise ValueError("n_each must be a one-dimensional sequence of orders")
     count = len(n_each)
     offset = np.zeros(count + 1, dtype=np.int64)
     order = np.full(count, -1, dtype=np.int32)
-    tiers = np.zeros(3, dtype=np.int32)
-    check(lib().fwx_ragged_plan(count, _np_ptr(n_each), _np_ptr(offset), _np_ptr(order), _np_ptr(tiers)),
-          "fwx_ragged_plan")
+    tiers = np.zeros(ntiers, dtype=np.int32)
+    check(getattr(lib(), name)(count, _np_ptr(n_each), _np_ptr(offset), _np_ptr(order), _np_ptr(tiers)), name)
     return offset, order, tiers
 
 
@@ -393,15 +403,25 @@ def solve_ragged(rates, nexts=None, hops=None, *, device=-1, count_updates=False
     as `solve` of that matrix alone would leave it.
 
     Returns the per-matrix U as a uint64 array if count_updates else None."""
+    return _solve_ragged("fwx_solve_ragged", rates, nexts, hops, device, count_updates)
+
+
+def solve_ragged_mid(rates, nexts=None, hops=None, *, device=-1, count_updates=False):
+    """solve_ragged with the limit at FWX_BATCH_MID_MAX_N (fwx_solve_ragged_mid_f64 / _f32): orders 0 ... 256 in one
+    call, four tiers, routing by FWX_BATCH_MID_MIN_N.  Same arrays, same return value."""
+    return _solve_ragged("fwx_solve_ragged_mid", rates, nexts, hops, device, count_updates)
+
+
+def _solve_ragged(stem, rates, nexts, hops, device, count_updates):
     rates = list(rates)
     nexts = None if nexts is None else list(nexts)
     hops = None if hops is None else list(hops)
     n_each, rate, nxt, hp = _pack_ragged(rates, nexts, hops)
     o, _ = _opts(device, FWX_ENGINE_AUTO)
     each = np.zeros(len(n_each), dtype=np.uint64) if count_updates else None
-    fn = lib().fwx_solve_ragged_f64 if rate.dtype == np.float64 else lib().fwx_solve_ragged_f32
+    fn = getattr(lib(), stem + ("_f64" if rate.dtype == np.float64 else "_f32"))
     check(fn(len(n_each), _np_ptr(n_each), _np_ptr(rate), _np_ptr(nxt), _np_ptr(hp), _np_ptr(each), ctypes.byref(o)),
-          "fwx_solve_ragged")
+          stem)
     _unpack_ragged(n_each, (rate, nxt, hp), (rates, nexts, hops))
     return each
 
@@ -411,6 +431,16 @@ def solve_ragged_lists(rates, nexts, hops=None, *, items=None, cap=None, device=
     nexts is required.  items, cap and the return value as in solve_batch_lists: items None means all n_b * n_b pairs
     of every matrix in the order (b, i, j); cap None starts at BATCH_LISTS_FIRST_CAP and doubles, solving the batch
     again from a kept copy of the input for the items that did not fit, up to BATCH_LISTS_MAX_CAP."""
+    return _solve_ragged_lists("fwx_solve_ragged_lists", rates, nexts, hops, items, cap, device, count_updates)
+
+
+def solve_ragged_mid_lists(rates, nexts, hops=None, *, items=None, cap=None, device=-1, count_updates=False):
+    """solve_ragged_lists with the limit at FWX_BATCH_MID_MAX_N (fwx_solve_ragged_mid_lists_f64 / _f32).  Same arrays,
+    same lists, same return value."""
+    return _solve_ragged_lists("fwx_solve_ragged_mid_lists", rates, nexts, hops, items, cap, device, count_updates)
+
+
+def _solve_ragged_lists(stem, rates, nexts, hops, items, cap, device, count_updates):
     if nexts is None:
         raise ValueError("the exact lists need next")
     rates, nexts = list(rates), list(nexts)
@@ -425,7 +455,7 @@ def solve_ragged_lists(rates, nexts, hops=None, *, items=None, cap=None, device=
     mat, src, dst = (np.ascontiguousarray(a, dtype=np.int32) for a in items)
     if not (mat.ndim == 1 and mat.shape == src.shape == dst.shape):
         raise ValueError("items must be three equally long one-dimensional sequences (mat, src, dst)")
-    fn = lib().fwx_solve_ragged_lists_f64 if rate.dtype == np.float64 else lib().fwx_solve_ragged_lists_f32
+    fn = getattr(lib(), stem + ("_f64" if rate.dtype == np.float64 else "_f32"))
     grow = cap is None
     cap = BATCH_LISTS_FIRST_CAP if grow else int(cap)
     kept = (rate.copy(), nxt.copy(), None if hp is None else hp.copy()) if grow else None
@@ -440,20 +470,20 @@ def solve_ragged_lists(rates, nexts, hops=None, *, items=None, cap=None, device=
         m, s, d = (np.ascontiguousarray(a[todo]) for a in (mat, src, dst))
         check(fn(count, _np_ptr(n_each), _np_ptr(arrays[0]), _np_ptr(arrays[1]), _np_ptr(arrays[2]),
                  _np_ptr(each) if arrays[0] is rate else None, len(todo), _np_ptr(m), _np_ptr(s), _np_ptr(d),
-                 _np_ptr(lens), _np_ptr(paths), cap, ctypes.byref(o)), "fwx_solve_ragged_lists")
+                 _np_ptr(lens), _np_ptr(paths), cap, ctypes.byref(o)), stem)
         if count == 0 or not n_each.any():
             lens[:] = _lib.FWX_ERR_INVALID       # nothing was solved: no item lies in the batch
         short = lens == _lib.FWX_ERR_CAPACITY
         bad = (lens < 0) & ~short
         if bad.any():
-            raise FwxError(int(lens[bad][0]), "fwx_solve_ragged_lists: item %d" % int(todo[bad][0]))
+            raise FwxError(int(lens[bad][0]), "%s: item %d" % (stem, int(todo[bad][0])))
         for q in np.nonzero(~short)[0]:
             out[todo[q]] = tuple(int(v) for v in paths[q, :lens[q]])
         if not short.any():
             break
         if not grow or cap >= BATCH_LISTS_MAX_CAP:
-            raise FwxError(_lib.FWX_ERR_CAPACITY, "fwx_solve_ragged_lists: item %d does not fit cap %d"
-                           % (int(todo[short][0]), cap))
+            raise FwxError(_lib.FWX_ERR_CAPACITY, "%s: item %d does not fit cap %d"
+                           % (stem, int(todo[short][0]), cap))
         cap, todo = min(2 * cap, BATCH_LISTS_MAX_CAP), todo[short]
         arrays = tuple(None if a is None else a.copy() for a in kept)     # solved again from the input
     _unpack_ragged(n_each, (rate, nxt, hp), (rates, nexts, hops))
@@ -472,29 +502,54 @@ def dev_solve_ragged(rate_t, n_each_t, offset_t, order_t, tier_count, *, next_t=
     order_t (int32) are DEVICE arrays of count entries, order_t / tier_count a plan as ragged_plan gives it.  Gaps
     between the matrices are never touched.  Asynchronous on `stream`.  updates_t: device array of count 64-bit
     counters, counter b is incremented by U of matrix b."""
+    _dev_solve_ragged("fwx_dev_solve_ragged", 3, rate_t, n_each_t, offset_t, order_t, tier_count, next_t, hops_t, trace,
+                      updates_t, stream)
+
+
+def dev_solve_ragged_mid(rate_t, n_each_t, offset_t, order_t, tier_count, *, next_t=None, hops_t=None, trace=None,
+                         updates_t=None, stream=None):
+    """fwx_dev_solve_ragged_mid: dev_solve_ragged for orders up to FWX_BATCH_MID_MAX_N; order_t / tier_count (four
+    entries) a plan as ragged_mid_plan gives it.  Same arrays, same trace, same counters."""
+    _dev_solve_ragged("fwx_dev_solve_ragged_mid", 4, rate_t, n_each_t, offset_t, order_t, tier_count, next_t, hops_t,
+                      trace, updates_t, stream)
+
+
+def _dev_solve_ragged(name, ntiers, rate_t, n_each_t, offset_t, order_t, tier_count, next_t, hops_t, trace, updates_t,
+                      stream):
     count = n_each_t.numel()
     tiers = np.ascontiguousarray(tier_count, dtype=np.int32)
-    assert tiers.shape == (3,)
+    assert tiers.shape == (ntiers,)
     assert rate_t.is_cuda and rate_t.is_contiguous()
     for t in (next_t, hops_t):
         assert t is None or (t.is_cuda and t.is_contiguous() and _dtype_name(t) == "int32")
     assert updates_t is None or (updates_t.element_size() == 8 and updates_t.numel() >= count)
     vp = ctypes.c_void_p
-    check(lib().fwx_dev_solve_ragged(
+    check(getattr(lib(), name)(
         count, _tensor_dtype_code(rate_t), vp(rate_t.data_ptr()),
         vp(next_t.data_ptr()) if next_t is not None else None,
         vp(hops_t.data_ptr()) if hops_t is not None else None,
         _index_ptr(n_each_t, "int32", count), _index_ptr(offset_t, "int64", count),
         _index_ptr(order_t, "int32", int(tiers.sum())), _np_ptr(tiers),
         _trace_of(trace, 0) if trace is not None else None,
-        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)),
-        "fwx_dev_solve_ragged")
+        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)), name)
 
 
 def dev_exact_paths_ragged(next0_t, n_each_t, offset_t, n_max, trace, mat_t, src_t, dst_t, cap, *, stream=None):
     """fwx_dev_exact_paths_ragged: the exact `_path` lists of the items (mat_t[q], src_t[q], dst_t[q]) of a ragged
     batch that dev_solve_ragged solved with `trace`; next0_t is the caller's copy of the UNSOLVED next-hop array (same
     offsets), n_max at least the largest order.  Returns (len_t, path_t) as dev_exact_paths_batch."""
+    return _dev_exact_paths_ragged("fwx_dev_exact_paths_ragged", next0_t, n_each_t, offset_t, n_max, trace, mat_t,
+                                   src_t, dst_t, cap, stream)
+
+
+def dev_exact_paths_ragged_mid(next0_t, n_each_t, offset_t, n_max, trace, mat_t, src_t, dst_t, cap, *, stream=None):
+    """fwx_dev_exact_paths_ragged_mid: dev_exact_paths_ragged over a batch that dev_solve_ragged_mid solved, n_max <=
+    FWX_BATCH_MID_MAX_N."""
+    return _dev_exact_paths_ragged("fwx_dev_exact_paths_ragged_mid", next0_t, n_each_t, offset_t, n_max, trace, mat_t,
+                                   src_t, dst_t, cap, stream)
+
+
+def _dev_exact_paths_ragged(name, next0_t, n_each_t, offset_t, n_max, trace, mat_t, src_t, dst_t, cap, stream):
     count = n_each_t.numel()
     assert next0_t.is_cuda and next0_t.is_contiguous() and _dtype_name(next0_t) == "int32"
     items = mat_t.numel()
@@ -504,11 +559,11 @@ def dev_exact_paths_ragged(next0_t, n_each_t, offset_t, n_max, trace, mat_t, src
     path_t = _empty_like_device(mat_t, (items, cap), "int32")
     scratch = _empty_like_device(mat_t, (max(items * 3 * (n_max + 2), 1),), "int32")
     vp = ctypes.c_void_p
-    check(lib().fwx_dev_exact_paths_ragged(
+    check(getattr(lib(), name)(
         count, _index_ptr(n_each_t, "int32", count), _index_ptr(offset_t, "int64", count), n_max,
         vp(next0_t.data_ptr()), _trace_of(trace, 0), items, vp(mat_t.data_ptr()), vp(src_t.data_ptr()),
         vp(dst_t.data_ptr()), vp(len_t.data_ptr()), vp(path_t.data_ptr()), cap, vp(scratch.data_ptr()),
-        _stream_ptr(stream, mat_t)), "fwx_dev_exact_paths_ragged")
+        _stream_ptr(stream, mat_t)), name)
     if not _is_torch(mat_t):
         len_t._scratch = scratch              # stays alive until the results are read
     return len_t, path_t

@@ -385,6 +385,66 @@ int fwx_solve_ragged_lists_f32(int32_t count, const int32_t *n_each, float *rate
                                const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
                                const fwx_opts *opts);
 
+/* ---- ragged batches up to order FWX_BATCH_MID_MAX_N: a fourth tier in the same call ------------------------
+ * A history of the 20 x 12 market above (240 vertices) is ragged AND crosses 128.  These entry points are the
+ * ragged family above, word for word, with the limit at FWX_BATCH_MID_MAX_N (256) and a plan of FOUR tiers: the
+ * three above and the mid tier (one workgroup per matrix, the matrix resident in device memory, as
+ * fwx_dev_solve_batch_mid runs it).  Every matrix comes back bit-identical to the reference loop on that matrix alone
+ * -- rate, next, hops, U, the trace and the lists -- and no matrix pays for the largest order of the batch.  The
+ * entry points above keep refusing orders above FWX_BATCH_MAX_N, and fwx_ragged_plan keeps its three tiers.
+ *
+ * fwx_ragged_mid_plan: as fwx_ragged_plan, needs no device; order_out groups the matrices with n_b >= 1 into the
+ * wave tier, the 64-wide tier, the 128-wide tier and the mid tier, in this order, each sorted by descending order,
+ * ties by ascending index, the rest -1; tier_count_out has four entries.  Tier boundaries: FWX_BATCH_WAVE_MAX_N as
+ * above, and FWX_BATCH_MID_MIN_N (1 ... 129, default 129, as for fwx_solve_batch_mid_*) sends every order from it
+ * upward to the mid tier.  Both are read by the plan and only by the plan.  Where both settings claim an order
+ * (FWX_BATCH_MID_MIN_N <= n_b <= FWX_BATCH_WAVE_MAX_N) the MID tier wins.  With FWX_BATCH_MID_MIN_N at its default
+ * and every order <= FWX_BATCH_MAX_N the first three counts and the order list are fwx_ragged_plan's.
+ * FWX_ERR_INVALID as fwx_ragged_plan; FWX_ERR_UNSUPPORTED: an order above FWX_BATCH_MID_MAX_N.  No result bit of a
+ * solve depends on the split.
+ *
+ * fwx_solve_ragged_mid_f64 / _f32 and fwx_solve_ragged_mid_lists_f64 / _f32: HOST arrays, packed, whole pivot range
+ * only; up to four launches on one stream, the mid tier first because its workgroups run longest.  updates_each,
+ * opts->updates_out, the lists arguments, the chunks (FWX_BATCH_LISTS_CHUNK, sized by the largest order present) and
+ * the capacity rule as in fwx_solve_ragged_* / fwx_solve_ragged_lists_*.
+ *
+ * fwx_dev_solve_ragged_mid / fwx_dev_exact_paths_ragged_mid: caller-owned DEVICE memory, asynchronous on `stream`,
+ * nothing allocated or synchronised; the offsets need not be packed and nothing outside the n_b x n_b cells of a
+ * matrix is read or written.  tier_count (HOST) has four entries.  In the three small tiers a matrix listed in a
+ * tier whose tile does not hold its order is left untouched, as above; the mid tier's tile holds every order 1 ...
+ * 256, so a matrix of ANY such order listed there is solved.  An id outside [0, count) in d_order leaves its
+ * workgroup idle.  The walk: n_max <= FWX_BATCH_MID_MAX_N, scratch holds items * FWX_EXACT_SCRATCH_INTS(n_max) int32.
+ *
+ * Statuses, all decided before any device call, as in the ragged family above with: FWX_ERR_UNSUPPORTED for an order
+ * (n_max in the walk) above FWX_BATCH_MID_MAX_N; FWX_ERR_INVALID for a sum of the FOUR tier counts above count.
+ * Then FWX_ERR_NO_DEVICE without a device, the arrays untouched.
+ * When it pays (MI355X, f64 + next + hops, profiles/r22_ragged_mid.txt): 4096 matrices whose orders ramp from 4 to 256
+ * take 8.3 ms in one fwx_dev_solve_ragged_mid call, 19.7 ms NaN-padded to 256 in one fwx_dev_solve_batch_mid launch
+ * and 12.5 ms split by hand into fwx_dev_solve_ragged plus one padded mid launch.  With all orders equal the call is
+ * 0.4 - 1.5 % slower than fwx_dev_solve_batch_mid (most at n = 129): use that one for a uniform batch.          */
+int fwx_ragged_mid_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
+                        int32_t tier_count_out[4]);
+int fwx_solve_ragged_mid_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                             uint64_t *updates_each, const fwx_opts *opts);
+int fwx_solve_ragged_mid_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                             uint64_t *updates_each, const fwx_opts *opts);
+int fwx_dev_solve_ragged_mid(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                             const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                             const int32_t tier_count[4], const struct fwx_trace *trace,
+                             unsigned long long *d_updates_each, void *stream);
+int fwx_dev_exact_paths_ragged_mid(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                                   const int32_t *next0, const struct fwx_trace *trace, int32_t items,
+                                   const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
+                                   int32_t *path_out, int32_t cap, int32_t *scratch, void *stream);
+int fwx_solve_ragged_mid_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                   const fwx_opts *opts);
+int fwx_solve_ragged_mid_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                   const fwx_opts *opts);
+
 /* Index form of the `_path` list that optimum returns (Algorithms.hs:74-75): follow next-hops
  * from src until dst.  Returns the number of vertices written to out (dst included, src not), 0 if
  * next[src][dst] == -1 (empty path, "no exchange"), or a negative fwx_status.  Host arrays.      */
