@@ -1293,6 +1293,8 @@ int fwx_test_perk_pivots(uint64_t *launches, int reset)
 
 int fwx_test_perk_fold(void) { return perk_fold_compare() ? 1 : 0; }
 
+int fwx_test_perk_walk(void) { return perk_walk() ? 1 : 0; }
+
 int fwx_test_perk_wide(uint64_t *wide_launches, int reset)
 {
     const uint64_t v = reset ? g_perk_wide_launches.exchange(0, std::memory_order_relaxed)

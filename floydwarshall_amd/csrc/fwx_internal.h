@@ -496,6 +496,17 @@ inline bool perk_wide()
     return !(e && !strcmp(e, "0"));
 }
 
+// The kernel of the 16-pivot sweep (round 23): relax_walk -- one body for every tile, three waves per SIMD
+// (fwx_kernels.hip; the geometry: FWX_PERK_WALK_* in fwx_kernels.h).  FWX_PERK_WALK=0 gives round 19's relax_kt instead,
+// launch for launch; anything else, or unset, leaves relax_walk on; read on every call.  The schedule, its launch
+// counts and both hooks' counters are the same either way.  For tests and A/B runs in one binary, and the remedy
+// should the new kernel misbehave.  No result bit depends on it.
+inline bool perk_walk()
+{
+    const char *e = getenv("FWX_PERK_WALK");
+    return !(e && !strcmp(e, "0"));
+}
+
 // The fold of relax_kt's non-counting f32 sweeps: FWX_PERK_FOLD=compare forces the compare form in every tile, read on
 // every call; anything else, or unset: automatic (each wave takes the max form where the operands it has loaded
 // are all NaN or sign-clear).  For tests and A/B runs in one binary.  No result bit depends on it (DESIGN.md
@@ -655,6 +666,7 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
     a.temporal_bytes = perk_temporal_bytes((size_t)n * n * sizeof(T));
     a.store_bytes = perk_store_bytes();
     a.fold_compare = perk_fold_compare();
+    a.walk = perk_walk();
     fwx::RelaxArgs<T> a1;
     a1.rate = rate; a1.next = nullptr; a1.hops = nullptr; a1.phops = nullptr; a1.rows = n; a1.n = n; a1.row0 = 0;
     a1.updates = d_updates; a1.temporal_bytes = a.temporal_bytes; a1.store_bytes = a.store_bytes;

@@ -117,6 +117,10 @@ template <typename T> hipError_t launch_relax(const RelaxArgs<T> &a, hipStream_t
 #define FWX_PERK_KT_UNROLL 8       //   pivot than relax_k's 4 x 4 at NP = 8 (profiles/r07_tune_relax_pivots.txt)
 #define FWX_PERK_KT16_RPB 16       // the 16-pivot sweep (non-counting f32 only): its geometry
 #define FWX_PERK_KT16_UNROLL 8     //   (profiles/r19_tune_relax_pivots.txt)
+#define FWX_PERK_WALK_RPB 16       // relax_walk, the 16-pivot sweep since round 23: rows per workgroup, row slots in
+#define FWX_PERK_WALK_UNROLL 8     //   flight, cache policy of the stream (WALK_POL_*, fwx_kernels.hip: 0 = default-
+#define FWX_PERK_WALK_POL 0        //   policy loads everywhere), slots reloaded one by one behind their folds (1) or
+#define FWX_PERK_WALK_ROLL false   //   in batches (0).  What was timed: profiles/r23_tune_relax_pivots.txt
 template <typename T> struct RelaxKtArgs {
     T *rate;                       // n x n
     const T *w;                    // w[t*n + j]      = row k+t at time k+t          (t < np)
@@ -127,6 +131,8 @@ template <typename T> struct RelaxKtArgs {
     int store_bytes = 0;
     bool fold_compare = false;     // true: the compare form of the fold in every tile (FWX_PERK_FOLD=compare); false: each
                                    // wave takes the max form where its operands allow it.  No result bit depends on it
+    bool walk = false;             // np == 16: true: relax_walk sweeps (FWX_PERK_WALK); false: relax_kt, round 19's launch.
+                                   // No result bit depends on it
     unsigned long long *updates = nullptr;   // FWX_UPDATE_SHARDS_K counters or nullptr
 };
 template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s);

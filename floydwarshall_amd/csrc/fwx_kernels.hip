@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
+#include <utility>
 
 #include "fwx_kernels.h"
 
@@ -716,6 +717,278 @@ void relax_kt(T *rate, const T *w, const T *ct, int ct_ld, int n, int k,
 }
 
 // -------------------------------------------------------------------------------------------------
+// relax_walk (round 23): the 16-pivot sweep of the non-counting f32 solve, relax_kt<float, 4, ., ., false, GL, 16>
+// word for word in what it computes -- operands from the snapshot panels only, the NaN patch at column k + t and in
+// clamped lanes, the per-wave vote between the max form and the compare form, the diagonal never updates, the group
+// store with exact write-back, visit_tile, strip_magic, `nt_below` -- in another shape:
+//
+// ONE body.  relax_kt is four copies of `stream` (cache policy x diagonal), and the compiler hoists the 16 loads of W
+// in front of them and patches the NaNs into registers of each copy's own: 247 VGPRs, two waves per SIMD
+// (profiles/r19_relax_kt16_isa.txt).  Here W is loaded and patched once, in place; the diagonal is a run-time term
+// of the fold and the cache policy is chosen at the load.  160 VGPRs with 8 row slots, three waves per SIMD
+// (profiles/r23_relax_walk_isa.txt).
+// The diagonal term: a tile starts at a multiple of 4 rows and a lane at a multiple of 4 columns, so the component
+// of row r on the diagonal is r % 4 in whichever lane holds it, and r % 4 is the slot's number % 4, a constant of the
+// unrolled body: ONE component per row carries `&& d != c` (d: this lane's diagonal component of the row, -1 in a
+// tile off the diagonal), one v_cmp_ne and one scalar AND per row.
+//
+// What ships is this body with relax_kt's geometry and row loop (16 rows per workgroup, 8 loaded together and folded
+// together, twice; !ROLL) and default-policy loads everywhere (WALK_POL_PLAIN): 223.8 us per pass late in the solve
+// at N = 16384 against relax_kt's 257.5 (profiles/r23_tune_relax_pivots.txt).  The other values of ROLL and POL are
+// what was timed against it and lost (tools/tune_relax.hip `pivots`, profiles/r23_experiments_not_adopted.txt):
+//
+// The WALK (ROLL).  A workgroup owns RPB rows of its strip, RPB a multiple of UNROLL up to 64, and keeps W for all of
+// them.  UNROLL row slots are in flight; a slot is reloaded with the row UNROLL further on right after its fold and
+// its store, UNCONDITIONALLY, and the last batch is peeled without a reload.  In that shape, from RPB = 32 and with
+// WALK_POL_PLAIN, the compiler's waits are exact: one s_waitcnt vmcnt(UNROLL - 1) per row in front of the row's
+// compares, so UNROLL - 1 rows stay in flight under every fold.  A reload behind a uniform `if (more)` gets one
+// vmcnt(0) per batch instead (the wait pass merges the path on which no later load was issued), which is what the
+// compare form's loop below has: it is the rare form and keeps the simple loop.  The walk was slower than the batches
+// in every window, the more rows the slower: the exposed wait was not what the pass was short of.
+//
+// The cache policy (POL), what `nt_below` means to the loads of r[i][j]:
+//   WALK_POL_PLAIN  default-policy loads everywhere (the split of round 5 dropped)
+//   WALK_POL_FENCE  one load, its policy chosen at run time; the non-temporal arm stands between two empty asm
+//                   statements, without which the optimiser merges the two arms into one plain load.  Two
+//                   conditional blocks per load, and one vmcnt(0) per batch in the walk
+//   WALK_POL_LOOP   two copies of the steady loop alone, one per policy; the head loads as WALK_POL_FENCE.  Spills
+// No result bit depends on it.
+//
+// Staging: thread t stages the cells t, t + 256, ... of the RPB x 16 values of Ct, one writer per cell.  The race-
+// freedom and write-back arguments are relax_kt's: every element belongs to exactly one lane of one workgroup.
+// -------------------------------------------------------------------------------------------------
+enum { WALK_POL_PLAIN = 0, WALK_POL_FENCE = 1, WALK_POL_LOOP = 2 };
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant of each step
+template <typename F, int... U> __device__ __forceinline__ void for_slots_seq(F &&f, std::integer_sequence<int, U...>)
+{
+    (f(std::integral_constant<int, U>()), ...);
+}
+template <int N, typename F> __device__ __forceinline__ void for_slots(F &&f)
+{
+    for_slots_seq(f, std::make_integer_sequence<int, N>());
+}
+
+template <int UNROLL> constexpr int relax_walk_min_waves() { return UNROLL <= 4 ? 4 : 3; }
+
+template <int RPB, int UNROLL, int GL, int POL, bool ROLL>
+__global__ __launch_bounds__(256, (relax_walk_min_waves<UNROLL>()))
+void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, int k, int nstrips, int flip,
+                int nt_below, unsigned strip_magic, int fold_compare)
+{
+    constexpr int NP = 16, W = 4, SW = 256 * W;
+    constexpr int STAGE = (RPB * NP + 255) / 256;     // staged values per thread
+    using L = Lanes<float, W>;
+    using V = typename L::V;
+    static_assert(GL == 1 || GL == 2 || GL == 4 || GL == 8, "store group: 1, 2, 4 or 8 lanes");
+    static_assert(UNROLL % 4 == 0 && RPB % UNROLL == 0 && RPB * NP % 256 == 0, "slots and rows");
+
+    __shared__ __attribute__((aligned(16))) float s_ct[RPB][NP];
+
+    const int t = threadIdx.x;
+    const int bid = visit_tile(flip);
+    int strip, chunk;                         // as relax_kt
+    if (strip_magic) {
+        chunk = (int)__umulhi((unsigned)bid, strip_magic);
+        strip = bid - chunk * nstrips;
+    } else {
+        strip = bid % nstrips;
+        chunk = bid / nstrips;
+    }
+    const int r_begin = chunk * RPB;
+    const int r_cnt = min(RPB, n - r_begin);
+    const int c0 = strip * SW + t * W;
+    const bool own = c0 < n;                  // false: a clamped lane (never stores)
+    const int col = own ? c0 : n - W;
+    const unsigned boff = (unsigned)col * (unsigned)sizeof(float);
+    auto at = [&](const float *q, int r) {
+        const char *const row = reinterpret_cast<const char *>(q + (size_t)r * n);
+        return const_cast<float *>(reinterpret_cast<const float *>(row + boff));
+    };
+    float *const base = rate + (size_t)r_begin * n;
+    const int g0 = (int)(__lane_id() & ~(GL - 1));
+    const bool nt = bid < nt_below;           // workgroup-uniform
+    const bool diag = r_begin < (strip + 1) * SW && r_begin + r_cnt > strip * SW;
+    const int d0 = diag ? r_begin - col : -1 - RPB;   // row r of the tile: my diagonal component is d0 + r if in [0, W)
+
+    auto ld_nt = [&](const float *q) { return __builtin_nontemporal_load(reinterpret_cast<const V *>(q)); };
+    auto ld_t = [&](const float *q) { return *reinterpret_cast<const V *>(q); };
+    // the policy chosen at the load; the fences keep the two arms apart (header)
+    auto ld = [&](const float *q) -> V {
+        if constexpr (POL == WALK_POL_PLAIN) return ld_t(q);
+        V v;
+        if (nt) { asm volatile(""); v = ld_nt(q); asm volatile(""); }
+        else v = ld_t(q);
+        return v;
+    };
+    auto group_stores = [&](bool changed) {
+        if constexpr (GL == 1) return changed;
+        const unsigned long long m = __ballot(changed);
+        return own && ((m >> g0) & ((1ull << GL) - 1)) != 0;
+    };
+
+    // Prologue: every load the first fold needs back to back (relax_kt's), then the NaN patch of W in place.
+    float cv[STAGE];
+#pragma unroll
+    for (int i = 0; i < STAGE; ++i) {
+        const int id = t + 256 * i;
+        cv[i] = ct[(size_t)(id / RPB % NP) * ct_ld + r_begin + min(id % RPB, r_cnt - 1)];
+    }
+    V p[NP];
+#pragma unroll
+    for (int tt = 0; tt < NP; ++tt) p[tt] = *reinterpret_cast<const V *>(at(w, tt));
+    const bool head = UNROLL <= r_cnt;        // workgroup-uniform
+    V x[UNROLL];
+    if (head) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) x[u] = ld(at(base, u));
+    }
+    // rows of a ragged chunk past the end of the matrix get the last row's values again; one writer per cell
+#pragma unroll
+    for (int i = 0; i < STAGE; ++i) {
+        const int id = t + 256 * i;
+        s_ct[id % RPB][id / RPB % NP] = cv[i];
+    }
+#pragma unroll
+    for (int tt = 0; tt < NP; ++tt)
+#pragma unroll
+        for (int c = 0; c < W; ++c)
+            L::set(p[tt], c, !own || col + c == k + tt ? quiet_nan<float>() : L::get(p[tt], c));
+    __syncthreads();
+    // The vote, per wave (relax_kt's): the max form iff no value of W in my lanes after the patch and no staged Ct
+    // value of the tile has its sign bit set.  A ragged chunk keeps the compare form.
+    float signs = 0.f;
+#pragma unroll
+    for (int tt = 0; tt < NP; ++tt)
+        asm("v_or3_b32 %0, %0, %1, %2\n\tv_or3_b32 %0, %0, %3, %4"
+            : "+v"(signs)
+            : "v"(L::get(p[tt], 0)), "v"(L::get(p[tt], 1)), "v"(L::get(p[tt], 2)), "v"(L::get(p[tt], 3)));
+#pragma unroll
+    for (int i = 0; i < RPB * NP; i += 64) {
+        const float v = (&s_ct[0][0])[i + (int)__lane_id()];         // rows past r_cnt repeat the last row
+        asm("v_or_b32 %0, %1, %2" : "=v"(signs) : "v"(signs), "v"(v));
+    }
+    const bool any = __builtin_amdgcn_ballot_w64(__builtin_signbit(signs)) != 0;
+    const bool max_form = !fold_compare && !any && r_cnt % UNROLL == 0;
+
+    // One row through the 16 pivots, max form (relax_kt's relax_vec_max).  CD = r % 4: the one component of the row
+    // that can lie on the diagonal.
+    auto vec_max = [&](const V &xv, int r, auto cd) {
+        constexpr int CD = decltype(cd)::value;
+        float cik[NP];
+#pragma unroll
+        for (int tt = 0; tt < NP; ++tt) cik[tt] = s_ct[r][tt];
+        float m[W];
+        bool up[W];
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            float cand[NP];
+#pragma unroll
+            for (int tt = 0; tt < NP; ++tt) cand[tt] = cik[tt] * L::get(p[tt], c);
+            m[c] = max_of(cand);
+        }
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            up[c] = L::get(xv, c) < m[c];
+            if (c == CD) up[c] = up[c] && d0 + r != CD;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        V nx;
+        bool changed = false;
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            L::set(nx, c, up[c] ? m[c] : L::get(xv, c));
+            changed = changed || up[c];
+        }
+        if (group_stores(changed)) *reinterpret_cast<V *>(at(base, r)) = nx;
+    };
+    // ... compare form (relax_kt's relax_vec with the diagonal as a run-time term).
+    auto vec_cmp = [&](const V &xv, int r) {
+        const int d = d0 + r;
+        V nx;
+#pragma unroll
+        for (int c = 0; c < W; ++c) L::set(nx, c, c == d ? __builtin_huge_valf() : L::get(xv, c));
+        float cik[NP];
+#pragma unroll
+        for (int tt = 0; tt < NP; ++tt) cik[tt] = s_ct[r][tt];
+#pragma unroll
+        for (int tt = 0; tt < NP; ++tt) {
+            float cand[W];
+            bool up[W];
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                cand[c] = cik[tt] * L::get(p[tt], c);
+                up[c] = L::get(nx, c) < cand[c];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c = 0; c < W; ++c) L::set(nx, c, up[c] ? cand[c] : L::get(nx, c));
+        }
+#pragma unroll
+        for (int c = 0; c < W; ++c) L::set(nx, c, c == d ? L::get(xv, c) : L::get(nx, c));
+        uint32_t diff = 0;
+#pragma unroll
+        for (int c = 0; c < W; ++c)
+            diff |= __builtin_bit_cast(uint32_t, L::get(nx, c)) ^ __builtin_bit_cast(uint32_t, L::get(xv, c));
+        if (group_stores(diff != 0)) *reinterpret_cast<V *>(at(base, r)) = nx;
+    };
+
+    if (max_form) {                           // wave-uniform; r_cnt is a multiple of UNROLL here, so `head` holds
+        int rb = 0;
+        if constexpr (ROLL) {
+            // steady state: fold slot u (row rb + u), reload it with row rb + UNROLL + u, unconditionally
+            auto steady = [&](auto load) {
+#pragma unroll 1
+                for (; rb + UNROLL < r_cnt; rb += UNROLL) {
+                    for_slots<UNROLL>([&](auto uc) {
+                        constexpr int u = decltype(uc)::value;
+                        vec_max(x[u], rb + u, std::integral_constant<int, u % 4>());
+                        x[u] = load(at(base, rb + UNROLL + u));
+                    });
+                }
+            };
+            if constexpr (POL == WALK_POL_LOOP) {
+                if (nt) steady(ld_nt); else steady(ld_t);
+            } else {
+                steady(ld);
+            }
+        } else {
+#pragma unroll 1
+            for (; rb + UNROLL < r_cnt; rb += UNROLL) {
+                for_slots<UNROLL>([&](auto uc) {
+                    constexpr int u = decltype(uc)::value;
+                    vec_max(x[u], rb + u, std::integral_constant<int, u % 4>());
+                });
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) x[u] = ld(at(base, rb + UNROLL + u));
+            }
+        }
+        // the last batch, peeled: no reload
+        for_slots<UNROLL>([&](auto uc) {
+            constexpr int u = decltype(uc)::value;
+            vec_max(x[u], rb + u, std::integral_constant<int, u % 4>());
+        });
+        return;
+    }
+    int r = 0;
+    if (head) {
+#pragma unroll 1
+        for (int rb = 0; rb + UNROLL <= r_cnt; rb += UNROLL) {
+            const bool more = rb + 2 * UNROLL <= r_cnt;
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                vec_cmp(x[u], rb + u);
+                if (more) x[u] = ld(at(base, rb + UNROLL + u));
+            }
+            r = rb + UNROLL;
+        }
+    }
+    // the row-by-row tail of a ragged last chunk, rolled
+#pragma unroll 1
+    for (; __builtin_expect(r < r_cnt, 0); ++r) vec_cmp(ld(at(base, r)), r);
+}
+
+// -------------------------------------------------------------------------------------------------
 // small_solve: the whole of runAlgo for n <= 128 in ONE launch of one workgroup -- the reference's
 // own regime (its tests stop at 4 x 4, src/test/AlgorithmsTest.hs:66-77; the README session has 4
 // vertices; a market of 10 exchanges x 12 currencies has 120).  The matrix is padded with NaN to
@@ -1357,9 +1630,56 @@ static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
     return hipGetLastError();
 }
 
+// relax_walk with the geometry (RPB rows per workgroup, UNROLL slots), the policy POL and the walk ROLL: np == 16,
+// uncounted f32.  The tile order, the cache-policy split and the store group are chosen as launch_relax_kt_cfg chooses
+// them, in tiles of RPB rows.  ALLGL: every store group; otherwise the default one alone (tools/tune_relax.hip).
+template <int RPB, int UNROLL, int POL, bool ROLL, bool ALLGL = false>
+static hipError_t launch_relax_walk_cfg(const RelaxKtArgs<float> &a, hipStream_t s)
+{
+    constexpr int W = 4, SW = 256 * W;
+    if (a.n <= 0) return hipSuccess;
+    if (a.n % W || (uintptr_t)a.rate % 16 || (uintptr_t)a.w % 16 || a.ct_ld < a.n || a.k < 0 || a.np != 16 ||
+        a.k + a.np > a.n || a.updates)
+        return hipErrorInvalidValue;
+    const int nstrips = (a.n + SW - 1) / SW;
+    const int nchunks = (a.n + RPB - 1) / RPB;
+    unsigned strip_magic = 0;
+    if (nstrips >= 2 && (unsigned long long)nstrips * nchunks * nstrips < (1ull << 32))
+        strip_magic = (unsigned)(0xffffffffull / (unsigned)nstrips) + 1u;
+    const dim3 grid((unsigned)(nstrips * nchunks)), block(256);
+    const int flip = a.flip == 2 && grid.x % 8 ? 1 : a.flip;
+    int nt_below = 0;
+    const double slab = (double)a.n * a.n * sizeof(float);
+    if (a.temporal_bytes >= 0 && slab > (double)a.temporal_bytes) {
+        const double tail = std::ceil((double)a.temporal_bytes / slab * grid.x);
+        nt_below = (int)grid.x - (int)std::min(tail, (double)grid.x);
+    }
+    const int sb = a.store_bytes > 0 ? a.store_bytes : FWX_PERK_STORE_BYTES_DEFAULT;
+    const int gl = sb >= 128 ? 8 : sb >= 64 ? 4 : sb >= 32 ? 2 : 1;
+#define FWX_LAUNCH_WALK(GL)                                                                        \
+    hipLaunchKernelGGL((relax_walk<RPB, UNROLL, GL, POL, ROLL>), grid, block, 0, s, a.rate, a.w, a.ct, a.ct_ld, a.n, \
+                       a.k, nstrips, flip, nt_below, strip_magic, a.fold_compare ? 1 : 0)
+    note_form(KF_RELAX_K);
+    if (gl == 4) FWX_LAUNCH_WALK(4);
+    else if constexpr (ALLGL) {
+        if (gl == 8) FWX_LAUNCH_WALK(8);
+        else if (gl == 2) FWX_LAUNCH_WALK(2);
+        else FWX_LAUNCH_WALK(1);
+    } else {
+        return hipErrorInvalidValue;
+    }
+#undef FWX_LAUNCH_WALK
+    return hipGetLastError();
+}
+
 template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s)
 {
     if (a.np == 16) {
+        if constexpr (std::is_same<T, float>::value) {
+            if (a.walk && !a.updates)
+                return launch_relax_walk_cfg<FWX_PERK_WALK_RPB, FWX_PERK_WALK_UNROLL, FWX_PERK_WALK_POL,
+                                             FWX_PERK_WALK_ROLL, true>(a, s);
+        }
         if constexpr (relax_kt_wide<T, FWX_PERK_KT16_RPB, FWX_PERK_KT16_UNROLL>())
             return launch_relax_kt_cfg<T, FWX_PERK_KT16_RPB, FWX_PERK_KT16_UNROLL, false, true>(a, s);
         return hipErrorInvalidValue;

@@ -144,6 +144,10 @@ int fwx_test_perk_wide(uint64_t *wide_launches, int reset);
 /* TEST HOOK: what FWX_PERK_FOLD parses to right now: 1 = compare (the value `compare`, exactly), 0 = automatic
  * (anything else, or unset).  Needs no device.  Not for production use.                              */
 int fwx_test_perk_fold(void);
+/* TEST HOOK: what FWX_PERK_WALK parses to right now: 0 = round 19's kernel sweeps the 16-pivot launches (the value
+ * `0`, exactly), 1 = round 23's does (anything else, or unset).  Launches are counted by the two hooks above, the
+ * same either way.  Needs no device.  Not for production use.                                        */
+int fwx_test_perk_walk(void);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).

@@ -215,6 +215,12 @@ static hipError_t run_kt(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
     return fwx::launch_relax_kt_cfg<float, RPB, UNROLL>(a, s);
 }
 
+template <int RPB, int UNROLL, int POL, bool ROLL>
+static hipError_t run_walk(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
+{
+    return fwx::launch_relax_walk_cfg<RPB, UNROLL, POL, ROLL>(a, s);
+}
+
 static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
 {
     std::vector<KtCfg> vars;
@@ -233,6 +239,18 @@ static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
     vars.push_back({"RPB16 U4", 16, run_kt<16, 4>});
     vars.push_back({"RPB16 U8", 16, run_kt<16, 8>});
     vars.push_back({"RPB16 U8 cmp", 16, run_kt<16, 8>, true});
+    // round 23, relax_walk.  A: one body, three waves, relax_kt's batches (no walk).  wR Us pol: R rows walked, s slots
+    // (8: three waves, 4: four), policy pl = plain loads, fn = chosen at the load (fenced), lp = two steady loops.
+    vars.push_back({"A 16 U8 fn", 16, run_walk<16, 8, fwx::WALK_POL_FENCE, false>});
+    vars.push_back({"A 16 U8 pl", 16, run_walk<16, 8, fwx::WALK_POL_PLAIN, false>});
+#define FWX_TUNE_WALK(R, U)                                                                        \
+    vars.push_back({"w" #R " U" #U " pl", 16, run_walk<R, U, fwx::WALK_POL_PLAIN, true>});         \
+    vars.push_back({"w" #R " U" #U " fn", 16, run_walk<R, U, fwx::WALK_POL_FENCE, true>});         \
+    vars.push_back({"w" #R " U" #U " lp", 16, run_walk<R, U, fwx::WALK_POL_LOOP, true>});
+    FWX_TUNE_WALK(16, 8) FWX_TUNE_WALK(32, 8) FWX_TUNE_WALK(64, 8)
+    FWX_TUNE_WALK(16, 4) FWX_TUNE_WALK(32, 4) FWX_TUNE_WALK(64, 4)
+#undef FWX_TUNE_WALK
+    vars.push_back({"w32 U8 cmp", 16, run_walk<32, 8, fwx::WALK_POL_FENCE, true>, true});
     const int k0s[3] = {0, 4096, 12000}, nw = 3, nv = (int)vars.size();
     if (n % 64 || per % 16) { printf("pivots mode: n must be a multiple of 64 and per of 16\n"); return 1; }
     const size_t bytes = (size_t)n * n * sizeof(float);
