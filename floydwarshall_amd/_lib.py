@@ -31,6 +31,14 @@ FWX_UPDATE_SHARDS = 256
 FWX_FUSED_BLOCK = 64
 FWX_BATCH_MAX_N = 128
 FWX_BATCH_MID_MAX_N = 256
+FWX_BATCH_LARGE_MAX_N = 1024
+
+
+def batch_large_scratch_bytes(n):
+    """FWX_BATCH_LARGE_SCRATCH_BYTES(n) of include/fwx.h: device scratch one matrix of order n needs."""
+    return int(n) * 512
+
+
 FWX_FLAG_NONNEG = 1
 FWX_XCHG_AUTO, FWX_XCHG_PEER, FWX_XCHG_RCCL = 0, 1, 2
 FWX_XCHG_CALLBACK = 3
@@ -112,6 +120,12 @@ SIGNATURES = {
                                                c_vp, c_vp]),
     "fwx_test_batch_mid_min_n": (ctypes.c_int, []),
     "fwx_test_batch_mid_block": (ctypes.c_int, []),
+    "fwx_solve_batch_large_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_batch_large_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
+    "fwx_dev_solve_batch_large": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32,
+                                                 c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "fwx_test_batch_large_min_n": (ctypes.c_int, []),
+    "fwx_test_batch_large_geometry": (ctypes.c_int, [ctypes.POINTER(c_i32)]),
     "fwx_dev_solve_batch_traced": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64,
                                                   ctypes.POINTER(FwxTrace), c_vp, c_vp]),
     "fwx_dev_exact_paths_batch": (ctypes.c_int, [c_i32, c_i32, ctypes.c_int64, c_vp, ctypes.POINTER(FwxTrace), c_i32,

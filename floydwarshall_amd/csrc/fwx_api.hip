@@ -520,6 +520,21 @@ int dev_solve_batch(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *h
     return FWX_OK;
 }
 
+// The large tier (fwx_solve_batch_large_*, fwx_dev_solve_batch_large) for a call already routed to it (n >=
+// FWX_BATCH_LARGE_MIN_N; below it the callers take dev_solve_batch with mid set): groups of as many matrices as the
+// scratch holds, one after the other on s.
+template <typename T>
+int dev_solve_batch_large(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, int64_t stride,
+                          int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, void *scratch,
+                          size_t scratch_bytes, hipStream_t s)
+{
+    const hipError_t e = fwx::launch_batch_large<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
+                                                    d_updates_each, scratch, scratch_bytes, s);
+    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
+    FWX_HIP(e);
+    return FWX_OK;
+}
+
 // Ragged batches (fwx_solve_ragged_*): what the orders alone decide.  FWX_ERR_INVALID for a negative order;
 // n_max is the largest order, whatever it is -- the caller compares it with FWX_BATCH_MAX_N.
 int ragged_orders(int32_t count, const int32_t *n_each, int32_t &n_max)
@@ -615,10 +630,14 @@ struct BatchLists {
 // ragged && mid (fwx_solve_ragged_mid_*, fwx_solve_ragged_mid_lists_*): the ragged batch with the limit at
 // FWX_BATCH_MID_MAX_N and the four-tier plan (FWX_BATCH_MID_MIN_N read here, by the plan); the workspace layout and
 // the walk are the ragged ones.
+// large (fwx_solve_batch_large_*; with mid, without ls or ragged): the limit on n is FWX_BATCH_LARGE_MAX_N; orders
+// from FWX_BATCH_LARGE_MIN_N up run the large tier, whose scratch panels -- at most kBatchLargeScratchCap, larger
+// batches run in groups -- are the context's SMALL buffer; smaller orders are the mid call.
+constexpr size_t kBatchLargeScratchCap = (size_t)256 << 20;
 template <typename T>
 int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
                      const fwx_opts *o, const BatchLists *ls = nullptr, bool ragged = false,
-                     const int32_t *n_each = nullptr, bool mid = false)
+                     const int32_t *n_each = nullptr, bool mid = false, bool large = false)
 {
     if (count < 0 || (!ragged && n < 0) || (ls && ls->items < 0)) return FWX_ERR_INVALID;
     if (count == 0 || (!ragged && n == 0)) return FWX_OK;
@@ -635,8 +654,10 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     if (rc) return rc;
     if (ls && (op.k_begin != 0 || op.k_end != n)) return FWX_ERR_INVALID;      // the trace covers whole solves only
     if (ragged && o && (o->k_begin != 0 || o->k_end > 0)) return FWX_ERR_INVALID;   // one range does not fit all orders
-    if ((rc = batch_range(n, op.k_begin, op.k_end, mid ? FWX_BATCH_MID_MAX_N : FWX_BATCH_MAX_N))) return rc;
+    const int32_t max_n = large ? FWX_BATCH_LARGE_MAX_N : mid ? FWX_BATCH_MID_MAX_N : FWX_BATCH_MAX_N;
+    if ((rc = batch_range(n, op.k_begin, op.k_end, max_n))) return rc;
     if (op.engine != FWX_ENGINE_AUTO) return FWX_ERR_UNSUPPORTED;
+    const bool to_large = large && n >= batch_large_min_n();
     DeviceGuard g;
     if ((rc = g.enter(op.device))) return rc;
 
@@ -726,7 +747,15 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
         FWX_HIP(hipMemcpyAsync(d_next0, d_next, b_idx, hipMemcpyDeviceToDevice, s));
     }
 
-    if (ragged && mid)
+    if (to_large) {
+        void *scratch = nullptr;
+        const size_t per = FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n);
+        const size_t b_scratch = per * std::min<size_t>((size_t)count, std::max<size_t>(1, kBatchLargeScratchCap / per));
+        fail_point();
+        if (op.k_end > op.k_begin && (rc = cx.reserve(CallCtx::SMALL, b_scratch, &scratch))) return rc;
+        rc = dev_solve_batch_large<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
+                                      op.k_begin, op.k_end, (unsigned long long *)d_upd, scratch, b_scratch, s);
+    } else if (ragged && mid)
         rc = dev_solve_ragged_mid<T>(count, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, d_n_each, d_offset,
                                      d_order, tiers, (unsigned long long *)d_upd, s, plog);
     else if (ragged)
@@ -1419,6 +1448,70 @@ static_assert(FWX_BATCH_MID_MAX_N == FWX_MID_N, "fwx.h states the largest order 
 int fwx_test_batch_mid_min_n(void) { return batch_mid_min_n(); }
 
 int fwx_test_batch_mid_block(void) { return FWX_MID_B; }
+
+int fwx_solve_batch_large_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, nullptr, false, nullptr, true,
+                                        true);
+    });
+}
+
+int fwx_solve_batch_large_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, nullptr, false, nullptr, true,
+                                       true);
+    });
+}
+
+int fwx_dev_solve_batch_large(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                              int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
+                              void *scratch, size_t scratch_bytes, void *stream)
+{
+    return fwxi::guarded([&]() -> int {
+        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
+        if (count == 0 || n == 0) return FWX_OK;
+        if (!rate || (hops && !next) || stride < (int64_t)n * n) return FWX_ERR_INVALID;
+        const int rc = batch_range(n, k_begin, k_end, FWX_BATCH_LARGE_MAX_N);
+        if (rc) return rc;
+        const bool to_large = n >= batch_large_min_n();
+        // the scratch is judged only where it is used: a call routed to the large tier with pivots to apply
+        if (to_large && k_end > k_begin &&
+            (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n)))
+            return FWX_ERR_INVALID;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        hipStream_t s = (hipStream_t)stream;
+        if (dtype == FWX_F64)
+            return to_large ? dev_solve_batch_large<double>(count, n, (double *)rate, next, hops, stride, k_begin, k_end,
+                                                            d_updates_each, scratch, scratch_bytes, s)
+                            : dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, k_begin, k_end,
+                                                      d_updates_each, s, fwx::PathLog(), true);
+        return to_large ? dev_solve_batch_large<float>(count, n, (float *)rate, next, hops, stride, k_begin, k_end,
+                                                       d_updates_each, scratch, scratch_bytes, s)
+                        : dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, k_begin, k_end,
+                                                 d_updates_each, s, fwx::PathLog(), true);
+    });
+}
+
+static_assert(FWX_BATCH_LARGE_MAX_N <= FWX_LARGE_N, "fwx.h states no order the large tier cannot take");
+static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1000) == FWX_LARGE_SCRATCH_BYTES(1000) &&
+                  FWX_BATCH_LARGE_SCRATCH_BYTES(1) == FWX_LARGE_SCRATCH_BYTES(1),
+              "fwx.h states the scratch the large tier lays out");
+
+int fwx_test_batch_large_min_n(void) { return batch_large_min_n(); }
+
+int fwx_test_batch_large_geometry(int32_t out[4])
+{
+    if (!out) return FWX_ERR_INVALID;
+    out[0] = FWX_LARGE_B;
+    out[1] = FWX_LARGE_S;
+    out[2] = FWX_LARGE_TR;
+    out[3] = FWX_LARGE_TC;
+    return FWX_OK;
+}
 
 // fwx_dev_solve_batch_traced (max_n = FWX_BATCH_MAX_N) and fwx_dev_solve_batch_mid_traced (FWX_BATCH_MID_MAX_N, mid):
 // one contract, the limit apart.

@@ -551,6 +551,22 @@ inline int batch_mid_min_n()
     return FWX_BATCH_MID_MIN_N_DEFAULT;
 }
 
+// Routing of the large batch entry points (fwx_solve_batch_large_*, fwx_dev_solve_batch_large): orders below
+// FWX_BATCH_LARGE_MIN_N are forwarded to the mid entry path (which forwards further by FWX_BATCH_MID_MIN_N), orders
+// from it up to FWX_BATCH_LARGE_MAX_N run the large tier (fwx_large.hip).  An integer 1 ... FWX_BATCH_MID_MAX_N + 1,
+// read on every call; any other value: the default, FWX_BATCH_MID_MAX_N + 1.  No result bit depends on it.
+#define FWX_BATCH_LARGE_MIN_N_DEFAULT (FWX_BATCH_MID_MAX_N + 1)
+inline int batch_large_min_n()
+{
+    if (const char *e = getenv("FWX_BATCH_LARGE_MIN_N")) {
+        char *end = nullptr;
+        const long v = strtol(e, &end, 10);
+        // digits only: no sign, no blank
+        if (*e >= '0' && *e <= '9' && *end == '\0' && v >= 1 && v <= FWX_BATCH_LARGE_MIN_N_DEFAULT) return (int)v;
+    }
+    return FWX_BATCH_LARGE_MIN_N_DEFAULT;
+}
+
 // fwx_solve_batch_lists_*: items walked per launch.  The lists (cap int32 per item), the walk stacks
 // (FWX_EXACT_SCRATCH_INTS(n)) and the item triples + lengths (4) of one launch stay within
 // FWX_BATCH_LISTS_BUDGET_BYTES of device memory; FWX_BATCH_LISTS_CHUNK (environment, read per call: digits only,

@@ -171,6 +171,33 @@ template <typename T>
 hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
                             int k_end, unsigned long long *updates_each, hipStream_t s, PathLog plog = PathLog());
 
+// Large tier of the batched solves (fwx_large.hip): `count` matrices of one order n <= FWX_LARGE_N, same layout and
+// counters as launch_batch_mid, several workgroups per matrix: per block of FWX_LARGE_B pivots one panel launch
+// (column strips of FWX_LARGE_S, matrices) that writes the time-k snapshot panels to `scratch`, and one sweep launch
+// (column tiles of FWX_LARGE_TC, row tiles of FWX_LARGE_TR, matrices) that folds them into the matrix.  Any n from 1
+// up, any stride >= n*n, scalar accesses only; no path trace.  scratch: device memory, 16-byte aligned,
+// FWX_LARGE_SCRATCH_BYTES(n) per matrix (an upper bound over dtype and field set: W, Ct, WN, CNt, WH, CHt, each
+// [B][n]); the batch is solved in groups of scratch_bytes / FWX_LARGE_SCRATCH_BYTES(n) matrices, one after the other
+// on s, and nothing past group x per-matrix bytes is touched.  hipErrorInvalidValue for scratch that is null,
+// misaligned or smaller than one matrix's -- only with a non-empty pivot range.
+#define FWX_LARGE_N 1024
+#define FWX_LARGE_B 16             // pivots per block
+#define FWX_LARGE_S 48             // B + S = 64: a panel row is one wave
+#ifndef FWX_LARGE_TR               // rows of a sweep tile, a multiple of FWX_LARGE_ROWS (build variants: -DFWX_LARGE_TR=32)
+#define FWX_LARGE_TR 16
+#endif
+#ifndef FWX_LARGE_ROWS             // rows a sweep thread folds together
+#define FWX_LARGE_ROWS 4
+#endif
+#ifndef FWX_LARGE_TC               // columns of a sweep tile = threads of a sweep workgroup, a multiple of 64
+#define FWX_LARGE_TC 256
+#endif
+#define FWX_LARGE_SCRATCH_BYTES(n) ((size_t)(n) * (2 * FWX_LARGE_B * 16))
+template <typename T>
+hipError_t launch_batch_large(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
+                              int k_end, unsigned long long *updates_each, void *scratch, size_t scratch_bytes,
+                              hipStream_t s);
+
 // Ragged batch: `count` matrices of different orders, matrix id of order n_each[id] <= FWX_SMALL_N at element
 // offset[id] of rate (next / hops / the trace arrays alike), pitch n_each[id]; whole pivot range of each.  The three
 // index arrays are DEVICE arrays; order / tier_count (host) are what fwx_ragged_plan gives: the matrices grouped by

@@ -1,0 +1,296 @@
+// fwx_large.hip -- the large tier of the batched solves: `count` matrices of one order n <= FWX_LARGE_N (1024),
+// SEVERAL workgroups per matrix.  The scheme is the mid tier's (fwx_mid.hip): pivots are taken FWX_LARGE_B at a time
+// from time-k snapshot panels, the matrix resident in global memory.  One workgroup can neither hold the panels of a
+// 1024-wide matrix in LDS nor sweep it in reasonable time, so the two phases of a block of pivots become TWO
+// LAUNCHES over the whole group of matrices, the matrix index a grid dimension, and the frozen panels travel from
+// the first to the second through caller-provided scratch in global memory.
+//
+// For each block of pivots [k0, k0 + bt), bt <= B, the first block at k_begin:
+//   1. large_panel, grid (column strips of width S, matrices), 1024 threads.  Workgroup (s, b) runs the mid tier's
+//      panel phase on the index set cross U strip, cross = [k0, k0 + bt), strip = [sS, sS + S) n [0, n): P = B + S
+//      positions, position p < B the cross index k0 + p, position B + y the strip index sS + y.  W / WN / WH [t][p] =
+//      entry (k0+t, index(p)), C / CN / CH [t][p] = entry (index(p), k0+t), NaN at (k, k) in both and at positions
+//      without an index (NaN never wins a compare and no such position is ever an operand).  For t = 0 .. bt-2 row t
+//      of both panels is frozen and pivot k0+t applied to the rows u > t: wave w on row u = t + 1 + w, lane on
+//      position p, one barrier per pivot.  The operands a strip needs from outside itself are exactly the cross
+//      entries C[t][k0+u] and W[t][k0+u] -- positions u < B of its own copy of the cross: every strip workgroup
+//      evolves the bt x bt cross block in both forms.  Copies of one entry (in other workgroups, or twice in the
+//      strip that overlaps the cross) see the same operands in the same order while unfrozen and stay bit-equal; the
+//      mid tier's argument does the rest.  The frozen STRIP positions are written to the matrix's scratch panels,
+//      all [B][n]: W, Ct, WN, CNt, WH, CHt.  The matrix is only read; nothing is counted.
+//   2. large_sweep, grid (column tiles of TC, row tiles of TR, matrices), 256 threads.  The workgroup stages
+//      Ct / CNt / CHt [.][its rows] in LDS (NaN for t >= bt), a thread keeps W[0..B)[its column] in registers, wave w
+//      on columns [64w, 64w + 64) of the tile, every wave walking all TR rows, FWX_LARGE_ROWS of them together with t
+//      outermost (independent compare chains: a wave alone on its SIMD is bound by them): C[t][i] is a wave-uniform
+//      LDS read.
+//      Every entry (i, j), i != j, folds C[t][i] * W[t][j] in ascending t with the strict <, keeping the value, the
+//      LAST winning t and the count; only an entry that moved is written back, next = CNt[t*][i] if >= 0 else
+//      WN[t*][j], hops = CHt[t*][i] + WH[t*][j] (WN / WH read from scratch: only winners need them).  One atomic per
+//      workgroup adds the count to updates[b].
+// Between launches only STREAM ORDER is relied on: the sweep of a block reads the panels the panel launch before it
+// wrote and modifies the matrix, the next panel launch reads the matrix after it.  (One launch could not do both: a
+// sweep workgroup that rebuilt its own panels would read pivot rows and columns other workgroups are overwriting.)
+// No cooperative launch, no grid barrier, no spin-wait, no flag between workgroups.  Every __syncthreads is reached
+// by the whole workgroup with a trip count that is a function of (n, range, geometry) alone; there is no early exit.
+// Scalar element accesses only: any n from 1 up (smaller than B, S or a tile included), any stride >= n*n, no
+// alignment beyond the element; tiles and strips are ragged at the right and bottom edges.  The gap between
+// matrices is never read or written, the diagonal's rate neither.
+//
+// Scratch: FWX_LARGE_SCRATCH_BYTES(n) per matrix of the group, laid out for the dtype and field set of the call
+// (W, Ct as T, then the int32 panels), an upper bound: 2 panels x B rows x n columns x 16 bytes.  launch_batch_large
+// solves the batch in groups of as many matrices as the scratch holds, one group after the other on the stream.
+#include "fwx_kernels.h"
+
+#include <algorithm>
+
+namespace fwx {
+namespace {
+
+template <typename T> __device__ __forceinline__ T large_nan();
+template <> __device__ __forceinline__ float large_nan<float>() { return __builtin_nanf(""); }
+template <> __device__ __forceinline__ double large_nan<double>() { return __builtin_nan(""); }
+
+constexpr int kLargeB = FWX_LARGE_B;
+constexpr int kLargeS = FWX_LARGE_S;
+constexpr int kLargeTR = FWX_LARGE_TR;
+constexpr int kLargeTC = FWX_LARGE_TC;
+constexpr int kLargeP = kLargeB + kLargeS;            // positions of a panel workgroup: one wave wide
+constexpr int kPanelThreads = 64 * kLargeB;           // one wave per panel row
+constexpr int kSweepThreads = kLargeTC;               // one thread per column of the tile
+// Pitch of the panel kernel's LDS panels, in elements: the column loads run over t first and store one pitch apart;
+// an odd pitch spreads the 16 pivots of a position over the banks where 64 would put them all on one.
+constexpr int kLargePitch = kLargeP + 1;
+constexpr int kLargeRows = FWX_LARGE_ROWS;            // sweep: rows folded together per thread
+static_assert(kLargeP == 64, "a panel row is one wave: lane = position");
+static_assert(kLargeB == 16, "t = e & (B - 1) and 16 waves of a 1024-thread workgroup; FWX_LARGE_SCRATCH_BYTES");
+static_assert(kLargeTC % 64 == 0 && kLargeTC <= 1024 && kLargeTR % kLargeRows == 0, "waves of whole columns");
+
+// The scratch panels of one matrix, for dtype T: all [B][n], pitch n.
+template <typename T> struct LargePanels {
+    T *W, *Ct;
+    int32_t *WN, *CNt, *WH, *CHt;
+};
+template <typename T>
+__device__ __forceinline__ LargePanels<T> large_panels(char *scratch, size_t per_matrix, unsigned b, int n)
+{
+    const size_t bn = (size_t)kLargeB * (size_t)n;
+    LargePanels<T> p;
+    p.W = (T *)(scratch + (size_t)b * per_matrix);
+    p.Ct = p.W + bn;
+    p.WN = (int32_t *)(p.Ct + bn);
+    p.CNt = p.WN + bn;
+    p.WH = p.CNt + bn;
+    p.CHt = p.WH + bn;
+    return p;
+}
+
+template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+__global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, const int32_t *next, const int32_t *hops,
+                                                             int n, long long stride, int k0, int bt, char *scratch,
+                                                             size_t per_matrix)
+{
+    constexpr int B = kLargeB, S = kLargeS, Q = kLargePitch;
+    __shared__ T W[B][Q], C[B][Q];
+    __shared__ int32_t WN[HAS_NEXT ? B : 1][HAS_NEXT ? Q : 1], CN[HAS_NEXT ? B : 1][HAS_NEXT ? Q : 1];
+    __shared__ int32_t WH[HAS_HOPS ? B : 1][HAS_HOPS ? Q : 1], CH[HAS_HOPS ? B : 1][HAS_HOPS ? Q : 1];
+
+    const int tid = threadIdx.x;
+    const int s0 = (int)blockIdx.x * S;
+    const size_t off = (size_t)blockIdx.y * (size_t)stride;
+    rate += off;
+    if constexpr (HAS_NEXT) next += off;
+    if constexpr (HAS_HOPS) hops += off;
+    // the index (a row or a column of the matrix) of position p, -1 where it has none
+    auto index_of = [&](int p) {
+        const int x = p < B ? (p < bt ? k0 + p : -1) : s0 + p - B;
+        return x < n ? x : -1;
+    };
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+
+    // ---- load: pivot rows, wave t on row k0+t, lane on position ---------------------------------------------
+    if (wave < bt) {
+        const int t = wave, k = k0 + t, x = index_of(lane);
+        const size_t e = (size_t)k * n + (x < 0 ? 0 : x);
+        W[t][lane] = (x < 0 || x == k) ? large_nan<T>() : rate[e];
+        if constexpr (HAS_NEXT) WN[t][lane] = x < 0 ? -1 : next[e];
+        if constexpr (HAS_HOPS) WH[t][lane] = x < 0 ? 0 : hops[e];
+    }
+    // ---- load: pivot columns, thread on (position, t), t fastest: 16 consecutive elements of a row ----------
+    {
+        const int t = tid & (B - 1), p = tid >> 4;
+        if (t < bt) {
+            const int k = k0 + t, x = index_of(p);
+            const size_t g = (size_t)(x < 0 ? 0 : x) * n + k;
+            C[t][p] = (x < 0 || x == k) ? large_nan<T>() : rate[g];
+            if constexpr (HAS_NEXT) CN[t][p] = x < 0 ? -1 : next[g];
+            if constexpr (HAS_HOPS) CH[t][p] = x < 0 ? 0 : hops[g];
+        }
+    }
+    __syncthreads();
+    // ---- pivots k0 .. k0+bt-2 on the rows of both panels that are not yet frozen ----------------------------
+    for (int t = 0; t + 1 < bt; ++t) {
+        const int u = t + 1 + wave;                           // wave-uniform; position u is the cross index k0+u
+        if (u < bt) {
+            const int c = lane;
+            // row k0+u of the matrix: entry (k0+u, index(c)) against (k0+u, k) * (k, index(c))
+            const T cand_w = C[t][u] * W[t][c];
+            if (W[u][c] < cand_w) {
+                W[u][c] = cand_w;
+                if constexpr (HAS_NEXT) { const int32_t h = CN[t][u]; WN[u][c] = h >= 0 ? h : WN[t][c]; }
+                if constexpr (HAS_HOPS) WH[u][c] = CH[t][u] + WH[t][c];
+            }
+            // column k0+u of the matrix: entry (index(c), k0+u) against (index(c), k) * (k, k0+u)
+            const T cand_c = C[t][c] * W[t][u];
+            if (C[u][c] < cand_c) {
+                C[u][c] = cand_c;
+                if constexpr (HAS_NEXT) { const int32_t h = CN[t][c]; CN[u][c] = h >= 0 ? h : WN[t][u]; }
+                if constexpr (HAS_HOPS) CH[u][c] = CH[t][c] + WH[t][u];
+            }
+        }
+        __syncthreads();
+    }
+    // ---- store the frozen strip positions: wave t on row t of the six panels ---------------------------------
+    if (wave < bt && lane >= B) {
+        const int x = s0 + lane - B;
+        if (x < n) {
+            const LargePanels<T> pn = large_panels<T>(scratch, per_matrix, blockIdx.y, n);
+            const size_t e = (size_t)wave * n + x;
+            pn.W[e] = W[wave][lane];
+            pn.Ct[e] = C[wave][lane];
+            if constexpr (HAS_NEXT) { pn.WN[e] = WN[wave][lane]; pn.CNt[e] = CN[wave][lane]; }
+            if constexpr (HAS_HOPS) { pn.WH[e] = WH[wave][lane]; pn.CHt[e] = CH[wave][lane]; }
+        }
+    }
+}
+
+template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+__global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *next, int32_t *hops, int n,
+                                                             long long stride, int bt, char *scratch,
+                                                             size_t per_matrix, unsigned long long *updates)
+{
+    constexpr int B = kLargeB, TR = kLargeTR, TC = kLargeTC;
+    __shared__ T C[B][TR];
+    __shared__ int32_t CN[HAS_NEXT ? B : 1][HAS_NEXT ? TR : 1], CH[HAS_HOPS ? B : 1][HAS_HOPS ? TR : 1];
+    __shared__ unsigned int s_cnt;
+
+    const int tid = threadIdx.x;
+    const int j = (int)blockIdx.x * TC + tid, i0 = (int)blockIdx.y * TR;
+    const int rows = min(TR, n - i0);                         // >= 1: the grid covers [0, n) and no more
+    const size_t off = (size_t)blockIdx.z * (size_t)stride;
+    rate += off;
+    if constexpr (HAS_NEXT) next += off;
+    if constexpr (HAS_HOPS) hops += off;
+    const LargePanels<T> pn = large_panels<T>(scratch, per_matrix, blockIdx.z, n);
+
+    if (tid == 0) s_cnt = 0;
+    for (int e = tid; e < B * TR; e += kSweepThreads) {       // lane on (t, row), row fastest
+        const int t = e / TR, r = e - t * TR;
+        const bool have = t < bt && r < rows;
+        const size_t g = (size_t)t * n + i0 + r;
+        C[t][r] = have ? pn.Ct[g] : large_nan<T>();
+        if constexpr (HAS_NEXT) CN[t][r] = have ? pn.CNt[g] : -1;
+        if constexpr (HAS_HOPS) CH[t][r] = have ? pn.CHt[g] : 0;
+    }
+    T w[B];
+#pragma unroll
+    for (int t = 0; t < B; ++t) w[t] = (t < bt && j < n) ? pn.W[(size_t)t * n + j] : large_nan<T>();
+    __syncthreads();
+
+    unsigned int mine = 0;                                    // a WAVE total (scalar)
+    // a wave whose 64 columns all lie past the edge has nothing to fold (wave-uniform)
+    if ((int)blockIdx.x * TC + (tid & ~63) < n) {
+        for (int r0 = 0; r0 < rows; r0 += kLargeRows) {
+            // kLargeRows rows together, t outermost: independent compare chains for a wave that is alone on its SIMD.
+            // +inf where a lane has no entry (past an edge, or the diagonal's): no candidate compares greater, and the
+            // rows of C past the edge are NaN
+            T v[kLargeRows];
+            int tb[kLargeRows];
+#pragma unroll
+            for (int m = 0; m < kLargeRows; ++m) {
+                const int i = i0 + r0 + m;
+                v[m] = (T)__builtin_huge_val();
+                tb[m] = -1;
+                if (r0 + m < rows && j < n && i != j) v[m] = rate[(size_t)i * n + j];
+            }
+#pragma unroll
+            for (int t = 0; t < B; ++t) {
+#pragma unroll
+                for (int m = 0; m < kLargeRows; ++m) {
+                    const T cand = C[t][r0 + m] * w[t];       // NaN where a skip applies
+                    const bool p = v[m] < cand;               // false on NaN
+                    v[m] = p ? cand : v[m];
+                    tb[m] = p ? t : tb[m];
+                    mine += (unsigned int)__builtin_popcountll(__ballot(p));
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < kLargeRows; ++m) {
+                if (tb[m] >= 0) {
+                    const int r = r0 + m;
+                    const size_t e = (size_t)(i0 + r) * n + j;
+                    rate[e] = v[m];
+                    if constexpr (HAS_NEXT) {
+                        const int32_t h = CN[tb[m]][r];
+                        next[e] = h >= 0 ? h : pn.WN[(size_t)tb[m] * n + j];
+                    }
+                    if constexpr (HAS_HOPS) hops[e] = CH[tb[m]][r] + pn.WH[(size_t)tb[m] * n + j];
+                }
+            }
+        }
+    }
+    if (updates) {                                            // workgroup-uniform
+        if (mine && (tid & 63) == 0) atomicAdd(&s_cnt, mine);
+        __syncthreads();
+        if (tid == 0 && s_cnt) atomicAdd(&updates[blockIdx.z], (unsigned long long)s_cnt);
+    }
+}
+
+}  // namespace
+
+template <typename T>
+hipError_t launch_batch_large(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
+                              int k_end, unsigned long long *updates_each, void *scratch, size_t scratch_bytes,
+                              hipStream_t s)
+{
+    if (count <= 0 || n <= 0) return hipSuccess;
+    if (k_end <= k_begin) return hipSuccess;
+    if (n > FWX_LARGE_N || (hops && !next) || k_begin < 0 || k_end > n || stride < (long long)n * n)
+        return hipErrorInvalidValue;
+    const size_t per_matrix = FWX_LARGE_SCRATCH_BYTES(n);
+    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < per_matrix) return hipErrorInvalidValue;
+    // matrices per group: what the scratch holds, and what one grid dimension does
+    const long long group = std::min<long long>((long long)(scratch_bytes / per_matrix), 65535);
+    const dim3 strips((n + kLargeS - 1) / kLargeS), tiles((n + kLargeTC - 1) / kLargeTC, (n + kLargeTR - 1) / kLargeTR);
+    char *sc = (char *)scratch;
+    for (long long b0 = 0; b0 < count; b0 += group) {
+        const unsigned cnt = (unsigned)std::min<long long>(group, count - b0);
+        const size_t off = (size_t)b0 * (size_t)stride;
+        T *r = rate + off;
+        int32_t *nx = next ? next + off : nullptr, *hp = hops ? hops + off : nullptr;
+        unsigned long long *u = updates_each ? updates_each + b0 : nullptr;
+        for (int k0 = k_begin; k0 < k_end; k0 += kLargeB) {
+            const int bt = std::min(kLargeB, k_end - k0);
+#define FWX_BATCH_LARGE(HN, HH)                                                                                        \
+    do {                                                                                                               \
+        hipLaunchKernelGGL((large_panel<T, HN, HH>), dim3(strips.x, cnt), dim3(kPanelThreads), 0, s, r, nx, hp, n,     \
+                           stride, k0, bt, sc, per_matrix);                                                            \
+        hipLaunchKernelGGL((large_sweep<T, HN, HH>), dim3(tiles.x, tiles.y, cnt), dim3(kSweepThreads), 0, s, r, nx,    \
+                           hp, n, stride, bt, sc, per_matrix, u);                                                      \
+    } while (0)
+            if (hops) FWX_BATCH_LARGE(true, true);
+            else if (next) FWX_BATCH_LARGE(true, false);
+            else FWX_BATCH_LARGE(false, false);
+#undef FWX_BATCH_LARGE
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+template hipError_t launch_batch_large<float>(float *, int32_t *, int32_t *, int, int, long long, int, int,
+                                              unsigned long long *, void *, size_t, hipStream_t);
+template hipError_t launch_batch_large<double>(double *, int32_t *, int32_t *, int, int, long long, int, int,
+                                               unsigned long long *, void *, size_t, hipStream_t);
+
+}  // namespace fwx

@@ -19,6 +19,7 @@ from ._lib import (FWX_ENGINE_AUTO, FWX_ENGINE_FUSED, FWX_ENGINE_PERK, FWX_F32, 
 
 __all__ = ["solve", "solve_batch", "dev_solve_batch", "solve_batch_lists", "dev_solve_batch_traced",
            "dev_exact_paths_batch", "solve_batch_mid", "dev_solve_batch_mid", "solve_batch_mid_lists",
+           "solve_batch_large", "dev_solve_batch_large",
            "dev_solve_batch_mid_traced", "dev_exact_paths_batch_mid", "ragged_plan", "solve_ragged", "solve_ragged_lists", "dev_solve_ragged",
            "dev_exact_paths_ragged", "ragged_mid_plan", "solve_ragged_mid", "solve_ragged_mid_lists",
            "dev_solve_ragged_mid", "dev_exact_paths_ragged_mid", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
@@ -119,6 +120,14 @@ def solve_batch_mid(rate, nxt=None, hops=None, *, device=-1, k_begin=0, k_end=0,
     return _solve_batch("fwx_solve_batch_mid", rate, nxt, hops, device, k_begin, k_end, count_updates)
 
 
+def solve_batch_large(rate, nxt=None, hops=None, *, device=-1, k_begin=0, k_end=0, count_updates=False):
+    """solve_batch_mid with the limit at n <= FWX_BATCH_LARGE_MAX_N (fwx_solve_batch_large_f64 / _f32): orders from
+    FWX_BATCH_LARGE_MIN_N (environment, default 257) up run the large tier -- several workgroups per matrix, two
+    launches per 16 pivots over the whole batch -- and smaller ones are forwarded to solve_batch_mid's routing.  Same
+    arrays, same results, same return value."""
+    return _solve_batch("fwx_solve_batch_large", rate, nxt, hops, device, k_begin, k_end, count_updates)
+
+
 def _solve_batch(stem, rate, nxt, hops, device, k_begin, k_end, count_updates):
     if not (isinstance(rate, np.ndarray) and rate.ndim == 3 and rate.shape[1] == rate.shape[2]):
         raise ValueError("rate must be a numpy array of shape (count, n, n)")
@@ -156,7 +165,22 @@ def dev_solve_batch_mid(rate_t, count, n, *, next_t=None, hops_t=None, stride=No
                      stream)
 
 
-def _dev_solve_batch(name, rate_t, count, n, next_t, hops_t, stride, k_begin, k_end, updates_t, stream):
+def dev_solve_batch_large(rate_t, count, n, *, next_t=None, hops_t=None, stride=None, k_begin=0, k_end=0,
+                          updates_t=None, scratch_t=None, stream=None):
+    """fwx_dev_solve_batch_large: dev_solve_batch_mid with the limit at n <= FWX_BATCH_LARGE_MAX_N; routing by
+    FWX_BATCH_LARGE_MIN_N as solve_batch_large.  scratch_t: a device array of at least
+    _lib.batch_large_scratch_bytes(n) bytes, 16-byte aligned -- the call solves as many matrices at a time as it
+    holds; None: one for the whole batch is allocated here.  Returns the scratch array: it must stay alive until the
+    stream has run the call."""
+    if scratch_t is None:
+        scratch_t = _empty_like_device(rate_t, (max(count, 1) * _lib.batch_large_scratch_bytes(n),), "uint8")
+    _dev_solve_batch("fwx_dev_solve_batch_large", rate_t, count, n, next_t, hops_t, stride, k_begin, k_end, updates_t,
+                     stream, scratch_t)
+    return scratch_t
+
+
+def _dev_solve_batch(name, rate_t, count, n, next_t, hops_t, stride, k_begin, k_end, updates_t, stream,
+                     scratch_t=None):
     stride = n * n if stride is None else int(stride)
     need = (count - 1) * stride + n * n if count > 0 else 0
     assert rate_t.is_cuda and rate_t.is_contiguous() and rate_t.numel() >= need
@@ -169,7 +193,9 @@ def _dev_solve_batch(name, rate_t, count, n, next_t, hops_t, stride, k_begin, k_
         count, n, _tensor_dtype_code(rate_t), vp(rate_t.data_ptr()),
         vp(next_t.data_ptr()) if next_t is not None else None,
         vp(hops_t.data_ptr()) if hops_t is not None else None, stride, k_begin, k_end,
-        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)), name)
+        vp(updates_t.data_ptr()) if updates_t is not None else None,
+        *(() if scratch_t is None else (vp(scratch_t.data_ptr()), scratch_t.numel() * scratch_t.element_size())),
+        _stream_ptr(stream, rate_t)), name)
 
 
 # solve_batch_lists with cap=None: the first capacity tried, and the last (the lists of an input with arbitrage

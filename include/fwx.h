@@ -237,6 +237,67 @@ int fwx_test_batch_mid_min_n(void);
 /* TEST HOOK: the pivots per pass of the mid tier (B).  Needs no device.  Not for production use. */
 int fwx_test_batch_mid_block(void);
 
+/* ---- batched large solves: many matrices of one order n <= FWX_BATCH_LARGE_MAX_N, several workgroups each ----
+ * The calls above stop at n = 256, where one workgroup still solves its matrix alone.  A price history of a 30 x 20
+ * market (600 vertices) or a what-if sweep over a 1000-vertex book is a batch of larger matrices, and one such solve
+ * does not fill the chip.  These entry points take the batch up to n = 1024: the mid tier's scheme -- 16 pivots per
+ * pass from time-k snapshot panels -- with the two phases of a pass as two launches over the whole batch, the
+ * panels in device scratch between them, column strips (panel) and tiles (sweep) of every matrix on workgroups of
+ * their own.  Every matrix gets the full semantics above, the list rule included; there is no domain check and no
+ * routing by content, and each matrix comes back bit-identical to the reference loop on that matrix alone -- rate,
+ * next, hops (diagonals included) and U.  No exact `_path` lists and no ragged form above 256.
+ *
+ * The contract is that of fwx_solve_batch_mid_* / fwx_dev_solve_batch_mid, with the limit at
+ * FWX_BATCH_LARGE_MAX_N: count matrices of order n, matrix b at rate + b*n*n (next / hops alike, both optional, hops
+ * needs next); HOST arrays, solved in place.  updates_each: optional, count entries, U of each matrix.
+ * count == 0 or n == 0: FWX_OK, nothing is touched.  FWX_ERR_INVALID: count < 0, n < 0, rate NULL, hops without
+ * next, a bad struct_size or pivot range.  FWX_ERR_UNSUPPORTED: n > FWX_BATCH_LARGE_MAX_N, or opts->engine other
+ * than FWX_ENGINE_AUTO.  All of these are decided before any device call; then FWX_ERR_NO_DEVICE without a device,
+ * the arrays untouched.  opts: device, k_begin / k_end (one range for every matrix), stream / use_stream and
+ * updates_out (the SUM of U over the batch) are honoured; serpentine is ignored.  The host forms take the scratch
+ * panels from the pooled per-call context, at most 256 MiB: larger batches run in groups on the one stream.
+ * Routing: FWX_BATCH_LARGE_MIN_N (environment, read per call; an integer 1 ... 257, default 257, anything else
+ * means the default): orders below it are forwarded to fwx_solve_batch_mid_* / fwx_dev_solve_batch_mid (which
+ * forward further by FWX_BATCH_MID_MIN_N), orders from it up to 1024 run the large tier.  No result bit depends on
+ * it; it exists so that tests and A/B runs can put n <= 256 through the large tier.
+ * When to use it: see the measurements beside the device form below.                                        */
+#define FWX_BATCH_LARGE_MAX_N 1024
+/* Device scratch ONE matrix of order n needs in fwx_dev_solve_batch_large, in bytes: the snapshot panels of 16
+ * pivots, 2 panels x 16 rows x n columns x 16 bytes (rate + next + hops in f64; an upper bound for every dtype and
+ * field set).                                                                                                 */
+#define FWX_BATCH_LARGE_SCRATCH_BYTES(n) ((size_t)(n) * 512)
+int fwx_solve_batch_large_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, const fwx_opts *opts);
+int fwx_solve_batch_large_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, const fwx_opts *opts);
+/* The same on caller-owned DEVICE memory, asynchronous on `stream`, nothing allocated or synchronised; stride,
+ * pivots, dtype and d_updates_each (INCREMENTED) as fwx_dev_solve_batch_mid.  scratch: device memory for the
+ * snapshot panels, 16-byte aligned, scratch_bytes >= FWX_BATCH_LARGE_SCRATCH_BYTES(n); the batch is solved in groups
+ * of floor(scratch_bytes / FWX_BATCH_LARGE_SCRATCH_BYTES(n)) matrices, one group after the other on `stream`, and
+ * nothing past group x FWX_BATCH_LARGE_SCRATCH_BYTES(n) bytes of it is touched.  FWX_ERR_INVALID for scratch that is
+ * NULL, misaligned or too small for one matrix -- only when n is routed to the large tier and the pivot range is not
+ * empty; below FWX_BATCH_LARGE_MIN_N scratch is ignored.  Statuses otherwise as above (n > FWX_BATCH_LARGE_MAX_N:
+ * FWX_ERR_UNSUPPORTED).  A solve is 2 * ceil(pivots / 16) launches per group.
+ * When it pays (MI355X, f64 + next + hops, profiles/r24_batch_large.txt): one call against `count` blocking
+ * fwx_dev_solve calls.  One matrix takes the call 0.42 ms at n = 257, 0.59 at 384, 0.78 at 512, 1.20 at 768 and
+ * 1.60 ms at 1024 -- 64 pivot blocks of a 7.7 us panel launch and a 17.3 us sweep launch, back to back -- where
+ * fwx_dev_solve takes 1.03, 0.45, 0.55, 0.82 and 1.07 ms.  The call overtakes the loop at count = 1 for n = 257 and at
+ * count = 2 for n = 384 ... 1024 (1.5x ... 1.1x); at count = 16 it is 26x, 14x, 9.7x, 7.4x and 4.7x faster, at
+ * count = 256 66x, 21x, 15x, 7.5x and 4.4x (0.048 ms per matrix at n = 512, 0.33 ms at n = 1024).  For ONE matrix of
+ * order 384 and up call fwx_dev_solve: this entry point does not route it there, because it may not block or
+ * allocate.  Around n = 256 fwx_dev_solve_batch_mid is the better call somewhere between 64 and 256 matrices
+ * (64: 1.31 ms at n = 256 against 1.05 ms at n = 257 here; 256: 1.37 against 3.21 ms); for fewer matrices this
+ * tier is the faster one, 0.42 against 1.26 ms up to 4 matrices (FWX_BATCH_LARGE_MIN_N routes them here).     */
+int fwx_dev_solve_batch_large(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                              int64_t stride, int32_t k_begin, int32_t k_end,
+                              unsigned long long *d_updates_each,
+                              void *scratch, size_t scratch_bytes, void *stream);
+/* TEST HOOK: what FWX_BATCH_LARGE_MIN_N parses to right now.  Needs no device.  Not for production use. */
+int fwx_test_batch_large_min_n(void);
+/* TEST HOOK: the geometry of the large tier: out[0] = pivots per pass (B), out[1] = width of a panel strip (S),
+ * out[2] / out[3] = rows / columns of a sweep tile.  Needs no device.  Not for production use. */
+int fwx_test_batch_large_geometry(int32_t out[4]);
+
 /* ---- batched small solves with the exact `_path` lists ----------------------------------------------------
  * The reference returns, per entry, the list it concatenated when the entry last improved (`_path`,
  * Algorithms.hs:55; see "Exact `_path` lists" below): under exact ties -- its 1.0 edges between the same currency
