@@ -1324,6 +1324,14 @@ int fwx_test_perk_fold(void) { return perk_fold_compare() ? 1 : 0; }
 
 int fwx_test_perk_walk(void) { return perk_walk() ? 1 : 0; }
 
+int fwx_test_perk_deep(uint64_t *deep_launches, int reset)
+{
+    const uint64_t v = reset ? g_perk_deep_launches.exchange(0, std::memory_order_relaxed)
+                             : g_perk_deep_launches.load(std::memory_order_relaxed);
+    if (deep_launches) *deep_launches = v;
+    return perk_deep() ? 1 : 0;
+}
+
 int fwx_test_perk_wide(uint64_t *wide_launches, int reset)
 {
     const uint64_t v = reset ? g_perk_wide_launches.exchange(0, std::memory_order_relaxed)

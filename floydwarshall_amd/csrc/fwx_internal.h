@@ -507,6 +507,19 @@ inline bool perk_walk()
     return !(e && !strcmp(e, "0"));
 }
 
+// The deep pass (round 25): where the ladder of the multi-pivot schedule starts at 16 -- an uncounted f32 call at the
+// width 8 with the wide pass and the walk on -- it starts at 32: relax_walk with 8 bytes of a row per lane and 32
+// pivots per streaming pass, so a 64-pivot block is one panel launch and two sweeps.  FWX_PERK_DEEP=0 gives the
+// schedule before it, launch for launch; anything else, or unset, leaves the 32-pivot pass on; read on every call.
+// Both hooks' counters read the same either way (a 32-pivot launch is four 8-pivot groups and two wide ones); the
+// 32-pivot launches themselves are g_perk_deep_launches.  For tests and A/B runs in one binary, and the remedy for
+// inputs with sparse sign-set operands.  No result bit depends on it.
+inline bool perk_deep()
+{
+    const char *e = getenv("FWX_PERK_DEEP");
+    return !(e && !strcmp(e, "0"));
+}
+
 // The fold of relax_kt's non-counting f32 sweeps: FWX_PERK_FOLD=compare forces the compare form in every tile, read on
 // every call; anything else, or unset: automatic (each wave takes the max form where the operands it has loaded
 // are all NaN or sign-clear).  For tests and A/B runs in one binary.  No result bit depends on it (DESIGN.md
@@ -591,7 +604,10 @@ inline long long batch_lists_chunk(int n, int cap)
 // A 16-pivot sweep applies two 8-pivot groups and adds 2 to [3], so that the five counters read the same with the
 // wide pass on and off; the number of 16-pivot launches themselves is g_perk_wide_launches (fwx_test_perk_wide).
 inline std::atomic<uint64_t> g_perk_launches[5];
+// A 32-pivot sweep (round 25) adds 4 to [3] and 2 to g_perk_wide_launches, for the same reason, and 1 to
+// g_perk_deep_launches (fwx_test_perk_deep).
 inline std::atomic<uint64_t> g_perk_wide_launches;
+inline std::atomic<uint64_t> g_perk_deep_launches;
 
 // Snapshot panels (W and Ct of one 64-pivot block) of the multi-pivot schedule: perk_kt_ws_bytes.  A blocking
 // entry point that holds a per-call context passes that context's workspace.  fwx_dev_relax* has no workspace
@@ -662,7 +678,8 @@ private:
 // each, all on `s`.  A ragged end of a block goes down the powers of two; a last single pivot is a relax_k
 // launch on the live row -- exact, because between launches the matrix is a consistent time-k state.
 // An uncounted f32 call at np == 8 starts the ladder at 16 (perk_wide): the panels hold the snapshots of all 64
-// pivots of the block, so the second 8-pivot sweep of a pair need not re-read the matrix.
+// pivots of the block, so the second 8-pivot sweep of a pair need not re-read the matrix; with the walk on as well it
+// starts at 32 (perk_deep), one streaming pass per half block.
 template <typename T>
 inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine, int np,
                           unsigned long long *d_updates, hipStream_t s, void *ws)
@@ -693,10 +710,12 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
         if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
         FWX_HIP(e);
         g_perk_launches[slot].fetch_add((uint64_t)groups, std::memory_order_relaxed);
-        if (groups == 2) g_perk_wide_launches.fetch_add(1, std::memory_order_relaxed);
+        if (groups >= 2) g_perk_wide_launches.fetch_add((uint64_t)groups / 2, std::memory_order_relaxed);
+        if (groups == 4) g_perk_deep_launches.fetch_add(1, std::memory_order_relaxed);
         return thr.tick(s);
     };
-    const int g_top = np == 8 && !d_updates && std::is_same<T, float>::value && perk_wide() ? 16 : np;
+    const bool wide = np == 8 && !d_updates && std::is_same<T, float>::value && perk_wide();
+    const int g_top = wide ? (a.walk && perk_deep() ? 32 : 16) : np;
     for (int k0 = k_begin; k0 < k_end; k0 += FWX_FUSED_B) {
         const int bt = std::min(FWX_FUSED_B, k_end - k0);
         int t = 0;
@@ -707,7 +726,7 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
                 for (; bt - t >= g; t += g) {
                     a.k = k0 + t; a.np = g; a.w = w + (size_t)t * n; a.ct = ct + (size_t)t * ld;
                     a.flip = serpentine ? rev * (sweeps++ & 1) : 0;
-                    if (const int rc = after(fwx::launch_relax_kt<T>(a, s), g >= 8 ? 3 : g == 4 ? 2 : 1, g == 16 ? 2 : 1))
+                    if (const int rc = after(fwx::launch_relax_kt<T>(a, s), g >= 8 ? 3 : g == 4 ? 2 : 1, g >= 16 ? g / 8 : 1))
                         return rc;
                 }
         }

@@ -121,11 +121,13 @@ template <typename T> hipError_t launch_relax(const RelaxArgs<T> &a, hipStream_t
 #define FWX_PERK_WALK_UNROLL 8     //   flight, cache policy of the stream (WALK_POL_*, fwx_kernels.hip: 0 = default-
 #define FWX_PERK_WALK_POL 0        //   policy loads everywhere), slots reloaded one by one behind their folds (1) or
 #define FWX_PERK_WALK_ROLL false   //   in batches (0).  What was timed: profiles/r23_tune_relax_pivots.txt
+#define FWX_PERK_DEEP_RPB 64       // relax_walk at 32 pivots and 8 bytes of a row per lane (round 25): rows per workgroup
+#define FWX_PERK_DEEP_UNROLL 8     //   and row slots in flight.  What was timed: profiles/r25_tune_relax_pivots.txt
 template <typename T> struct RelaxKtArgs {
     T *rate;                       // n x n
     const T *w;                    // w[t*n + j]      = row k+t at time k+t          (t < np)
     const T *ct;                   // ct[t*ct_ld + i] = column k+t at time k+t, NaN at i == k+t
-    int ct_ld, n, k, np;           // np: 2, 4 or 8; 16 for f32 with updates == nullptr
+    int ct_ld, n, k, np;           // np: 2, 4 or 8; 16 for f32 with updates == nullptr; 32 for that with `walk` as well
     int flip;                      // as RelaxArgs
     long long temporal_bytes = -1;
     int store_bytes = 0;

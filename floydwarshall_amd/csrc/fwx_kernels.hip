@@ -6,7 +6,7 @@
 // predicated stores.  No MFMA: (max, x) with a strict compare is not a dense contraction.
 //
 // Kernel 1  relax_k      one launch per pivot k over a slab of rows (HBM-bound streaming read)
-//           relax_kt     2, 4, 8 or 16 neighbouring pivots per launch from time-k snapshots (rates only, whole
+//           relax_kt     2, 4, 8, 16 or (relax_walk) 32 neighbouring pivots per launch from time-k snapshots (rates only, whole
 //                        matrix in place): the same stream, read once per launch instead of once per pivot
 // Kernel 2  snapshot_row copies pivot row k into the snapshot panel (panel phase, multi-GPU)
 //
@@ -34,6 +34,7 @@ namespace fwx {
 
 template <typename T, int W> struct VecOf;
 template <> struct VecOf<float, 4> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct VecOf<float, 2> { typedef float type __attribute__((ext_vector_type(2))); };
 template <> struct VecOf<double, 2> { typedef double type __attribute__((ext_vector_type(2))); };
 template <> struct VecOf<float, 1> { typedef float type; };
 template <> struct VecOf<double, 1> { typedef double type; };
@@ -754,8 +755,16 @@ void relax_kt(T *rate, const T *w, const T *ct, int ct_ld, int n, int k,
 //   WALK_POL_LOOP   two copies of the steady loop alone, one per policy; the head loads as WALK_POL_FENCE.  Spills
 // No result bit depends on it.
 //
-// Staging: thread t stages the cells t, t + 256, ... of the RPB x 16 values of Ct, one writer per cell.  The race-
+// Staging: thread t stages the cells t, t + 256, ... of the RPB x NP values of Ct, one writer per cell.  The race-
 // freedom and write-back arguments are relax_kt's: every element belongs to exactly one lane of one workgroup.
+//
+// Round 25: NP = 32 with W = 2.  A lane owns 8 bytes of a row instead of 16, so 32 rows of W are the same 64 registers
+// and the kernel stays at three waves; the strip is 512 columns, the diagonal component of row r is r % 2, a store
+// group of G bytes is G / 8 lanes, a staged row of Ct is eight 16-byte reads.  Per row-vector the max form is the same
+// 64 multiplies, 30 v_max3_f32, 2 v_max_f32 and 2 compares; the compare form is 32 steps of two chains, with the next
+// step's multiplies between a step's compares and its selects (vec_cmp).  The matrix is streamed once per 32 pivots.
+// What ships: 64 rows per workgroup, 8 slots, batches, plain loads (profiles/r25_tune_relax_pivots.txt,
+// r25_relax_walk_isa.txt); the schedule: relax_range_kt, FWX_PERK_DEEP.
 // -------------------------------------------------------------------------------------------------
 enum { WALK_POL_PLAIN = 0, WALK_POL_FENCE = 1, WALK_POL_LOOP = 2 };
 
@@ -771,16 +780,17 @@ template <int N, typename F> __device__ __forceinline__ void for_slots(F &&f)
 
 template <int UNROLL> constexpr int relax_walk_min_waves() { return UNROLL <= 4 ? 4 : 3; }
 
-template <int RPB, int UNROLL, int GL, int POL, bool ROLL>
+template <int RPB, int UNROLL, int GL, int POL, bool ROLL, int NP = 16, int W = 4>
 __global__ __launch_bounds__(256, (relax_walk_min_waves<UNROLL>()))
 void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, int k, int nstrips, int flip,
                 int nt_below, unsigned strip_magic, int fold_compare)
 {
-    constexpr int NP = 16, W = 4, SW = 256 * W;
+    constexpr int SW = 256 * W;
     constexpr int STAGE = (RPB * NP + 255) / 256;     // staged values per thread
     using L = Lanes<float, W>;
     using V = typename L::V;
-    static_assert(GL == 1 || GL == 2 || GL == 4 || GL == 8, "store group: 1, 2, 4 or 8 lanes");
+    static_assert((NP == 16 && W == 4) || (NP == 32 && W == 2), "16 pivots on 16 bytes of a row or 32 on 8: 64 registers of W");
+    static_assert(GL * W == 4 || GL * W == 8 || GL * W == 16 || GL * W == 32, "store group: 16, 32, 64 or 128 bytes");
     static_assert(UNROLL % 4 == 0 && RPB % UNROLL == 0 && RPB * NP % 256 == 0, "slots and rows");
 
     __shared__ __attribute__((aligned(16))) float s_ct[RPB][NP];
@@ -859,10 +869,14 @@ void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, 
     // value of the tile has its sign bit set.  A ragged chunk keeps the compare form.
     float signs = 0.f;
 #pragma unroll
-    for (int tt = 0; tt < NP; ++tt)
-        asm("v_or3_b32 %0, %0, %1, %2\n\tv_or3_b32 %0, %0, %3, %4"
-            : "+v"(signs)
-            : "v"(L::get(p[tt], 0)), "v"(L::get(p[tt], 1)), "v"(L::get(p[tt], 2)), "v"(L::get(p[tt], 3)));
+    for (int tt = 0; tt < NP; ++tt) {
+        if constexpr (W == 4)
+            asm("v_or3_b32 %0, %0, %1, %2\n\tv_or3_b32 %0, %0, %3, %4"
+                : "+v"(signs)
+                : "v"(L::get(p[tt], 0)), "v"(L::get(p[tt], 1)), "v"(L::get(p[tt], 2)), "v"(L::get(p[tt], 3)));
+        else
+            asm("v_or3_b32 %0, %0, %1, %2" : "+v"(signs) : "v"(L::get(p[tt], 0)), "v"(L::get(p[tt], 1)));
+    }
 #pragma unroll
     for (int i = 0; i < RPB * NP; i += 64) {
         const float v = (&s_ct[0][0])[i + (int)__lane_id()];         // rows past r_cnt repeat the last row
@@ -871,7 +885,7 @@ void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, 
     const bool any = __builtin_amdgcn_ballot_w64(__builtin_signbit(signs)) != 0;
     const bool max_form = !fold_compare && !any && r_cnt % UNROLL == 0;
 
-    // One row through the 16 pivots, max form (relax_kt's relax_vec_max).  CD = r % 4: the one component of the row
+    // One row through the NP pivots, max form (relax_kt's relax_vec_max).  CD = r % W: the one component of the row
     // that can lie on the diagonal.
     auto vec_max = [&](const V &xv, int r, auto cd) {
         constexpr int CD = decltype(cd)::value;
@@ -911,18 +925,46 @@ void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, 
         float cik[NP];
 #pragma unroll
         for (int tt = 0; tt < NP; ++tt) cik[tt] = s_ct[r][tt];
-#pragma unroll
-        for (int tt = 0; tt < NP; ++tt) {
+        if constexpr (W == 2) {
+            // Two components are two compares: a select would follow the compare that feeds it at a distance of one
+            // instruction and get a wait state.  The next step's two multiplies, which do not depend on this step,
+            // stand between them instead.
             float cand[W];
-            bool up[W];
 #pragma unroll
-            for (int c = 0; c < W; ++c) {
-                cand[c] = cik[tt] * L::get(p[tt], c);
-                up[c] = L::get(nx, c) < cand[c];
+            for (int c = 0; c < W; ++c) cand[c] = cik[0] * L::get(p[0], c);
+#pragma unroll
+            for (int tt = 0; tt < NP; ++tt) {
+                float next[W];
+                bool up[W];
+#pragma unroll
+                for (int c = 0; c < W; ++c) up[c] = L::get(nx, c) < cand[c];
+                __builtin_amdgcn_sched_barrier(0);
+                if (tt + 1 < NP) {
+#pragma unroll
+                    for (int c = 0; c < W; ++c) next[c] = cik[tt + 1] * L::get(p[tt + 1], c);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int c = 0; c < W; ++c) L::set(nx, c, up[c] ? cand[c] : L::get(nx, c));
+                if (tt + 1 < NP) {
+#pragma unroll
+                    for (int c = 0; c < W; ++c) cand[c] = next[c];
+                }
             }
-            __builtin_amdgcn_sched_barrier(0);
+        } else {
 #pragma unroll
-            for (int c = 0; c < W; ++c) L::set(nx, c, up[c] ? cand[c] : L::get(nx, c));
+            for (int tt = 0; tt < NP; ++tt) {
+                float cand[W];
+                bool up[W];
+#pragma unroll
+                for (int c = 0; c < W; ++c) {
+                    cand[c] = cik[tt] * L::get(p[tt], c);
+                    up[c] = L::get(nx, c) < cand[c];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int c = 0; c < W; ++c) L::set(nx, c, up[c] ? cand[c] : L::get(nx, c));
+            }
         }
 #pragma unroll
         for (int c = 0; c < W; ++c) L::set(nx, c, c == d ? L::get(xv, c) : L::get(nx, c));
@@ -942,7 +984,7 @@ void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, 
                 for (; rb + UNROLL < r_cnt; rb += UNROLL) {
                     for_slots<UNROLL>([&](auto uc) {
                         constexpr int u = decltype(uc)::value;
-                        vec_max(x[u], rb + u, std::integral_constant<int, u % 4>());
+                        vec_max(x[u], rb + u, std::integral_constant<int, u % W>());
                         x[u] = load(at(base, rb + UNROLL + u));
                     });
                 }
@@ -957,7 +999,7 @@ void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, 
             for (; rb + UNROLL < r_cnt; rb += UNROLL) {
                 for_slots<UNROLL>([&](auto uc) {
                     constexpr int u = decltype(uc)::value;
-                    vec_max(x[u], rb + u, std::integral_constant<int, u % 4>());
+                    vec_max(x[u], rb + u, std::integral_constant<int, u % W>());
                 });
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) x[u] = ld(at(base, rb + UNROLL + u));
@@ -966,7 +1008,7 @@ void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, 
         // the last batch, peeled: no reload
         for_slots<UNROLL>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
-            vec_max(x[u], rb + u, std::integral_constant<int, u % 4>());
+            vec_max(x[u], rb + u, std::integral_constant<int, u % W>());
         });
         return;
     }
@@ -1630,15 +1672,17 @@ static hipError_t launch_relax_kt_cfg(const RelaxKtArgs<T> &a, hipStream_t s)
     return hipGetLastError();
 }
 
-// relax_walk with the geometry (RPB rows per workgroup, UNROLL slots), the policy POL and the walk ROLL: np == 16,
+// relax_walk with the geometry (RPB rows per workgroup, UNROLL slots), the policy POL and the walk ROLL: np == NP,
 // uncounted f32.  The tile order, the cache-policy split and the store group are chosen as launch_relax_kt_cfg chooses
 // them, in tiles of RPB rows.  ALLGL: every store group; otherwise the default one alone (tools/tune_relax.hip).
-template <int RPB, int UNROLL, int POL, bool ROLL, bool ALLGL = false>
+// NP = 32 (round 25): 8 bytes of a row per lane, strips of 512 columns, a store group of the same bytes is twice the
+// lanes.  The matrix keeps the 16-byte rules of every relax_kt launch (n a multiple of 4, 16-byte aligned).
+template <int RPB, int UNROLL, int POL, bool ROLL, bool ALLGL = false, int NP = 16>
 static hipError_t launch_relax_walk_cfg(const RelaxKtArgs<float> &a, hipStream_t s)
 {
-    constexpr int W = 4, SW = 256 * W;
+    constexpr int W = 64 / NP, SW = 256 * W, LG = 4 / W;      // LG: lanes per 16 bytes
     if (a.n <= 0) return hipSuccess;
-    if (a.n % W || (uintptr_t)a.rate % 16 || (uintptr_t)a.w % 16 || a.ct_ld < a.n || a.k < 0 || a.np != 16 ||
+    if (a.n % 4 || (uintptr_t)a.rate % 16 || (uintptr_t)a.w % 16 || a.ct_ld < a.n || a.k < 0 || a.np != NP ||
         a.k + a.np > a.n || a.updates)
         return hipErrorInvalidValue;
     const int nstrips = (a.n + SW - 1) / SW;
@@ -1657,8 +1701,8 @@ static hipError_t launch_relax_walk_cfg(const RelaxKtArgs<float> &a, hipStream_t
     const int sb = a.store_bytes > 0 ? a.store_bytes : FWX_PERK_STORE_BYTES_DEFAULT;
     const int gl = sb >= 128 ? 8 : sb >= 64 ? 4 : sb >= 32 ? 2 : 1;
 #define FWX_LAUNCH_WALK(GL)                                                                        \
-    hipLaunchKernelGGL((relax_walk<RPB, UNROLL, GL, POL, ROLL>), grid, block, 0, s, a.rate, a.w, a.ct, a.ct_ld, a.n, \
-                       a.k, nstrips, flip, nt_below, strip_magic, a.fold_compare ? 1 : 0)
+    hipLaunchKernelGGL((relax_walk<RPB, UNROLL, (GL) * LG, POL, ROLL, NP, W>), grid, block, 0, s, a.rate, a.w, a.ct,  \
+                       a.ct_ld, a.n, a.k, nstrips, flip, nt_below, strip_magic, a.fold_compare ? 1 : 0)
     note_form(KF_RELAX_K);
     if (gl == 4) FWX_LAUNCH_WALK(4);
     else if constexpr (ALLGL) {
@@ -1674,6 +1718,13 @@ static hipError_t launch_relax_walk_cfg(const RelaxKtArgs<float> &a, hipStream_t
 
 template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s)
 {
+    if (a.np == 32) {
+        if constexpr (std::is_same<T, float>::value) {
+            if (a.walk && !a.updates)
+                return launch_relax_walk_cfg<FWX_PERK_DEEP_RPB, FWX_PERK_DEEP_UNROLL, WALK_POL_PLAIN, false, true, 32>(a, s);
+        }
+        return hipErrorInvalidValue;
+    }
     if (a.np == 16) {
         if constexpr (std::is_same<T, float>::value) {
             if (a.walk && !a.updates)

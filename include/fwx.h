@@ -148,6 +148,13 @@ int fwx_test_perk_fold(void);
  * `0`, exactly), 1 = round 23's does (anything else, or unset).  Launches are counted by the two hooks above, the
  * same either way.  Needs no device.  Not for production use.                                        */
 int fwx_test_perk_walk(void);
+/* TEST HOOK for the deep pass of that schedule (FWX_PERK_DEEP): returns what the variable parses to right now: 0 = off
+ * (the value `0`, exactly: the ladder starts at 16, the schedule before the 32-pivot sweep launch for launch), 1 = on
+ * (anything else, or unset: where the ladder would start at 16 with the walk on, it starts at 32).  *deep_launches
+ * (if not NULL) receives the number of 32-pivot sweeps launched in this process -- each of them also counted as 4 by
+ * fwx_test_perk_pivots and as 2 by fwx_test_perk_wide -- which is cleared if reset.  Needs no device.  Not for
+ * production use.                                                                                        */
+int fwx_test_perk_deep(uint64_t *deep_launches, int reset);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).

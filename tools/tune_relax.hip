@@ -207,6 +207,8 @@ static int stores_sweep(float *d, int n, int per, int rounds)
 // their own, back to back on an otherwise idle chip, and reported separately).  NP = 16 (round 19): the 16-pivot
 // sweep of the non-counting f32 kernel in its candidate geometries, 64 / 16 sweeps per block.  An optional last
 // argument keeps only the variants with at least that many pivots per launch (`8`: the 8- and 16-wide ones).
+// NP = 32 (round 25): relax_walk with 8 bytes of a row per lane, 64 / 32 sweeps per block; a last table puts the 16-
+// and 32-pivot rows on one scale, us of sweep launches per 16 pivots.
 //   tune_relax 16384 0 256 3 pivots [min NP]
 struct KtCfg { const char *name; int np; hipError_t (*fn)(const fwx::RelaxKtArgs<float> &, hipStream_t); bool cmp = false; };
 template <int RPB, int UNROLL>
@@ -219,6 +221,13 @@ template <int RPB, int UNROLL, int POL, bool ROLL>
 static hipError_t run_walk(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
 {
     return fwx::launch_relax_walk_cfg<RPB, UNROLL, POL, ROLL>(a, s);
+}
+
+// round 25: relax_walk at 32 pivots per pass and 8 bytes of a row per lane, R rows per workgroup, U slots
+template <int RPB, int UNROLL, bool ROLL = false>
+static hipError_t run_deep(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
+{
+    return fwx::launch_relax_walk_cfg<RPB, UNROLL, fwx::WALK_POL_PLAIN, ROLL, false, 32>(a, s);
 }
 
 static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
@@ -251,8 +260,18 @@ static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
     FWX_TUNE_WALK(16, 4) FWX_TUNE_WALK(32, 4) FWX_TUNE_WALK(64, 4)
 #undef FWX_TUNE_WALK
     vars.push_back({"w32 U8 cmp", 16, run_walk<32, 8, fwx::WALK_POL_FENCE, true>, true});
+    // round 25, 32 pivots per pass: dR Us = R rows per workgroup, s slots, plain loads, batches (roll: the walk); 64 / 32
+    // sweeps per block
+    vars.push_back({"d32 U8", 32, run_deep<32, 8>});
+    vars.push_back({"d16 U8", 32, run_deep<16, 8>});
+    vars.push_back({"d32 U16", 32, run_deep<32, 16>});
+    vars.push_back({"d64 U8", 32, run_deep<64, 8>});
+    vars.push_back({"d128 U8", 32, run_deep<128, 8>});
+    vars.push_back({"d32 U8 roll", 32, run_deep<32, 8, true>});      // slots reloaded one by one behind their folds
+    vars.push_back({"d64 U8 roll", 32, run_deep<64, 8, true>});
+    vars.push_back({"d32 U8 cmp", 32, run_deep<32, 8>, true});
     const int k0s[3] = {0, 4096, 12000}, nw = 3, nv = (int)vars.size();
-    if (n % 64 || per % 16) { printf("pivots mode: n must be a multiple of 64 and per of 16\n"); return 1; }
+    if (n % 64 || per % 32) { printf("pivots mode: n must be a multiple of 64 and per of 32\n"); return 1; }
     const size_t bytes = (size_t)n * n * sizeof(float);
     float *snap[3], *work, *w, *ct;
     for (int i = 0; i < nw; ++i) CK(hipMalloc(&snap[i], bytes));
@@ -271,7 +290,7 @@ static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
     int sweeps = 0;
     // pivots [kb, ke) with variant v; returns the number of sweep launches.  Timing only: a 64-block is
     // rounded DOWN to whole groups of np pivots (production sends a ragged end down the powers of two), so
-    // the window starts and `per` must be multiples of 16 (the widest group) for the states to be the per-k states
+    // the window starts and `per` must be multiples of 32 (the widest group) for the states to be the per-k states
     auto run = [&](const KtCfg &v, int kb, int ke) {
         int launches = 0;
         if (v.np == 1) {
@@ -349,6 +368,20 @@ static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
             const float panels = vars[v].np == 1 ? 0.f : panel_us[i] * ((npv[x] + 63) / 64);
             printf("  %7.2f (%7.2f)  %7.1f         ", best[x] / npv[x], sum[x] / rounds / npv[x],
                    (best[x] - panels) / nl[x]);
+        }
+        printf("\n");
+    }
+    // round 25: the 16- and 32-pivot sweeps on one scale, us of sweep launches per 16 pivots (panels taken out)
+    printf("\nsweeps per 16 pivots, us (min over rounds)\n%-4s %-12s", "NP", "geometry");
+    for (int i = 0; i < nw; ++i) printf("  k=%-7d", k0s[i]);
+    printf("\n");
+    for (int v = 0; v < nv; ++v) {
+        if (vars[v].np < 16) continue;
+        printf("%-4d %-12s", vars[v].np, vars[v].name);
+        for (int i = 0; i < nw; ++i) {
+            const int x = v * nw + i;
+            if (!nl[x]) { printf("  %-9s", "-"); continue; }
+            printf("  %7.1f  ", (best[x] - panel_us[i] * ((npv[x] + 63) / 64)) / npv[x] * 16);
         }
         printf("\n");
     }
