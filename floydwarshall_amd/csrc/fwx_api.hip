@@ -1332,6 +1332,14 @@ int fwx_test_perk_deep(uint64_t *deep_launches, int reset)
     return perk_deep() ? 1 : 0;
 }
 
+int fwx_test_perk_tile(uint64_t *launches, int reset)
+{
+    const uint64_t v = reset ? g_perk_tile_launches.exchange(0, std::memory_order_relaxed)
+                             : g_perk_tile_launches.load(std::memory_order_relaxed);
+    if (launches) *launches = v;
+    return perk_tile_min_n();
+}
+
 int fwx_test_perk_wide(uint64_t *wide_launches, int reset)
 {
     const uint64_t v = reset ? g_perk_wide_launches.exchange(0, std::memory_order_relaxed)

@@ -1169,6 +1169,233 @@ __global__ __launch_bounds__(256, MINW) void fused_main_max(float *rate, int row
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// relax_tile (round 26): the per-k engine's sweep for a full 64-pivot block, fused_main_max's shape
+// (128 x 128 tile, 8 x 8 entries per thread, 16-pivot LDS stages, double-buffered) WITHOUT a verified
+// domain: fwx_dev_relax has no handle and no pre-pass, so each tile decides from what it loads.
+//
+// The result is the sequential strict fold  x <- (x < c*w) ? c*w : x  over t = 0 .. 63, bit for bit,
+// for every input:
+//   * a stage (16 pivots) is CLEAN if no staged W value (after the NaN patch of column k+t) and no
+//     staged Ct value of the tile has its sign bit set -- relax_kt's rule;
+//   * the tile's x is CLEAN if no loaded entry is NaN or has its sign bit set;
+//   * while x and every stage so far are clean, a stage folds as x <- max3(x, p, p').  Every candidate
+//     is then a product of sign-clear operands: >= +0, +inf or NaN; x is >= +0 and not NaN; max
+//     ignores a NaN candidate exactly as `x < NaN` is false, on equality both forms leave the same
+//     bits (no -0 is in play), and max is associative (fused_main_max's header) -- and x stays clean;
+//   * from the first stage that is not clean (from stage 0 if x is not clean, or if the caller forces
+//     it: RelaxKtArgs::fold_compare) the tile folds in the compare form, pivot after pivot in order,
+//     and stays there: once a compare-form stage has run, x may hold a negative value or a -0.
+// The vote: every thread ORs the bits of the operands it commits to LDS (x's class test joins stage
+// 0's), one ballot per wave, one LDS word per wave, read behind the barrier the stage already has.  The
+// words of stage s + 2 are written behind barrier s + 1, which every wave reaches after it has read
+// those of stage s: two sets suffice.  The branch is workgroup-uniform, once per stage.
+//
+// In place without a race: a tile reads only the two panels, which no tile writes, and its own
+// entries (the diagonal restore included), which no other tile touches.
+// ------------------------------------------------------------------------------------------------
+
+// One pivot pair of the compare-form fold on the register tile: pivot u = 0 on every entry, then u = 1
+// -- per entry the order of the sequential fold.  v_mul_f32 by hand for the reason given at max_fold_pair.
+template <int RI, int NH>
+__device__ __forceinline__ void cmp_fold_pair(const float (&sWp)[2][64 * NH], const float (&sCp)[2][16 * RI],
+                                              int ti, int tj, F32x4 (&x)[RI][NH])
+{
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        float c[RI], wv[NH][4];
+#pragma unroll
+        for (int q = 0; q < RI / 4; ++q) {
+            const F32x4 cv = *reinterpret_cast<const F32x4 *>(&sCp[u][ti * RI + q * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) c[q * 4 + e] = cv[e];
+        }
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            const F32x4 wq = *reinterpret_cast<const F32x4 *>(&sWp[u][h * 64 + tj * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) wv[h][e] = wq[e];
+        }
+#pragma unroll
+        for (int r = 0; r < RI; ++r)
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float p;
+                    asm("v_mul_f32 %0, %1, %2" : "=v"(p) : "v"(c[r]), "v"(wv[h][e]));
+                    x[r][h][e] = x[r][h][e] < p ? p : x[r][h][e];
+                }
+    }
+}
+
+// OR of the bit patterns of a staged vector: its sign bit is set iff one of the four has it set
+__device__ __forceinline__ int sign_bits(F32x4 v)
+{
+    typedef int I4 __attribute__((ext_vector_type(4)));
+    const I4 b = __builtin_bit_cast(I4, v);
+    return b[0] | b[1] | b[2] | b[3];
+}
+
+template <int MINW, int RI, int NH>
+__global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int k0, const float *w,
+                                                        const float *ct, int ct_ld, int force_cmp)
+{
+    typedef float V4 __attribute__((ext_vector_type(4)));
+    constexpr int TI = 16 * RI, TJ = 64 * NH, HJ = 64, BS = 16, HP = BS / 2, NS = B / BS;
+    static_assert(TI == 128 && TJ == 128, "every thread stages both operands: 8 pivot pairs x 32 vectors");
+
+    __shared__ __attribute__((aligned(16))) float sW[2][HP][2][TJ];
+    __shared__ __attribute__((aligned(16))) float sC[2][HP][2][TI];
+    __shared__ __attribute__((aligned(16))) int sVote[2][4];   // [stage parity][wave]: the wave staged a sign bit
+
+    const int tid = threadIdx.x;
+    const int i_base = blockIdx.y * TI;
+    const int j_base = blockIdx.x * TJ;
+    const int ti = tid >> 4, tj = tid & 15;
+    const int i0 = i_base + ti * RI;
+    const int sp = tid >> 5, sv = tid & 31;      // staging role: pivot pair sp, 4 columns / rows at sv * 4
+
+    auto voted = [&](int buf) -> bool {          // behind the stage's barrier; workgroup-uniform
+        typedef int I4 __attribute__((ext_vector_type(4)));
+        const I4 v = *reinterpret_cast<const I4 *>(&sVote[buf][0]);
+        return __builtin_amdgcn_readfirstlane(v[0] | v[1] | v[2] | v[3]) != 0;
+    };
+    // x's class test: sign clear and not NaN <=> the bits, as unsigned, are at most +inf's
+    auto x_bits = [&](const V4 (&x)[RI][NH]) -> int {
+        unsigned m = 0;
+#pragma unroll
+        for (int r = 0; r < RI; ++r)
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float f = x[r][h][e];  // by value: a bit cast of the vector ELEMENT reads element 0
+                    const unsigned b = __builtin_bit_cast(unsigned, f);
+                    m = b > m ? b : m;           // an UNSIGNED maximum: a set sign bit is the largest of all
+                }
+        return m > 0x7f800000u ? (int)0x80000000u : 0;
+    };
+    // Interior tiles (inside the matrix, off the diagonal, away from the pivot columns; workgroup-uniform) load and
+    // store the tile without clamps, predicates or a restore.  The stage loop between is ONE body for every tile: a
+    // second copy of the folds costs registers the tile does not have (see main_max_interior).
+    const bool interior = i_base + TI <= n && j_base + TJ <= n &&
+                          !(i_base < j_base + TJ && j_base < i_base + TI) &&   // off the diagonal
+                          (k0 + B <= j_base || k0 >= j_base + TJ);             // no pivot column
+
+    // Staging: addresses clamped into the panels, so every load is unconditional and nothing waits for it before
+    // commit(), which replaces what lies outside the matrix and the pivot's own column (skip j == k) by NaN.
+    const float nanv = qnan<float>();
+    const int sj = j_base + sv * 4, si = i_base + sv * 4;     // W columns, C rows; n % 4 == 0: whole vector in or out
+    const bool sj_ok = sj < n, si_ok = si < n;
+    const float *wp = w + (size_t)(2 * sp) * n + (sj_ok ? sj : 0);
+    const float *cp = ct + (size_t)(2 * sp) * ct_ld + (si_ok ? si : 0);
+    int kcol = k0 + 2 * sp - sj;                 // where pivot 2 * sp of the stage to commit lies in this thread's W vector
+    V4 pw[2], pc[2];
+    auto prefetch = [&]() {
+        pw[0] = *reinterpret_cast<const V4 *>(wp);
+        pw[1] = *reinterpret_cast<const V4 *>(wp + n);
+        pc[0] = *reinterpret_cast<const V4 *>(cp);
+        pc[1] = *reinterpret_cast<const V4 *>(cp + ct_ld);
+        wp += (size_t)BS * n;
+        cp += (size_t)BS * ct_ld;
+    };
+    auto commit = [&](int buf, int extra) {      // the vote sees the operands as the folds will
+        int bits = extra;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            V4 a = pw[u], c = pc[u];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                a[e] = (!sj_ok || kcol + u == e) ? nanv : a[e];
+                c[e] = si_ok ? c[e] : nanv;
+            }
+            *reinterpret_cast<V4 *>(&sW[buf][sp][u][sv * 4]) = a;
+            *reinterpret_cast<V4 *>(&sC[buf][sp][u][sv * 4]) = c;
+            bits |= sign_bits(a) | sign_bits(c);
+        }
+        kcol += BS;
+        // every lane of the wave stores the same word: no divergent branch in the stage loop, which the compiler
+        // would answer by keeping two copies of the tile across the two folds
+        sVote[buf][tid >> 6] = __builtin_amdgcn_ballot_w64(bits < 0) != 0 ? 1 : 0;
+    };
+
+    prefetch();
+    V4 x[RI][NH];
+    if (interior) {
+        const float *xp = rate + (size_t)i0 * n + j_base + tj * 4;
+#pragma unroll
+        for (int r = 0; r < RI; ++r)
+#pragma unroll
+            for (int h = 0; h < NH; ++h) x[r][h] = *reinterpret_cast<const V4 *>(xp + (size_t)r * n + h * HJ);
+    } else {
+#pragma unroll
+        for (int r = 0; r < RI; ++r) {
+            const int i = min(i0 + r, n - 1);
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                const int j = j_base + h * HJ + tj * 4;
+                x[r][h] = *reinterpret_cast<const V4 *>(rate + (size_t)i * n + (j < n ? j : n - 4));
+            }
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(FWX_WAIT_VMCNT0);   // the tile is complete here, once (see fused_main_max)
+    commit(0, x_bits(x));                          // clamped duplicates vote too: on the safe side
+    __syncthreads();
+
+    bool cmp = force_cmp != 0;                     // the compare form has begun (it persists)
+    int buf = 0;
+#pragma unroll 1
+    for (int s = 0; s < NS; ++s, buf ^= 1) {
+        const bool more = s + 1 < NS;              // workgroup-uniform
+        cmp |= voted(buf);
+        if (more) prefetch();                      // in flight during the fold below
+        // two loops one behind the other, one of them empty: an if / else of the two forms makes the compiler keep
+        // the tile twice (the entry state stays live beside the branch not taken) and spill
+        const int nmax = cmp ? 0 : HP;
+#pragma unroll 1
+        for (int tp = 0; tp < nmax; ++tp) max_fold_pair<RI, NH>(sW[buf][tp], sC[buf][tp], ti, tj, x);
+#pragma unroll 1
+        for (int tp = nmax; tp < HP; ++tp) cmp_fold_pair<RI, NH>(sW[buf][tp], sC[buf][tp], ti, tj, x);
+        if (more) {
+            commit(buf ^ 1, 0);                    // the other buffer: nobody reads it now
+            __syncthreads();
+        }
+    }
+
+    if (interior) {
+        float *xp = rate + (size_t)i0 * n + j_base + tj * 4;
+#pragma unroll
+        for (int r = 0; r < RI; ++r)
+#pragma unroll
+            for (int h = 0; h < NH; ++h) *reinterpret_cast<V4 *>(xp + (size_t)r * n + h * HJ) = x[r][h];
+        return;
+    }
+    if (i_base < j_base + TJ && j_base < i_base + TI) {   // the diagonal entries keep their value: restored once
+#pragma unroll
+        for (int r = 0; r < RI; ++r) {
+            const int i = i0 + r;
+            if (i >= n) continue;
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                const int j = j_base + h * HJ + tj * 4;
+                if (i >= j && i < j + 4) x[r][h][i - j] = rate[(size_t)i * n + i];
+            }
+        }
+        __builtin_amdgcn_s_waitcnt(FWX_WAIT_VMCNT0);
+    }
+#pragma unroll
+    for (int r = 0; r < RI; ++r) {
+        const int i = i0 + r;
+        if (i >= n) continue;
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            const int j = j_base + h * HJ + tj * 4;
+            if (j < n) *reinterpret_cast<V4 *>(rate + (size_t)i * n + j) = x[r][h];
+        }
+    }
+}
+
 typedef double F64x2 __attribute__((ext_vector_type(2)));
 
 // One pivot of the f64 max-form fold on a thread's 8 x (4 x 2) register tile: the 8 products of a
@@ -2671,6 +2898,22 @@ hipError_t launch_fused_panels(const FusedArgs<T> &a, T *w_out, int32_t *wh_out,
 }
 template hipError_t launch_fused_panels<float>(const FusedArgs<float> &, float *, int32_t *, hipStream_t);
 template hipError_t launch_fused_panels<double>(const FusedArgs<double> &, double *, int32_t *, hipStream_t);
+
+// The per-k engine's tile sweep (relax_tile): pivots [a.k, a.k + 64) on the whole matrix in place, one launch.
+// a.flip, a.temporal_bytes, a.store_bytes and a.walk are not read: a tile is loaded once and stored once whatever
+// the order of the tiles, and no result bit depends on them.
+hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s)
+{
+    if (a.n <= 0) return hipSuccess;
+    if (a.np != B || a.n < B || a.n % 4 || a.ct_ld % 4 || a.ct_ld < a.n || (uintptr_t)a.rate % 16 || (uintptr_t)a.w % 16 ||
+        (uintptr_t)a.ct % 16 || a.k < 0 || a.k + a.np > a.n || a.updates)
+        return hipErrorInvalidValue;
+    const unsigned tiles = (unsigned)((a.n + 127) / 128);
+    note_form(KF_RELAX_K);
+    hipLaunchKernelGGL((relax_tile<3, 8, 2>), dim3(tiles, tiles), dim3(256), 0, s, a.rate, a.n, a.k, a.w, a.ct,
+                       a.ct_ld, a.fold_compare ? 1 : 0);
+    return hipGetLastError();
+}
 
 template hipError_t launch_fused_relax<float>(const FusedArgs<float> &, hipStream_t, int, int);
 template hipError_t launch_fused_relax<double>(const FusedArgs<double> &, hipStream_t, int, int);

@@ -10,6 +10,7 @@
 #include <type_traits>
 #include <vector>
 #include <errno.h>
+#include <limits.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <stdint.h>
@@ -520,6 +521,27 @@ inline bool perk_deep()
     return !(e && !strcmp(e, "0"));
 }
 
+// The tile sweep (round 26): where the deep pass would issue two 32-pivot sweeps for a FULL 64-pivot block, a matrix
+// of order n >= FWX_PERK_TILE_MIN_N takes one relax_tile launch (fwx_fused.hip: the block's 64 pivots in one pass on
+// register tiles).  Digits only, read on every call: 0 = never, otherwise the smallest order that takes it; any
+// other text means the default.  Ragged blocks, counted calls, f64 and every switch above at `0` keep the ladder.  The
+// three older hooks' counters read the same either way (a tile launch is eight 8-pivot groups, four wide ones and
+// two deep ones); the tile launches themselves are g_perk_tile_launches.  For tests and A/B runs in one binary, and
+// the remedy for inputs whose operands carry sign bits everywhere.  No result bit
+// depends on it.
+#define FWX_PERK_TILE_MIN_N_DEFAULT 1024
+inline int perk_tile_min_n()
+{
+    if (const char *e = getenv("FWX_PERK_TILE_MIN_N")) {
+        char *end = nullptr;
+        errno = 0;
+        const long v = strtol(e, &end, 10);
+        // digits only: no sign, no blank
+        if (*e >= '0' && *e <= '9' && *end == '\0' && errno == 0 && v >= 0 && v <= INT_MAX) return (int)v;
+    }
+    return FWX_PERK_TILE_MIN_N_DEFAULT;
+}
+
 // The fold of relax_kt's non-counting f32 sweeps: FWX_PERK_FOLD=compare forces the compare form in every tile, read on
 // every call; anything else, or unset: automatic (each wave takes the max form where the operands it has loaded
 // are all NaN or sign-clear).  For tests and A/B runs in one binary.  No result bit depends on it (DESIGN.md
@@ -608,6 +630,9 @@ inline std::atomic<uint64_t> g_perk_launches[5];
 // g_perk_deep_launches (fwx_test_perk_deep).
 inline std::atomic<uint64_t> g_perk_wide_launches;
 inline std::atomic<uint64_t> g_perk_deep_launches;
+// A tile sweep (round 26) applies a whole 64-pivot block: 8 to [3], 4 to g_perk_wide_launches, 2 to g_perk_deep_launches,
+// for the same reason, and 1 to g_perk_tile_launches (fwx_test_perk_tile).
+inline std::atomic<uint64_t> g_perk_tile_launches;
 
 // Snapshot panels (W and Ct of one 64-pivot block) of the multi-pivot schedule: perk_kt_ws_bytes.  A blocking
 // entry point that holds a per-call context passes that context's workspace.  fwx_dev_relax* has no workspace
@@ -680,6 +705,8 @@ private:
 // An uncounted f32 call at np == 8 starts the ladder at 16 (perk_wide): the panels hold the snapshots of all 64
 // pivots of the block, so the second 8-pivot sweep of a pair need not re-read the matrix; with the walk on as well it
 // starts at 32 (perk_deep), one streaming pass per half block.
+// A FULL block of such a call at n >= perk_tile_min_n() takes one relax_tile launch instead of the two 32-pivot sweeps
+// (round 26): the block's 64 pivots in one pass on register tiles, the operands through LDS.
 template <typename T>
 inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine, int np,
                           unsigned long long *d_updates, hipStream_t s, void *ws)
@@ -711,17 +738,29 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
         FWX_HIP(e);
         g_perk_launches[slot].fetch_add((uint64_t)groups, std::memory_order_relaxed);
         if (groups >= 2) g_perk_wide_launches.fetch_add((uint64_t)groups / 2, std::memory_order_relaxed);
-        if (groups == 4) g_perk_deep_launches.fetch_add(1, std::memory_order_relaxed);
+        if (groups >= 4) g_perk_deep_launches.fetch_add((uint64_t)groups / 4, std::memory_order_relaxed);
+        if (groups == 8) g_perk_tile_launches.fetch_add(1, std::memory_order_relaxed);
         return thr.tick(s);
     };
     const bool wide = np == 8 && !d_updates && std::is_same<T, float>::value && perk_wide();
     const int g_top = wide ? (a.walk && perk_deep() ? 32 : 16) : np;
+    // a full block where the ladder would start at 32: one tile sweep (round 26) instead of the two 32-pivot sweeps
+    const int tile_min_n = perk_tile_min_n();
+    const bool tile = g_top == 32 && tile_min_n > 0 && n >= tile_min_n && n >= FWX_FUSED_B;
     for (int k0 = k_begin; k0 < k_end; k0 += FWX_FUSED_B) {
         const int bt = std::min(FWX_FUSED_B, k_end - k0);
         int t = 0;
         if (bt >= 2) {
             pa.k0 = k0; pa.bt = bt;
             if (const int rc = after(fwx::launch_fused_panels<T>(pa, w, nullptr, s), 4)) return rc;
+            if constexpr (std::is_same<T, float>::value) {
+                if (tile && bt == FWX_FUSED_B) {
+                    a.k = k0; a.np = bt; a.w = w; a.ct = ct;
+                    a.flip = 0;                    // not read: a tile is loaded and stored once, in any order
+                    if (const int rc = after(fwx::launch_relax_tile(a, s), 3, 8)) return rc;
+                    t = bt;
+                }
+            }
             for (int g = g_top; g >= 2; g >>= 1)
                 for (; bt - t >= g; t += g) {
                     a.k = k0 + t; a.np = g; a.w = w + (size_t)t * n; a.ct = ct + (size_t)t * ld;

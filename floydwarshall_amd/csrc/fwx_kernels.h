@@ -138,6 +138,11 @@ template <typename T> struct RelaxKtArgs {
     unsigned long long *updates = nullptr;   // FWX_UPDATE_SHARDS_K counters or nullptr
 };
 template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s);
+// relax_tile (round 26, fwx_fused.hip): pivots [k, k+64) in ONE pass on 128 x 128 register tiles, operands from LDS;
+// np == 64, f32, updates == nullptr, n >= 64.  The fold is chosen per tile and stage (max form where the tile's
+// entries and operands allow it; fold_compare forces the compare form).  flip, temporal_bytes, store_bytes and walk
+// are not read: no result bit depends on them.
+hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s);
 
 // Whole solve (pivots [k_begin,k_end)) of an n <= FWX_SMALL_N matrix in one single-workgroup launch.
 #define FWX_SMALL_N 128

@@ -155,6 +155,13 @@ int fwx_test_perk_walk(void);
  * fwx_test_perk_pivots and as 2 by fwx_test_perk_wide -- which is cleared if reset.  Needs no device.  Not for
  * production use.                                                                                        */
 int fwx_test_perk_deep(uint64_t *deep_launches, int reset);
+/* TEST HOOK for the tile sweep of that schedule (FWX_PERK_TILE_MIN_N): returns what the variable parses to right now:
+ * 0 = never, otherwise the smallest order n whose full 64-pivot blocks take ONE tile sweep where the deep pass would
+ * issue two 32-pivot sweeps (digits only; any other text, or unset: the default).  *launches (if not NULL) receives
+ * the number of tile sweeps launched in this process -- each of them also counted as 8 by fwx_test_perk_pivots, as 4
+ * by fwx_test_perk_wide and as 2 by fwx_test_perk_deep -- which is cleared if reset.  Needs no device.  Not for
+ * production use.                                                                                        */
+int fwx_test_perk_tile(uint64_t *launches, int reset);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).

@@ -1,0 +1,77 @@
+"""FWX_PERK_TILE_MIN_N (the smallest order whose full 64-pivot blocks take one tile sweep of the per-k engine where the
+deep pass issues two 32-pivot sweeps) is read on every call: digits only; `0` means never; any other text, or unset,
+means the default.  CPU only: the hook needs no device."""
+import ctypes
+
+import pytest
+
+from floydwarshall_amd import _lib
+
+
+def _parsed():
+    return _lib.lib().fwx_test_perk_tile(None, 0)
+
+
+def _default(monkeypatch):
+    monkeypatch.delenv("FWX_PERK_TILE_MIN_N", raising=False)
+    return _parsed()
+
+
+def test_unset_is_the_default(monkeypatch):
+    d = _default(monkeypatch)
+    assert d == 0 or d >= 64          # never, or an order the kernel takes
+
+
+def test_zero_is_never(monkeypatch):
+    monkeypatch.setenv("FWX_PERK_TILE_MIN_N", "0")
+    assert _parsed() == 0
+
+
+@pytest.mark.parametrize("value,want", [("1", 1), ("64", 64), ("1024", 1024), ("16384", 16384), ("007", 7),
+                                        ("2147483647", 2147483647)])
+def test_a_number_is_itself(value, want, monkeypatch):
+    monkeypatch.setenv("FWX_PERK_TILE_MIN_N", value)
+    assert _parsed() == want
+
+
+@pytest.mark.parametrize("value", ["", " ", "-1", "+64", "-0", " 64", "64 ", "64k", "0x40", "6.4e1", "64.0", "off", "never",
+                                   "2147483648", "99999999999999999999"])
+def test_sign_blank_or_trailing_text_is_the_default(value, monkeypatch):
+    d = _default(monkeypatch)
+    monkeypatch.setenv("FWX_PERK_TILE_MIN_N", value)
+    assert _parsed() == d
+
+
+def test_read_on_every_call(monkeypatch):
+    d = _default(monkeypatch)
+    for value, want in (("0", 0), ("128", 128), ("junk", d), ("0", 0), ("4096", 4096)):
+        monkeypatch.setenv("FWX_PERK_TILE_MIN_N", value)
+        assert _parsed() == want
+    monkeypatch.delenv("FWX_PERK_TILE_MIN_N")
+    assert _parsed() == d
+
+
+def test_the_counter_needs_no_device_and_resets():
+    c = ctypes.c_uint64(7)
+    _lib.lib().fwx_test_perk_tile(ctypes.byref(c), 1)
+    _lib.lib().fwx_test_perk_tile(ctypes.byref(c), 0)
+    assert c.value == 0
+
+
+def test_it_leaves_the_other_knobs_alone(monkeypatch):
+    """The tile sweep is a choice of schedule: FWX_PERK_DEEP, FWX_PERK_WIDE, FWX_PERK_WALK, FWX_PERK_FOLD and
+    FWX_PERK_PIVOTS keep their parse beside it, and it keeps its own beside theirs."""
+    monkeypatch.setenv("FWX_PERK_TILE_MIN_N", "0")
+    for v in ("FWX_PERK_DEEP", "FWX_PERK_WIDE", "FWX_PERK_WALK", "FWX_PERK_FOLD", "FWX_PERK_PIVOTS"):
+        monkeypatch.delenv(v, raising=False)
+    L = _lib.lib()
+    assert (L.fwx_test_perk_deep(None, 0), L.fwx_test_perk_wide(None, 0), L.fwx_test_perk_walk(), L.fwx_test_perk_fold(),
+            L.fwx_test_perk_pivots(None, 0)) == (1, 1, 1, 0, 8)
+    monkeypatch.setenv("FWX_PERK_DEEP", "0")
+    monkeypatch.setenv("FWX_PERK_WIDE", "0")
+    monkeypatch.setenv("FWX_PERK_WALK", "0")
+    monkeypatch.setenv("FWX_PERK_FOLD", "compare")
+    monkeypatch.setenv("FWX_PERK_PIVOTS", "4")
+    monkeypatch.setenv("FWX_PERK_TILE_MIN_N", "512")
+    assert (L.fwx_test_perk_deep(None, 0), L.fwx_test_perk_wide(None, 0), L.fwx_test_perk_walk(), L.fwx_test_perk_fold(),
+            L.fwx_test_perk_pivots(None, 0), _parsed()) == (0, 0, 0, 1, 4, 512)

@@ -209,6 +209,8 @@ static int stores_sweep(float *d, int n, int per, int rounds)
 // argument keeps only the variants with at least that many pivots per launch (`8`: the 8- and 16-wide ones).
 // NP = 32 (round 25): relax_walk with 8 bytes of a row per lane, 64 / 32 sweeps per block; a last table puts the 16-
 // and 32-pivot rows on one scale, us of sweep launches per 16 pivots.
+// NP = 64 (round 26): relax_tile, one sweep per block (`tile`; `tile cmp`: the compare form forced in every tile); a last
+// table gives the 32- and 64-pivot rows per whole block, us per 64 pivots with the panel launch.
 //   tune_relax 16384 0 256 3 pivots [min NP]
 struct KtCfg { const char *name; int np; hipError_t (*fn)(const fwx::RelaxKtArgs<float> &, hipStream_t); bool cmp = false; };
 template <int RPB, int UNROLL>
@@ -229,6 +231,9 @@ static hipError_t run_deep(const fwx::RelaxKtArgs<float> &a, hipStream_t s)
 {
     return fwx::launch_relax_walk_cfg<RPB, UNROLL, fwx::WALK_POL_PLAIN, ROLL, false, 32>(a, s);
 }
+
+// round 26: relax_tile, the block's 64 pivots in one pass on register tiles
+static hipError_t run_tile(const fwx::RelaxKtArgs<float> &a, hipStream_t s) { return fwx::launch_relax_tile(a, s); }
 
 static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
 {
@@ -270,8 +275,18 @@ static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
     vars.push_back({"d32 U8 roll", 32, run_deep<32, 8, true>});      // slots reloaded one by one behind their folds
     vars.push_back({"d64 U8 roll", 32, run_deep<64, 8, true>});
     vars.push_back({"d32 U8 cmp", 32, run_deep<32, 8>, true});
+    vars.push_back({"d64 U8 cmp", 32, run_deep<64, 8>, true});        // the production pair on an input that votes for the compare
+    // round 26, 64 pivots per pass: relax_tile (fwx_fused.hip), one sweep per block; cmp: the compare form forced in
+    // every tile, what an input with sign bits in every tile pays
+    vars.push_back({"tile", 64, run_tile});
+    vars.push_back({"tile cmp", 64, run_tile, true});
+    if (min_np > 1) {
+        std::vector<KtCfg> keep;
+        for (const KtCfg &v : vars) if (v.np >= min_np) keep.push_back(v);
+        vars.swap(keep);
+    }
     const int k0s[3] = {0, 4096, 12000}, nw = 3, nv = (int)vars.size();
-    if (n % 64 || per % 32) { printf("pivots mode: n must be a multiple of 64 and per of 32\n"); return 1; }
+    if (n % 64 || per % 64) { printf("pivots mode: n and per must be multiples of 64\n"); return 1; }
     const size_t bytes = (size_t)n * n * sizeof(float);
     float *snap[3], *work, *w, *ct;
     for (int i = 0; i < nw; ++i) CK(hipMalloc(&snap[i], bytes));
@@ -290,7 +305,7 @@ static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
     int sweeps = 0;
     // pivots [kb, ke) with variant v; returns the number of sweep launches.  Timing only: a 64-block is
     // rounded DOWN to whole groups of np pivots (production sends a ragged end down the powers of two), so
-    // the window starts and `per` must be multiples of 32 (the widest group) for the states to be the per-k states
+    // the window starts and `per` must be multiples of 64 (the widest group) for the states to be the per-k states
     auto run = [&](const KtCfg &v, int kb, int ke) {
         int launches = 0;
         if (v.np == 1) {
@@ -385,6 +400,68 @@ static int pivots_sweep(float *d, int n, int per, int rounds, int min_np)
         }
         printf("\n");
     }
+    // round 26: the 32- and 64-pivot sweeps per whole block, us per 64 pivots, the panel launch included
+    printf("\nper 64 pivots with the panel launch, us (min over rounds)\n%-4s %-12s", "NP", "geometry");
+    for (int i = 0; i < nw; ++i) printf("  k=%-7d", k0s[i]);
+    printf("\n");
+    for (int v = 0; v < nv; ++v) {
+        if (vars[v].np < 32) continue;
+        printf("%-4d %-12s", vars[v].np, vars[v].name);
+        for (int i = 0; i < nw; ++i) {
+            const int x = v * nw + i;
+            if (!nl[x]) { printf("  %-9s", "-"); continue; }
+            printf("  %7.1f  ", best[x] / npv[x] * 64);
+        }
+        printf("\n");
+    }
+    return 0;
+}
+
+// `crossover` mode (round 26): the default of FWX_PERK_TILE_MIN_N.  For every order m = 1024, 2048, ... up to n the
+// first `per` pivots (at most m) of an m x m matrix, as production issues them: per 64 pivots one panel launch, then
+// the two 32-pivot relax_walk sweeps of the deep pass, or one relax_tile sweep.  us per 64 pivots, min over rounds.
+//   tune_relax 16384 0 256 5 crossover
+static int tile_crossover(float *d, int n, int per, int rounds)
+{
+    float *work, *w, *ct;
+    CK(hipMalloc(&work, (size_t)n * n * sizeof(float)));
+    CK(hipMalloc(&w, (size_t)64 * n * sizeof(float)));
+    CK(hipMalloc(&ct, (size_t)64 * n * sizeof(float)));
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    printf("crossover per=%d rounds=%d  (us per 64 pivots with the panel launch, min over rounds)\n", per, rounds);
+    printf("%-8s %-14s %-14s %s\n", "n", "2 x walk 32", "tile", "tile / pair");
+    for (int m = 1024; m <= n; m *= 2) {
+        const size_t bytes = (size_t)m * m * sizeof(float);
+        const int ke = std::min(m, per) / 64 * 64;
+        hipLaunchKernelGGL(fill_uniform, dim3(4096), dim3(256), 0, 0, d, (size_t)m * m, m, 12345u);
+        fwx::FusedArgs<float> pa;
+        pa.rate = work; pa.next = nullptr; pa.rows = m; pa.n = m; pa.row0 = 0; pa.w = nullptr; pa.ct = ct;
+        pa.cnt = nullptr; pa.ct_ld = m; pa.updates = nullptr; pa.nonneg = false;
+        fwx::RelaxKtArgs<float> a;
+        a.rate = work; a.ct_ld = m; a.n = m; a.temporal_bytes = 256ll << 20; a.walk = true;
+        float best[2] = {1e30f, 1e30f};
+        for (int r = 0; r < rounds; ++r)
+            for (int v = 0; v < 2; ++v) {
+                CK(hipMemcpyAsync(work, d, bytes, hipMemcpyDeviceToDevice, 0));
+                CK(hipEventRecord(e0, 0));
+                for (int k0 = 0, sweeps = 0; k0 < ke; k0 += 64) {
+                    pa.k0 = k0; pa.bt = 64;
+                    CK(fwx::launch_fused_panels<float>(pa, w, nullptr, 0));
+                    const int np = v ? 64 : 32;
+                    for (int t = 0; t < 64; t += np) {
+                        a.k = k0 + t; a.np = np; a.w = w + (size_t)t * m; a.ct = ct + (size_t)t * m;
+                        a.flip = 2 * (sweeps++ & 1);
+                        CK(v ? fwx::launch_relax_tile(a, 0) : fwx::launch_relax_kt<float>(a, 0));
+                    }
+                }
+                CK(hipEventRecord(e1, 0));
+                CK(hipEventSynchronize(e1));
+                float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                best[v] = std::min(best[v], 1e3f * ms / (ke / 64));
+            }
+        printf("%-8d %-14.1f %-14.1f %.3f\n", m, best[0], best[1], best[1] / best[0]);
+    }
     return 0;
 }
 
@@ -450,6 +527,7 @@ int main(int argc, char **argv)
 
     if (argc > 5 && !strcmp(argv[5], "policy")) return policy_sweep(d, n, warm, per, rounds);
     if (argc > 5 && !strcmp(argv[5], "stores")) return stores_sweep(d, n, per, rounds);
+    if (argc > 5 && !strcmp(argv[5], "crossover")) return tile_crossover(d, n, per, rounds);
     if (argc > 5 && !strcmp(argv[5], "pivots")) return pivots_sweep(d, n, per, rounds, argc > 6 ? atoi(argv[6]) : 1);
 
     if (argc > 5 && !strcmp(argv[5], "fused")) {
