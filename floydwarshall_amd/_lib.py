@@ -145,6 +145,14 @@ SIGNATURES = {
                                                      c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
     "fwx_solve_batch_mid_lists_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                                      c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
+    "fwx_dev_solve_batch_large_traced": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64,
+                                                        ctypes.POINTER(FwxTrace), c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "fwx_dev_exact_paths_batch_large": (ctypes.c_int, [c_i32, c_i32, ctypes.c_int64, c_vp, ctypes.POINTER(FwxTrace),
+                                                       c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "fwx_solve_batch_large_lists_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                       c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
+    "fwx_solve_batch_large_lists_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                       c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
     "fwx_ragged_plan": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp]),
     "fwx_solve_ragged_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
     "fwx_solve_ragged_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),

@@ -522,14 +522,15 @@ int dev_solve_batch(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *h
 
 // The large tier (fwx_solve_batch_large_*, fwx_dev_solve_batch_large) for a call already routed to it (n >=
 // FWX_BATCH_LARGE_MIN_N; below it the callers take dev_solve_batch with mid set): groups of as many matrices as the
-// scratch holds, one after the other on s.
+// scratch holds, one after the other on s.  plog: the path trace (fwx_dev_solve_batch_large_traced and
+// fwx_solve_batch_large_lists_*), whole pivot range only.
 template <typename T>
 int dev_solve_batch_large(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, int64_t stride,
                           int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, void *scratch,
-                          size_t scratch_bytes, hipStream_t s)
+                          size_t scratch_bytes, hipStream_t s, const fwx::PathLog &plog = fwx::PathLog())
 {
     const hipError_t e = fwx::launch_batch_large<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
-                                                    d_updates_each, scratch, scratch_bytes, s);
+                                                    d_updates_each, scratch, scratch_bytes, s, plog);
     if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
     FWX_HIP(e);
     return FWX_OK;
@@ -630,9 +631,11 @@ struct BatchLists {
 // ragged && mid (fwx_solve_ragged_mid_*, fwx_solve_ragged_mid_lists_*): the ragged batch with the limit at
 // FWX_BATCH_MID_MAX_N and the four-tier plan (FWX_BATCH_MID_MIN_N read here, by the plan); the workspace layout and
 // the walk are the ragged ones.
-// large (fwx_solve_batch_large_*; with mid, without ls or ragged): the limit on n is FWX_BATCH_LARGE_MAX_N; orders
+// large (fwx_solve_batch_large_*; with mid, without ragged): the limit on n is FWX_BATCH_LARGE_MAX_N; orders
 // from FWX_BATCH_LARGE_MIN_N up run the large tier, whose scratch panels -- at most kBatchLargeScratchCap, larger
-// batches run in groups -- are the context's SMALL buffer; smaller orders are the mid call.
+// batches run in groups -- are the context's SMALL buffer; smaller orders are the mid call.  With ls
+// (fwx_solve_batch_large_lists_*) ONE reservation of that buffer holds both: the scratch panels first (the buffer's
+// own alignment, and every matrix's part a multiple of 16 bytes), then the lists' memory as above.
 constexpr size_t kBatchLargeScratchCap = (size_t)256 << 20;
 template <typename T>
 int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
@@ -734,12 +737,19 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     int32_t *d_next0 = nullptr, *d_walk = nullptr;
     const long long chunk = ls ? std::min<long long>(batch_lists_chunk(n, ls->cap), ls->items) : 0;
     const size_t stack_ints = FWX_EXACT_SCRATCH_INTS((size_t)n);
+    // the large tier's scratch panels: none for an empty pivot range (with ls the range is whole)
+    const size_t per_large = FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n);
+    const size_t b_scratch = to_large && op.k_end > op.k_begin
+        ? per_large * std::min<size_t>((size_t)count, std::max<size_t>(1, kBatchLargeScratchCap / per_large)) : 0;
+    static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1) % 16 == 0, "what follows the scratch panels stays 16-byte aligned");
+    void *d_scratch = nullptr;
     if (ls) {
         void *p = nullptr;
         const size_t walk_ints = (size_t)chunk * (4 + (size_t)ls->cap + stack_ints);
         fail_point();
-        if ((rc = cx.reserve(CallCtx::SMALL, (4 * cells + walk_ints) * sizeof(int32_t), &p))) return rc;
-        d_next0 = (int32_t *)p;
+        if ((rc = cx.reserve(CallCtx::SMALL, b_scratch + (4 * cells + walk_ints) * sizeof(int32_t), &p))) return rc;
+        if (b_scratch) d_scratch = p;
+        d_next0 = (int32_t *)((char *)p + b_scratch);
         plog.last = d_next0 + cells;
         plog.at_col = plog.last + cells;
         plog.at_row = plog.at_col + cells;
@@ -748,13 +758,12 @@ int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *
     }
 
     if (to_large) {
-        void *scratch = nullptr;
-        const size_t per = FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n);
-        const size_t b_scratch = per * std::min<size_t>((size_t)count, std::max<size_t>(1, kBatchLargeScratchCap / per));
-        fail_point();
-        if (op.k_end > op.k_begin && (rc = cx.reserve(CallCtx::SMALL, b_scratch, &scratch))) return rc;
+        if (!ls) {
+            fail_point();
+            if (b_scratch && (rc = cx.reserve(CallCtx::SMALL, b_scratch, &d_scratch))) return rc;
+        }
         rc = dev_solve_batch_large<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
-                                      op.k_begin, op.k_end, (unsigned long long *)d_upd, scratch, b_scratch, s);
+                                      op.k_begin, op.k_end, (unsigned long long *)d_upd, d_scratch, b_scratch, s, plog);
     } else if (ragged && mid)
         rc = dev_solve_ragged_mid<T>(count, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, d_n_each, d_offset,
                                      d_order, tiers, (unsigned long long *)d_upd, s, plog);
@@ -922,6 +931,8 @@ __host__ __device__ constexpr size_t exact_stack_triples(int n_real) { return (s
 static_assert(FWX_EXACT_SCRATCH_INTS(128) == 3 * exact_stack_triples(128), "fwx.h states the walk's scratch per item");
 static_assert(FWX_EXACT_SCRATCH_INTS(FWX_BATCH_MID_MAX_N) == 3 * exact_stack_triples(FWX_BATCH_MID_MAX_N),
               "... at the mid tier's largest order too (fwx_dev_exact_paths_batch_mid)");
+static_assert(FWX_EXACT_SCRATCH_INTS(FWX_BATCH_LARGE_MAX_N) == 3 * exact_stack_triples(FWX_BATCH_LARGE_MAX_N),
+              "... and at the large tier's (fwx_dev_exact_paths_batch_large)");
 
 template <typename Tab>
 __device__ int exact_walk(const Tab &t, int n_real, int src, int dst, int32_t *out, int32_t *stack, int cap)
@@ -1529,11 +1540,14 @@ int fwx_test_batch_large_geometry(int32_t out[4])
     return FWX_OK;
 }
 
-// fwx_dev_solve_batch_traced (max_n = FWX_BATCH_MAX_N) and fwx_dev_solve_batch_mid_traced (FWX_BATCH_MID_MAX_N, mid):
-// one contract, the limit apart.
+// fwx_dev_solve_batch_traced (max_n = FWX_BATCH_MAX_N), fwx_dev_solve_batch_mid_traced (FWX_BATCH_MID_MAX_N, mid) and
+// fwx_dev_solve_batch_large_traced (FWX_BATCH_LARGE_MAX_N, mid and large): one contract, the limit apart.  large: orders
+// from FWX_BATCH_LARGE_MIN_N up run the large tier on `scratch`, which is judged there and only there, as
+// fwx_dev_solve_batch_large judges it (the range is whole, so never empty).
 static int dev_solve_batch_traced_any(int32_t max_n, bool mid, int32_t count, int32_t n, int32_t dtype, void *rate,
                                       int32_t *next, int32_t *hops, int64_t stride, const fwx_trace *trace,
-                                      unsigned long long *d_updates_each, void *stream)
+                                      unsigned long long *d_updates_each, void *stream, bool large = false,
+                                      void *scratch = nullptr, size_t scratch_bytes = 0)
 {
     return fwxi::guarded([&]() -> int {
         if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
@@ -1542,6 +1556,10 @@ static int dev_solve_batch_traced_any(int32_t max_n, bool mid, int32_t count, in
             stride < (int64_t)n * n)
             return FWX_ERR_INVALID;
         if (n > max_n) return FWX_ERR_UNSUPPORTED;
+        const bool to_large = large && n >= batch_large_min_n();
+        if (to_large &&
+            (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n)))
+            return FWX_ERR_INVALID;
         if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
         fwx::PathLog plog;
         plog.last = trace->last;
@@ -1549,9 +1567,14 @@ static int dev_solve_batch_traced_any(int32_t max_n, bool mid, int32_t count, in
         plog.at_row = trace->at_row;
         hipStream_t s = (hipStream_t)stream;
         if (dtype == FWX_F64)
-            return dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, 0, n, d_updates_each, s, plog,
-                                           mid);
-        return dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, 0, n, d_updates_each, s, plog, mid);
+            return to_large ? dev_solve_batch_large<double>(count, n, (double *)rate, next, hops, stride, 0, n,
+                                                            d_updates_each, scratch, scratch_bytes, s, plog)
+                            : dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, 0, n,
+                                                      d_updates_each, s, plog, mid);
+        return to_large ? dev_solve_batch_large<float>(count, n, (float *)rate, next, hops, stride, 0, n, d_updates_each,
+                                                       scratch, scratch_bytes, s, plog)
+                        : dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, 0, n, d_updates_each, s,
+                                                 plog, mid);
     });
 }
 
@@ -1571,7 +1594,16 @@ int fwx_dev_solve_batch_mid_traced(int32_t count, int32_t n, int32_t dtype, void
                                       d_updates_each, stream);
 }
 
-// fwx_dev_exact_paths_batch and fwx_dev_exact_paths_batch_mid: one walk, the limit apart.
+int fwx_dev_solve_batch_large_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                                     int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
+                                     void *scratch, size_t scratch_bytes, void *stream)
+{
+    return dev_solve_batch_traced_any(FWX_BATCH_LARGE_MAX_N, true, count, n, dtype, rate, next, hops, stride, trace,
+                                      d_updates_each, stream, true, scratch, scratch_bytes);
+}
+
+// fwx_dev_exact_paths_batch, fwx_dev_exact_paths_batch_mid and fwx_dev_exact_paths_batch_large: one walk, the limit
+// apart.
 static int dev_exact_paths_batch_any(int32_t max_n, int32_t count, int32_t n, int64_t stride, const int32_t *next0,
                                      const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
                                      const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
@@ -1609,6 +1641,15 @@ int fwx_dev_exact_paths_batch_mid(int32_t count, int32_t n, int64_t stride, cons
                                   int32_t *scratch, void *stream)
 {
     return dev_exact_paths_batch_any(FWX_BATCH_MID_MAX_N, count, n, stride, next0, trace, items, mat, src, dst,
+                                     len_out, path_out, cap, scratch, stream);
+}
+
+int fwx_dev_exact_paths_batch_large(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                                    const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                    int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_batch_any(FWX_BATCH_LARGE_MAX_N, count, n, stride, next0, trace, items, mat, src, dst,
                                      len_out, path_out, cap, scratch, stream);
 }
 
@@ -1653,6 +1694,28 @@ int fwx_solve_batch_mid_lists_f32(int32_t count, int32_t n, float *rate, int32_t
     return fwxi::guarded([&]() -> int {
         const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
         return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true);
+    });
+}
+
+int fwx_solve_batch_large_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                    const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true, true);
+    });
+}
+
+int fwx_solve_batch_large_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                    const fwx_opts *opts)
+{
+    return fwxi::guarded([&]() -> int {
+        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true, true);
     });
 }
 

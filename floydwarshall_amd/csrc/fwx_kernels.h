@@ -182,7 +182,10 @@ hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, in
 // counters as launch_batch_mid, several workgroups per matrix: per block of FWX_LARGE_B pivots one panel launch
 // (column strips of FWX_LARGE_S, matrices) that writes the time-k snapshot panels to `scratch`, and one sweep launch
 // (column tiles of FWX_LARGE_TC, row tiles of FWX_LARGE_TR, matrices) that folds them into the matrix.  Any n from 1
-// up, any stride >= n*n, scalar accesses only; no path trace.  scratch: device memory, 16-byte aligned,
+// up, any stride >= n*n, scalar accesses only.  plog (optional; plog.last != nullptr): the path trace as
+// launch_batch_mid lays it out -- `last` filled by a launch of its own before the first block, every cell of the n x n
+// part of at_row / at_col written by exactly one panel workgroup, the gap never; needs next and the whole pivot range
+// [0, n) (hipErrorInvalidValue otherwise) and no scratch of its own.  scratch: device memory, 16-byte aligned,
 // FWX_LARGE_SCRATCH_BYTES(n) per matrix (an upper bound over dtype and field set: W, Ct, WN, CNt, WH, CHt, each
 // [B][n]); the batch is solved in groups of scratch_bytes / FWX_LARGE_SCRATCH_BYTES(n) matrices, one after the other
 // on s, and nothing past group x per-matrix bytes is touched.  hipErrorInvalidValue for scratch that is null,
@@ -203,7 +206,7 @@ hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, in
 template <typename T>
 hipError_t launch_batch_large(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
                               int k_end, unsigned long long *updates_each, void *scratch, size_t scratch_bytes,
-                              hipStream_t s);
+                              hipStream_t s, PathLog plog = PathLog());
 
 // Ragged batch: `count` matrices of different orders, matrix id of order n_each[id] <= FWX_SMALL_N at element
 // offset[id] of rate (next / hops / the trace arrays alike), pitch n_each[id]; whole pivot range of each.  The three

@@ -36,6 +36,21 @@
 // alignment beyond the element; tiles and strips are ragged at the right and bottom edges.  The gap between
 // matrices is never read or written, the diagonal's rate neither.
 //
+// The path trace (HAS_LAST; PathLog in fwx_kernels.h, whole pivot range only) rides on the two launches as it rides on
+// the mid tier's three phases (fwx_mid.hip), and needs no scratch:
+//   0. large_fill_last, once per call and before the first block of the first group, writes -1 to the n x n cells of
+//      `last` of every matrix of the batch (the caller initialises nothing; the gap is not touched).
+//   1. large_panel keeps two more int32 LDS panels, AR and AC [B][pitch]: AR[t][p] = last[k0+t][index(p)] and
+//      AC[t][p] = last[index(p)][k0+t], loaded beside the rates -- `last` as it stands at BLOCK START, written by the
+//      sweeps before this launch.  A panel-phase win of pivot k0+t on W[u][c] sets AR[u][c] = k0+t, one on C[u][c] sets
+//      AC[u][c] = k0+t.  After the pivot loop the frozen STRIP positions -- the positions the rate panels store -- go
+//      straight to the caller's trace: at_row[k0+t][x] = AR[t][p], at_col[x][k0+t] = AC[t][p].  Every cell of at_row
+//      and at_col belongs to one pivot block and one strip: it is written by exactly one workgroup, exactly once per
+//      solve, and no two workgroups ever store to one address.  The copies of a cross cell in other strips see the same
+//      wins (the bit-equality argument above) and are dropped.
+//   2. large_sweep: a win stores last = k0 + (the last winning t) beside next and hops.
+// Stream order between launches is all the trace relies on, as the solve does.
+//
 // Scratch: FWX_LARGE_SCRATCH_BYTES(n) per matrix of the group, laid out for the dtype and field set of the call
 // (W, Ct as T, then the int32 panels), an upper bound: 2 panels x B rows x n columns x 16 bytes.  launch_batch_large
 // solves the batch in groups of as many matrices as the scratch holds, one group after the other on the stream.
@@ -84,15 +99,32 @@ __device__ __forceinline__ LargePanels<T> large_panels(char *scratch, size_t per
     return p;
 }
 
-template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+// -1 to the n x n cells of `last` of matrix blockIdx.y, kFillCells cells per workgroup.
+constexpr int kFillThreads = 256, kFillCells = 4 * kFillThreads;
+__global__ __launch_bounds__(kFillThreads) void large_fill_last(int32_t *last, int n, long long stride)
+{
+    const size_t cells = (size_t)n * (size_t)n;
+    int32_t *m = last + (size_t)blockIdx.y * (size_t)stride;
+    const size_t e0 = (size_t)blockIdx.x * kFillCells + threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < kFillCells / kFillThreads; ++q) {
+        const size_t e = e0 + (size_t)q * kFillThreads;
+        if (e < cells) m[e] = -1;
+    }
+}
+
+// The trace arguments stand last: an instantiation without HAS_LAST reads none of them.
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
 __global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, const int32_t *next, const int32_t *hops,
                                                              int n, long long stride, int k0, int bt, char *scratch,
-                                                             size_t per_matrix)
+                                                             size_t per_matrix, PathLog plog)
 {
+    static_assert(HAS_NEXT || !HAS_LAST, "the trace goes with next");
     constexpr int B = kLargeB, S = kLargeS, Q = kLargePitch;
     __shared__ T W[B][Q], C[B][Q];
     __shared__ int32_t WN[HAS_NEXT ? B : 1][HAS_NEXT ? Q : 1], CN[HAS_NEXT ? B : 1][HAS_NEXT ? Q : 1];
     __shared__ int32_t WH[HAS_HOPS ? B : 1][HAS_HOPS ? Q : 1], CH[HAS_HOPS ? B : 1][HAS_HOPS ? Q : 1];
+    __shared__ int32_t AR[HAS_LAST ? B : 1][HAS_LAST ? Q : 1], AC[HAS_LAST ? B : 1][HAS_LAST ? Q : 1];
 
     const int tid = threadIdx.x;
     const int s0 = (int)blockIdx.x * S;
@@ -114,6 +146,7 @@ __global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, cons
         W[t][lane] = (x < 0 || x == k) ? large_nan<T>() : rate[e];
         if constexpr (HAS_NEXT) WN[t][lane] = x < 0 ? -1 : next[e];
         if constexpr (HAS_HOPS) WH[t][lane] = x < 0 ? 0 : hops[e];
+        if constexpr (HAS_LAST) AR[t][lane] = x < 0 ? -1 : plog.last[off + e];
     }
     // ---- load: pivot columns, thread on (position, t), t fastest: 16 consecutive elements of a row ----------
     {
@@ -124,6 +157,7 @@ __global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, cons
             C[t][p] = (x < 0 || x == k) ? large_nan<T>() : rate[g];
             if constexpr (HAS_NEXT) CN[t][p] = x < 0 ? -1 : next[g];
             if constexpr (HAS_HOPS) CH[t][p] = x < 0 ? 0 : hops[g];
+            if constexpr (HAS_LAST) AC[t][p] = x < 0 ? -1 : plog.last[off + g];
         }
     }
     __syncthreads();
@@ -138,6 +172,7 @@ __global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, cons
                 W[u][c] = cand_w;
                 if constexpr (HAS_NEXT) { const int32_t h = CN[t][u]; WN[u][c] = h >= 0 ? h : WN[t][c]; }
                 if constexpr (HAS_HOPS) WH[u][c] = CH[t][u] + WH[t][c];
+                if constexpr (HAS_LAST) AR[u][c] = k0 + t;
             }
             // column k0+u of the matrix: entry (index(c), k0+u) against (index(c), k) * (k, k0+u)
             const T cand_c = C[t][c] * W[t][u];
@@ -145,6 +180,7 @@ __global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, cons
                 C[u][c] = cand_c;
                 if constexpr (HAS_NEXT) { const int32_t h = CN[t][c]; CN[u][c] = h >= 0 ? h : WN[t][u]; }
                 if constexpr (HAS_HOPS) CH[u][c] = CH[t][c] + WH[t][u];
+                if constexpr (HAS_LAST) AC[u][c] = k0 + t;
             }
         }
         __syncthreads();
@@ -159,15 +195,24 @@ __global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, cons
             pn.Ct[e] = C[wave][lane];
             if constexpr (HAS_NEXT) { pn.WN[e] = WN[wave][lane]; pn.CNt[e] = CN[wave][lane]; }
             if constexpr (HAS_HOPS) { pn.WH[e] = WH[wave][lane]; pn.CHt[e] = CH[wave][lane]; }
+            if constexpr (HAS_LAST) plog.at_row[off + (size_t)(k0 + wave) * n + x] = AR[wave][lane];
         }
+    }
+    // ---- the trace's column cells: thread on (position, t) as in the column load, t fastest -- the 16 pivots of a
+    // position are one 64-byte segment of its row of at_col
+    if constexpr (HAS_LAST) {
+        const int t = tid & (B - 1), p = tid >> 4, x = s0 + p - B;
+        if (p >= B && t < bt && x < n) plog.at_col[off + (size_t)x * n + k0 + t] = AC[t][p];
     }
 }
 
-template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
 __global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *next, int32_t *hops, int n,
                                                              long long stride, int bt, char *scratch,
-                                                             size_t per_matrix, unsigned long long *updates)
+                                                             size_t per_matrix, unsigned long long *updates,
+                                                             int32_t *last, int k0)
 {
+    static_assert(HAS_NEXT || !HAS_LAST, "the trace goes with next");
     constexpr int B = kLargeB, TR = kLargeTR, TC = kLargeTC;
     __shared__ T C[B][TR];
     __shared__ int32_t CN[HAS_NEXT ? B : 1][HAS_NEXT ? TR : 1], CH[HAS_HOPS ? B : 1][HAS_HOPS ? TR : 1];
@@ -180,6 +225,7 @@ __global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *n
     rate += off;
     if constexpr (HAS_NEXT) next += off;
     if constexpr (HAS_HOPS) hops += off;
+    if constexpr (HAS_LAST) last += off;
     const LargePanels<T> pn = large_panels<T>(scratch, per_matrix, blockIdx.z, n);
 
     if (tid == 0) s_cnt = 0;
@@ -234,6 +280,7 @@ __global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *n
                         next[e] = h >= 0 ? h : pn.WN[(size_t)tb[m] * n + j];
                     }
                     if constexpr (HAS_HOPS) hops[e] = CH[tb[m]][r] + pn.WH[(size_t)tb[m] * n + j];
+                    if constexpr (HAS_LAST) last[e] = k0 + tb[m];
                 }
             }
         }
@@ -250,9 +297,11 @@ __global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *n
 template <typename T>
 hipError_t launch_batch_large(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
                               int k_end, unsigned long long *updates_each, void *scratch, size_t scratch_bytes,
-                              hipStream_t s)
+                              hipStream_t s, PathLog plog)
 {
     if (count <= 0 || n <= 0) return hipSuccess;
+    const bool traced = plog.last != nullptr;
+    if (traced && (!next || !plog.at_col || !plog.at_row || k_begin != 0 || k_end != n)) return hipErrorInvalidValue;
     if (k_end <= k_begin) return hipSuccess;
     if (n > FWX_LARGE_N || (hops && !next) || k_begin < 0 || k_end > n || stride < (long long)n * n)
         return hipErrorInvalidValue;
@@ -262,24 +311,35 @@ hipError_t launch_batch_large(T *rate, int32_t *next, int32_t *hops, int count, 
     const long long group = std::min<long long>((long long)(scratch_bytes / per_matrix), 65535);
     const dim3 strips((n + kLargeS - 1) / kLargeS), tiles((n + kLargeTC - 1) / kLargeTC, (n + kLargeTR - 1) / kLargeTR);
     char *sc = (char *)scratch;
+    // the trace's step 0, over every group at once: a later group's `last` is not touched before its own first block
+    for (long long b0 = 0; traced && b0 < count; b0 += 65535) {
+        const unsigned cnt = (unsigned)std::min<long long>(65535, count - b0);
+        const unsigned wgs = (unsigned)(((size_t)n * n + kFillCells - 1) / kFillCells);
+        hipLaunchKernelGGL(large_fill_last, dim3(wgs, cnt), dim3(kFillThreads), 0, s,
+                           plog.last + (size_t)b0 * (size_t)stride, n, stride);
+    }
     for (long long b0 = 0; b0 < count; b0 += group) {
         const unsigned cnt = (unsigned)std::min<long long>(group, count - b0);
         const size_t off = (size_t)b0 * (size_t)stride;
         T *r = rate + off;
         int32_t *nx = next ? next + off : nullptr, *hp = hops ? hops + off : nullptr;
         unsigned long long *u = updates_each ? updates_each + b0 : nullptr;
+        PathLog pl;
+        if (traced) { pl.last = plog.last + off; pl.at_col = plog.at_col + off; pl.at_row = plog.at_row + off; }
         for (int k0 = k_begin; k0 < k_end; k0 += kLargeB) {
             const int bt = std::min(kLargeB, k_end - k0);
-#define FWX_BATCH_LARGE(HN, HH)                                                                                        \
+#define FWX_BATCH_LARGE(HN, HH, HL)                                                                                    \
     do {                                                                                                               \
-        hipLaunchKernelGGL((large_panel<T, HN, HH>), dim3(strips.x, cnt), dim3(kPanelThreads), 0, s, r, nx, hp, n,     \
-                           stride, k0, bt, sc, per_matrix);                                                            \
-        hipLaunchKernelGGL((large_sweep<T, HN, HH>), dim3(tiles.x, tiles.y, cnt), dim3(kSweepThreads), 0, s, r, nx,    \
-                           hp, n, stride, bt, sc, per_matrix, u);                                                      \
+        hipLaunchKernelGGL((large_panel<T, HN, HH, HL>), dim3(strips.x, cnt), dim3(kPanelThreads), 0, s, r, nx, hp, n, \
+                           stride, k0, bt, sc, per_matrix, pl);                                                        \
+        hipLaunchKernelGGL((large_sweep<T, HN, HH, HL>), dim3(tiles.x, tiles.y, cnt), dim3(kSweepThreads), 0, s, r,    \
+                           nx, hp, n, stride, bt, sc, per_matrix, u, pl.last, k0);                                     \
     } while (0)
-            if (hops) FWX_BATCH_LARGE(true, true);
-            else if (next) FWX_BATCH_LARGE(true, false);
-            else FWX_BATCH_LARGE(false, false);
+            if (traced && hops) FWX_BATCH_LARGE(true, true, true);
+            else if (traced) FWX_BATCH_LARGE(true, false, true);
+            else if (hops) FWX_BATCH_LARGE(true, true, false);
+            else if (next) FWX_BATCH_LARGE(true, false, false);
+            else FWX_BATCH_LARGE(false, false, false);
 #undef FWX_BATCH_LARGE
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
@@ -289,8 +349,8 @@ hipError_t launch_batch_large(T *rate, int32_t *next, int32_t *hops, int count, 
 }
 
 template hipError_t launch_batch_large<float>(float *, int32_t *, int32_t *, int, int, long long, int, int,
-                                              unsigned long long *, void *, size_t, hipStream_t);
+                                              unsigned long long *, void *, size_t, hipStream_t, PathLog);
 template hipError_t launch_batch_large<double>(double *, int32_t *, int32_t *, int, int, long long, int, int,
-                                               unsigned long long *, void *, size_t, hipStream_t);
+                                               unsigned long long *, void *, size_t, hipStream_t, PathLog);
 
 }  // namespace fwx

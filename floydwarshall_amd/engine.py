@@ -19,7 +19,8 @@ from ._lib import (FWX_ENGINE_AUTO, FWX_ENGINE_FUSED, FWX_ENGINE_PERK, FWX_F32, 
 
 __all__ = ["solve", "solve_batch", "dev_solve_batch", "solve_batch_lists", "dev_solve_batch_traced",
            "dev_exact_paths_batch", "solve_batch_mid", "dev_solve_batch_mid", "solve_batch_mid_lists",
-           "solve_batch_large", "dev_solve_batch_large",
+           "solve_batch_large", "dev_solve_batch_large", "solve_batch_large_lists", "dev_solve_batch_large_traced",
+           "dev_exact_paths_batch_large",
            "dev_solve_batch_mid_traced", "dev_exact_paths_batch_mid", "ragged_plan", "solve_ragged", "solve_ragged_lists", "dev_solve_ragged",
            "dev_exact_paths_ragged", "ragged_mid_plan", "solve_ragged_mid", "solve_ragged_mid_lists",
            "dev_solve_ragged_mid", "dev_exact_paths_ragged_mid", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
@@ -226,6 +227,12 @@ def solve_batch_mid_lists(rate, nxt, hops=None, *, items=None, cap=None, device=
     return _solve_batch_lists("fwx_solve_batch_mid_lists", rate, nxt, hops, items, cap, device, count_updates)
 
 
+def solve_batch_large_lists(rate, nxt, hops=None, *, items=None, cap=None, device=-1, count_updates=False):
+    """solve_batch_mid_lists with the limit at n <= FWX_BATCH_LARGE_MAX_N (fwx_solve_batch_large_lists_f64 / _f32);
+    routing by FWX_BATCH_LARGE_MIN_N as solve_batch_large.  Same arrays, same lists, same return value."""
+    return _solve_batch_lists("fwx_solve_batch_large_lists", rate, nxt, hops, items, cap, device, count_updates)
+
+
 def _solve_batch_lists(stem, rate, nxt, hops, items, cap, device, count_updates):
     if nxt is None:
         raise ValueError("the exact lists need next")
@@ -302,7 +309,19 @@ def dev_solve_batch_mid_traced(rate_t, count, n, trace, *, next_t, hops_t=None, 
                             updates_t, stream)
 
 
-def _dev_solve_batch_traced(name, rate_t, count, n, trace, next_t, hops_t, stride, updates_t, stream):
+def dev_solve_batch_large_traced(rate_t, count, n, trace, *, next_t, hops_t=None, stride=None, updates_t=None,
+                                 scratch_t=None, stream=None):
+    """fwx_dev_solve_batch_large_traced: dev_solve_batch_mid_traced with the limit at n <= FWX_BATCH_LARGE_MAX_N;
+    routing by FWX_BATCH_LARGE_MIN_N as solve_batch_large, scratch_t as dev_solve_batch_large takes it.  Same arrays,
+    same trace.  Returns the scratch array: it must stay alive until the stream has run the call."""
+    if scratch_t is None:
+        scratch_t = _empty_like_device(rate_t, (max(count, 1) * _lib.batch_large_scratch_bytes(n),), "uint8")
+    _dev_solve_batch_traced("fwx_dev_solve_batch_large_traced", rate_t, count, n, trace, next_t, hops_t, stride,
+                            updates_t, stream, scratch_t)
+    return scratch_t
+
+
+def _dev_solve_batch_traced(name, rate_t, count, n, trace, next_t, hops_t, stride, updates_t, stream, scratch_t=None):
     stride = n * n if stride is None else int(stride)
     need = (count - 1) * stride + n * n if count > 0 else 0
     assert rate_t.is_cuda and rate_t.is_contiguous() and rate_t.numel() >= need
@@ -315,7 +334,9 @@ def _dev_solve_batch_traced(name, rate_t, count, n, trace, next_t, hops_t, strid
     check(getattr(lib(), name)(
         count, n, _tensor_dtype_code(rate_t), vp(rate_t.data_ptr()), vp(next_t.data_ptr()),
         vp(hops_t.data_ptr()) if hops_t is not None else None, stride, _trace_of(trace, need),
-        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)), name)
+        vp(updates_t.data_ptr()) if updates_t is not None else None,
+        *(() if scratch_t is None else (vp(scratch_t.data_ptr()), scratch_t.numel() * scratch_t.element_size())),
+        _stream_ptr(stream, rate_t)), name)
 
 
 def dev_exact_paths_batch(next0_t, count, n, trace, mat_t, src_t, dst_t, cap, *, stride=None, stream=None):
@@ -332,6 +353,13 @@ def dev_exact_paths_batch_mid(next0_t, count, n, trace, mat_t, src_t, dst_t, cap
     n <= FWX_BATCH_MID_MAX_N."""
     return _dev_exact_paths_batch("fwx_dev_exact_paths_batch_mid", next0_t, count, n, trace, mat_t, src_t, dst_t, cap,
                                   stride, stream)
+
+
+def dev_exact_paths_batch_large(next0_t, count, n, trace, mat_t, src_t, dst_t, cap, *, stride=None, stream=None):
+    """fwx_dev_exact_paths_batch_large: dev_exact_paths_batch over a batch that dev_solve_batch_large_traced solved,
+    n <= FWX_BATCH_LARGE_MAX_N."""
+    return _dev_exact_paths_batch("fwx_dev_exact_paths_batch_large", next0_t, count, n, trace, mat_t, src_t, dst_t,
+                                  cap, stride, stream)
 
 
 def _dev_exact_paths_batch(name, next0_t, count, n, trace, mat_t, src_t, dst_t, cap, stride, stream):

@@ -259,7 +259,8 @@ int fwx_test_batch_mid_block(void);
  * panels in device scratch between them, column strips (panel) and tiles (sweep) of every matrix on workgroups of
  * their own.  Every matrix gets the full semantics above, the list rule included; there is no domain check and no
  * routing by content, and each matrix comes back bit-identical to the reference loop on that matrix alone -- rate,
- * next, hops (diagonals included) and U.  No exact `_path` lists and no ragged form above 256.
+ * next, hops (diagonals included) and U.  The exact `_path` lists: fwx_solve_batch_large_lists_* below.  No ragged
+ * form above 256.
  *
  * The contract is that of fwx_solve_batch_mid_* / fwx_dev_solve_batch_mid, with the limit at
  * FWX_BATCH_LARGE_MAX_N: count matrices of order n, matrix b at rate + b*n*n (next / hops alike, both optional, hops
@@ -394,6 +395,51 @@ int fwx_solve_batch_mid_lists_f32(int32_t count, int32_t n, float *rate, int32_t
                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
                                   const fwx_opts *opts);
+
+/* ---- batched large solves with the exact `_path` lists ----------------------------------------------------
+ * The three families above with the limit at FWX_BATCH_LARGE_MAX_N (1024): a price history of a 30 x 20 market gets
+ * the lists the reference would print, not only rate, next and hops.  The contracts are those of
+ * fwx_dev_solve_batch_mid_traced, fwx_dev_exact_paths_batch_mid and fwx_solve_batch_mid_lists_*, word for word -- the
+ * statuses decided before any device call (FWX_ERR_UNSUPPORTED: n > FWX_BATCH_LARGE_MAX_N), whole pivot range only,
+ * next required, hops optional, every cell of the n x n part of the three trace arrays written by the solve (the
+ * diagonal included; the caller initialises nothing) and the gap never, the capacity rule, items judged one by one,
+ * scratch of the walk items * FWX_EXACT_SCRATCH_INTS(n) int32, chunks by FWX_BATCH_LISTS_CHUNK.
+ * scratch / scratch_bytes of the traced solve: the snapshot panels, by the rules of fwx_dev_solve_batch_large --
+ * 16-byte aligned, at least FWX_BATCH_LARGE_SCRATCH_BYTES(n) (the trace needs none of it: the value is the untraced
+ * call's), the batch solved in groups of what it holds; FWX_ERR_INVALID for scratch that is NULL, misaligned or too
+ * small, only when n is routed to the large tier.  The host forms take the panels and the lists' memory from the
+ * pooled per-call context in one piece, the panels capped at 256 MiB as for fwx_solve_batch_large_*.
+ * Routing by FWX_BATCH_LARGE_MIN_N as for fwx_solve_batch_large_*: orders below it go to
+ * fwx_dev_solve_batch_mid_traced / the mid lists path (which forward further), orders from it up run the large tier:
+ * `last` is filled by a launch of its own before the first pivot block, the panel launch carries `last` of its strip
+ * through the panel phase in two more LDS panels and writes every cell of at_row / at_col from exactly one workgroup,
+ * the sweep stores `last` with next and hops.  No cell of any output, the trace arrays included, depends on the
+ * routing.  The entry points above keep refusing n > FWX_BATCH_MID_MAX_N.
+ * When it pays (MI355X, f64 + next + hops on market inputs, profiles/r27_batch_large_lists.txt).  The trace costs the
+ * solve 6 - 8 % for one matrix, 5.5 - 15 % for 16 and 15 - 18 % for 256 (n = 512, 16 matrices: 1.23 against 1.16 ms;
+ * n = 1024, 256 matrices: 91.4 against 79.4 ms); the walk of 65536 lists takes 0.10 - 0.13 ms at every order.  Against
+ * what a host had before -- one traced handle per matrix: upload, solve, fwx_matrix_query_exact_batch -- solve plus
+ * walk per matrix is 11.6x / 11.2x / 9.5x / 7.2x / 4.8x faster at n = 257 / 384 / 512 / 768 / 1024 with 16 matrices
+ * (0.042 ... 0.40 ms against 0.49 ... 1.9 ms), 29x ... 4.1x with 256, and 1.2 - 1.6x with one.  The HOST form copies the
+ * whole batch to the device and back through the caller's arrays and is bound by that: with 16 matrices it is 3.6x and
+ * 2.4x faster than the handle loop at n = 257 and 512 but 2 - 3x slower at n = 384, 768 and 1024, and 1.5 - 1.7x slower
+ * for one matrix at every order -- a host that can keep the batch on the device calls the device forms.           */
+int fwx_dev_solve_batch_large_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next,
+                                     int32_t *hops, int64_t stride, const struct fwx_trace *trace,
+                                     unsigned long long *d_updates_each,
+                                     void *scratch, size_t scratch_bytes, void *stream);
+int fwx_dev_exact_paths_batch_large(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                                    const struct fwx_trace *trace, int32_t items, const int32_t *mat,
+                                    const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                                    int32_t cap, int32_t *scratch, void *stream);
+int fwx_solve_batch_large_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                    const fwx_opts *opts);
+int fwx_solve_batch_large_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                    const fwx_opts *opts);
 
 /* ---- ragged batched small solves: matrices of DIFFERENT orders in one call --------------------------------
  * A price history does not have one order: the vertex set grows as exchanges and currencies first appear, and venue

@@ -19,7 +19,8 @@ Host form, host clock around blocking calls: fwx_solve_batch_large_f64 against `
 (cells up to --host-max-count matrices).
 
 Every order is measured by a child process of its own under a time limit (--step-timeout); after a child that
-failed or ran out of time nothing more is started.  No torch in the process.
+failed or ran out of time nothing more is started.  No torch in the process.  With FWX_LIB_PATH pointing at a build of
+an earlier commit the same cells give that commit's side of an A/B (symbols it lacks are not bound).
 usage: measure_batch_large.py [--out FILE.json] [--reps 5] [--orders 257,384,...] [--counts 1,2,...]"""
 import argparse
 import ctypes
@@ -184,6 +185,10 @@ def main():
     args = ap.parse_args()
     if args.reps < 5:
         ap.error("--reps must be at least 5")
+    if os.environ.get("FWX_LIB_PATH"):      # an older build of the same ABI lacks the symbols later rounds added: the
+        have = ctypes.CDLL(_lib.LIB_PATH)   # parent's side of an A/B of this call, alternated with this tree's in one job
+        for name in [name for name in _lib.SIGNATURES if not hasattr(have, name)]:
+            del _lib.SIGNATURES[name]
     counts = [int(v) for v in args.counts.split(",")]
     if args.worker is not None:
         return worker(args, args.worker, counts)
