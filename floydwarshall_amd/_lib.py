@@ -111,70 +111,6 @@ SIGNATURES = {
     "fwx_test_perk_wide": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "fwx_solve_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
     "fwx_solve_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_batch_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_batch_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_dev_solve_batch": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32,
-                                           c_vp, c_vp]),
-    "fwx_test_batch_wave_max_n": (ctypes.c_int, []),
-    "fwx_solve_batch_mid_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_batch_mid_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_dev_solve_batch_mid": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32,
-                                               c_vp, c_vp]),
-    "fwx_test_batch_mid_min_n": (ctypes.c_int, []),
-    "fwx_test_batch_mid_block": (ctypes.c_int, []),
-    "fwx_solve_batch_large_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_batch_large_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_dev_solve_batch_large": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32,
-                                                 c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "fwx_test_batch_large_min_n": (ctypes.c_int, []),
-    "fwx_test_batch_large_geometry": (ctypes.c_int, [ctypes.POINTER(c_i32)]),
-    "fwx_dev_solve_batch_traced": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64,
-                                                  ctypes.POINTER(FwxTrace), c_vp, c_vp]),
-    "fwx_dev_exact_paths_batch": (ctypes.c_int, [c_i32, c_i32, ctypes.c_int64, c_vp, ctypes.POINTER(FwxTrace), c_i32,
-                                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
-    "fwx_solve_batch_lists_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
-                                                 c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_batch_lists_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
-                                                 c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_test_batch_lists_chunk": (ctypes.c_int64, [c_i32, c_i32]),
-    "fwx_dev_solve_batch_mid_traced": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64,
-                                                      ctypes.POINTER(FwxTrace), c_vp, c_vp]),
-    "fwx_dev_exact_paths_batch_mid": (ctypes.c_int, [c_i32, c_i32, ctypes.c_int64, c_vp, ctypes.POINTER(FwxTrace),
-                                                     c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
-    "fwx_solve_batch_mid_lists_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
-                                                     c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_batch_mid_lists_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
-                                                     c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_dev_solve_batch_large_traced": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.c_int64,
-                                                        ctypes.POINTER(FwxTrace), c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "fwx_dev_exact_paths_batch_large": (ctypes.c_int, [c_i32, c_i32, ctypes.c_int64, c_vp, ctypes.POINTER(FwxTrace),
-                                                       c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
-    "fwx_solve_batch_large_lists_f64": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
-                                                       c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_batch_large_lists_f32": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
-                                                       c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_ragged_plan": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp]),
-    "fwx_solve_ragged_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_ragged_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_dev_solve_ragged": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                            ctypes.POINTER(FwxTrace), c_vp, c_vp]),
-    "fwx_dev_exact_paths_ragged": (ctypes.c_int, [c_i32, c_vp, c_vp, c_i32, c_vp, ctypes.POINTER(FwxTrace), c_i32,
-                                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
-    "fwx_solve_ragged_lists_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
-                                                  c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_ragged_lists_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
-                                                  c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_ragged_mid_plan": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp]),
-    "fwx_solve_ragged_mid_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_ragged_mid_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
-    "fwx_dev_solve_ragged_mid": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                                ctypes.POINTER(FwxTrace), c_vp, c_vp]),
-    "fwx_dev_exact_paths_ragged_mid": (ctypes.c_int, [c_i32, c_vp, c_vp, c_i32, c_vp, ctypes.POINTER(FwxTrace), c_i32,
-                                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
-    "fwx_solve_ragged_mid_lists_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
-                                                      c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
-    "fwx_solve_ragged_mid_lists_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
-                                                      c_vp, c_vp, c_i32, ctypes.POINTER(FwxOpts)]),
     "fwx_follow_path": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i32, c_vp, c_i32]),
     "fwx_matrix_create": (ctypes.c_int, [ctypes.POINTER(c_vp), c_i32, c_i32, c_i32, c_i32, c_i32]),
     "fwx_matrix_upload": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
@@ -230,6 +166,45 @@ SIGNATURES = {
                                                 c_vp]),
     "fwx_dev_check_nonneg": (ctypes.c_int, [ctypes.POINTER(FwxSlab), c_vp, c_vp]),
 }
+
+# The batched solves (csrc/fwx_batch.hip).  Every argument list of the family is put together from these pieces, each
+# named once: how a batch is addressed, its three arrays, the items of the exact lists.
+_OPTS, _TRACE = ctypes.POINTER(FwxOpts), ctypes.POINTER(FwxTrace)
+_UNIFORM = [c_i32, c_i32]                                   # count, n
+_RAGGED = [c_i32, c_vp]                                     # count, n_each
+_ARRAYS = [c_vp, c_vp, c_vp]                                # rate, next, hops
+_ITEMS = [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32]       # items, mat, src, dst, len_out, path_out, cap
+_SCRATCH = [c_vp, ctypes.c_size_t]                          # the large tier's scratch panels
+for _stem, _batch in (("batch", _UNIFORM), ("batch_mid", _UNIFORM), ("batch_large", _UNIFORM), ("ragged", _RAGGED),
+                      ("ragged_mid", _RAGGED)):
+    for _t in ("f64", "f32"):                               # ..., updates_each, [the items,] opts
+        SIGNATURES["fwx_solve_%s_%s" % (_stem, _t)] = (ctypes.c_int, _batch + _ARRAYS + [c_vp, _OPTS])
+        SIGNATURES["fwx_solve_%s_lists_%s" % (_stem, _t)] = (ctypes.c_int, _batch + _ARRAYS + [c_vp] + _ITEMS + [_OPTS])
+for _stem, _extra in (("batch", []), ("batch_mid", []), ("batch_large", _SCRATCH)):
+    # count, n, dtype, the arrays, stride, [k_begin, k_end | trace], d_updates_each, [scratch,] stream
+    SIGNATURES["fwx_dev_solve_" + _stem] = (
+        ctypes.c_int, _UNIFORM + [c_i32] + _ARRAYS + [ctypes.c_int64, c_i32, c_i32, c_vp] + _extra + [c_vp])
+    SIGNATURES["fwx_dev_solve_%s_traced" % _stem] = (
+        ctypes.c_int, _UNIFORM + [c_i32] + _ARRAYS + [ctypes.c_int64, _TRACE, c_vp] + _extra + [c_vp])
+    # count, n, stride, next0, trace, the items, scratch, stream
+    SIGNATURES["fwx_dev_exact_paths_" + _stem] = (
+        ctypes.c_int, _UNIFORM + [ctypes.c_int64, c_vp, _TRACE] + _ITEMS + [c_vp, c_vp])
+for _mid in ("", "_mid"):
+    SIGNATURES["fwx_ragged%s_plan" % _mid] = (ctypes.c_int, _RAGGED + [c_vp, c_vp, c_vp])
+    # count, dtype, the arrays, d_n_each, d_offset, d_order, tier_count, trace, d_updates_each, stream
+    SIGNATURES["fwx_dev_solve_ragged" + _mid] = (
+        ctypes.c_int, [c_i32, c_i32] + _ARRAYS + [c_vp, c_vp, c_vp, c_vp, _TRACE, c_vp, c_vp])
+    # count, d_n_each, d_offset, n_max, next0, trace, the items, scratch, stream
+    SIGNATURES["fwx_dev_exact_paths_ragged" + _mid] = (
+        ctypes.c_int, _RAGGED + [c_vp, c_i32, c_vp, _TRACE] + _ITEMS + [c_vp, c_vp])
+SIGNATURES.update({
+    "fwx_test_batch_wave_max_n": (ctypes.c_int, []),
+    "fwx_test_batch_mid_min_n": (ctypes.c_int, []),
+    "fwx_test_batch_mid_block": (ctypes.c_int, []),
+    "fwx_test_batch_large_min_n": (ctypes.c_int, []),
+    "fwx_test_batch_large_geometry": (ctypes.c_int, [ctypes.POINTER(c_i32)]),
+    "fwx_test_batch_lists_chunk": (ctypes.c_int64, [c_i32, c_i32]),
+})
 
 _LIB = None
 

@@ -17,7 +17,8 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfwx.so")
 CLI = os.path.join(PKG, "fwx_cli")
 
-HIP_SOURCES = ["fwx_kernels.hip", "fwx_mid.hip", "fwx_large.hip", "fwx_fused.hip", "fwx_api.hip", "fwx_multi.hip"]
+HIP_SOURCES = ["fwx_kernels.hip", "fwx_mid.hip", "fwx_large.hip", "fwx_fused.hip", "fwx_api.hip", "fwx_batch.hip",
+               "fwx_multi.hip"]
 CXX_SOURCES = []  # host mirror sources are appended below when present
 HOST_DIR = os.path.join(CSRC, "host")
 

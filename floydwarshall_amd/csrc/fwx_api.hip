@@ -2,6 +2,8 @@
 //
 // Replaces runAlgo (/root/reference/src/lib/Algorithms.hs:42-61) behind floydWarshall (:19-20).
 // No CPU fallback: every solve entry point needs a HIP device and says so when there is none.
+// The batched solves (fwx_solve_batch_*, fwx_solve_ragged_*, their device forms) are fwx_batch.hip; the kernels of
+// their exact walk are here, beside the handles' (fwx_query.h).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -489,327 +491,6 @@ int solve_host(int32_t n, T *rate, int32_t *next, int32_t *hops, const fwx_opts 
     }
     if (op.updates_out) {
         if ((rc = sum_updates((unsigned long long *)d_upd.p, op.updates_out, s))) return rc;
-    }
-    return FWX_OK;
-}
-
-// What the batch entry points decide before any device call (fwx.h): the pivot range against n, then the
-// order against the entry point's limit (FWX_BATCH_MAX_N; FWX_BATCH_MID_MAX_N for the _mid forms).  k_end <= 0
-// means n.
-int batch_range(int32_t n, int32_t k_begin, int32_t &k_end, int32_t max_n = FWX_BATCH_MAX_N)
-{
-    if (k_end <= 0) k_end = n;
-    if (k_begin < 0 || k_begin > k_end || k_end > n) return FWX_ERR_INVALID;
-    return n > max_n ? FWX_ERR_UNSUPPORTED : FWX_OK;
-}
-
-template <typename T>
-int dev_solve_batch(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, int64_t stride,
-                    int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, hipStream_t s,
-                    const fwx::PathLog &plog = fwx::PathLog(), bool mid = false)
-{
-    // mid (the _mid entry points): orders from FWX_BATCH_MID_MIN_N up run the mid tier, smaller ones the tiers
-    // of the plain batch -- the same bits either way
-    const hipError_t e = mid && n >= batch_mid_min_n()
-        ? fwx::launch_batch_mid<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end, d_updates_each, s,
-                                   plog)
-        : fwx::launch_batch_solve<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
-                                     d_updates_each, batch_wave_max_n(), s, plog);
-    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
-    FWX_HIP(e);
-    return FWX_OK;
-}
-
-// The large tier (fwx_solve_batch_large_*, fwx_dev_solve_batch_large) for a call already routed to it (n >=
-// FWX_BATCH_LARGE_MIN_N; below it the callers take dev_solve_batch with mid set): groups of as many matrices as the
-// scratch holds, one after the other on s.  plog: the path trace (fwx_dev_solve_batch_large_traced and
-// fwx_solve_batch_large_lists_*), whole pivot range only.
-template <typename T>
-int dev_solve_batch_large(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, int64_t stride,
-                          int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, void *scratch,
-                          size_t scratch_bytes, hipStream_t s, const fwx::PathLog &plog = fwx::PathLog())
-{
-    const hipError_t e = fwx::launch_batch_large<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
-                                                    d_updates_each, scratch, scratch_bytes, s, plog);
-    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
-    FWX_HIP(e);
-    return FWX_OK;
-}
-
-// Ragged batches (fwx_solve_ragged_*): what the orders alone decide.  FWX_ERR_INVALID for a negative order;
-// n_max is the largest order, whatever it is -- the caller compares it with FWX_BATCH_MAX_N.
-int ragged_orders(int32_t count, const int32_t *n_each, int32_t &n_max)
-{
-    n_max = 0;
-    for (int32_t b = 0; b < count; ++b) {
-        if (n_each[b] < 0) return FWX_ERR_INVALID;
-        n_max = std::max(n_max, n_each[b]);
-    }
-    return FWX_OK;
-}
-
-// fwx_ragged_plan (ntiers = 3; the orders all <= FWX_BATCH_MAX_N) and fwx_ragged_mid_plan (ntiers = 4; all <=
-// FWX_BATCH_MID_MAX_N) for orders that ragged_orders accepted: the packed offsets (count + 1 entries), the matrices
-// with n >= 1 grouped by tier -- wave (n <= wave_max_n), 64-wide, 128-wide and, with four tiers, mid (n >= mid_min_n,
-// which wins where the wave tier claims the order too) -- and within a tier by descending order, ties by ascending
-// index (a counting sort over the orders: the tier is monotone in the order), the rest of `order` -1.  tier_count
-// has ntiers entries.  Any output may be null.
-void ragged_plan(int32_t count, const int32_t *n_each, int wave_max_n, int ntiers, int mid_min_n, int64_t *offset,
-                 int32_t *order, int32_t *tier_count)
-{
-    const int max_n = ntiers == 4 ? FWX_BATCH_MID_MAX_N : FWX_BATCH_MAX_N;
-    auto tier_of = [&](int n) { return ntiers == 4 && n >= mid_min_n ? 3 : n <= wave_max_n ? 0 : n <= 64 ? 1 : 2; };
-    int64_t at[FWX_BATCH_MID_MAX_N + 2] = {0};  // at[n]: matrices of order n, then where the next one of order n goes
-    int32_t tiers[4] = {0, 0, 0, 0};
-    int64_t cells = 0;
-    for (int32_t b = 0; b < count; ++b) {
-        const int n = n_each[b];
-        if (offset) offset[b] = cells;
-        cells += (int64_t)n * n;
-        if (n >= 1) { ++at[n]; ++tiers[tier_of(n)]; }
-    }
-    if (offset) offset[count] = cells;
-    if (tier_count) std::copy(tiers, tiers + ntiers, tier_count);
-    if (!order) return;
-    int64_t pos = 0;
-    for (int tier = 0; tier < ntiers; ++tier)
-        for (int n = max_n; n >= 1; --n)
-            if (tier_of(n) == tier) { const int64_t c = at[n]; at[n] = pos; pos += c; }
-    for (int32_t b = 0; b < count; ++b)
-        if (n_each[b] >= 1) order[at[n_each[b]]++] = b;
-    for (int64_t i = pos; i < count; ++i) order[i] = -1;
-}
-
-template <typename T>
-int dev_solve_ragged(int32_t count, T *rate, int32_t *next, int32_t *hops, const int32_t *d_n_each,
-                     const int64_t *d_offset, const int32_t *d_order, const int32_t tier_count[3],
-                     unsigned long long *d_updates_each, hipStream_t s, const fwx::PathLog &plog = fwx::PathLog())
-{
-    const hipError_t e = fwx::launch_ragged_solve<T>(rate, next, hops, count, d_n_each, d_offset, d_order, tier_count,
-                                                     d_updates_each, s, plog);
-    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
-    FWX_HIP(e);
-    return FWX_OK;
-}
-
-// The four-tier plan (fwx_dev_solve_ragged_mid, fwx_solve_ragged_mid_*): the mid tier first -- its workgroups run
-// longest -- then the three small tiers as dev_solve_ragged launches them, all on s.
-template <typename T>
-int dev_solve_ragged_mid(int32_t count, T *rate, int32_t *next, int32_t *hops, const int32_t *d_n_each,
-                         const int64_t *d_offset, const int32_t *d_order, const int32_t tier_count[4],
-                         unsigned long long *d_updates_each, hipStream_t s, const fwx::PathLog &plog = fwx::PathLog())
-{
-    const long long small = (long long)tier_count[0] + tier_count[1] + tier_count[2];
-    const hipError_t e = fwx::launch_ragged_mid<T>(rate, next, hops, count, d_n_each, d_offset, d_order + small,
-                                                   tier_count[3], d_updates_each, s, plog);
-    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
-    FWX_HIP(e);
-    if (small == 0) return FWX_OK;
-    return dev_solve_ragged<T>(count, rate, next, hops, d_n_each, d_offset, d_order, tier_count, d_updates_each, s,
-                               plog);
-}
-
-// What fwx_solve_batch_lists_* adds to a batch solve: the exact lists of `items` triples, host arrays.
-struct BatchLists {
-    int32_t items;
-    const int32_t *mat, *src, *dst;
-    int32_t *len_out, *path_out;
-    int32_t cap;
-};
-
-// fwx_solve_batch_f64 / _f32: count matrices of order n from / to host arrays, one launch.  Pitch n, no
-// padding (the batch kernels load scalars), the arrays of the batch back to back on the device.
-// ls (fwx_solve_batch_lists_*): the solve also keeps the unsolved next-hops and the path trace in the context
-// and walks the items' lists from them, batch_lists_chunk items per launch.
-// ragged (fwx_solve_ragged_*, fwx_solve_ragged_lists_*): matrix b has order n_each[b] and the batch is packed, matrix
-// b at the sum of the squares before it; the n passed in is ignored and stands for the largest order from then on
-// (the walk's stacks and chunks are sized by it).  Whole pivot range only.  The plan -- offsets, orders, the tier
-// list -- is built here and goes to the context's workspace behind the counters, in one copy.
-// mid (fwx_solve_batch_mid_*): the limit on n is FWX_BATCH_MID_MAX_N and dev_solve_batch routes by
-// FWX_BATCH_MID_MIN_N; everything else is the plain batch solve.  With ls (fwx_solve_batch_mid_lists_*) the mid tier
-// writes the trace itself and the walk is the same launch_exact_batch.
-// ragged && mid (fwx_solve_ragged_mid_*, fwx_solve_ragged_mid_lists_*): the ragged batch with the limit at
-// FWX_BATCH_MID_MAX_N and the four-tier plan (FWX_BATCH_MID_MIN_N read here, by the plan); the workspace layout and
-// the walk are the ragged ones.
-// large (fwx_solve_batch_large_*; with mid, without ragged): the limit on n is FWX_BATCH_LARGE_MAX_N; orders
-// from FWX_BATCH_LARGE_MIN_N up run the large tier, whose scratch panels -- at most kBatchLargeScratchCap, larger
-// batches run in groups -- are the context's SMALL buffer; smaller orders are the mid call.  With ls
-// (fwx_solve_batch_large_lists_*) ONE reservation of that buffer holds both: the scratch panels first (the buffer's
-// own alignment, and every matrix's part a multiple of 16 bytes), then the lists' memory as above.
-constexpr size_t kBatchLargeScratchCap = (size_t)256 << 20;
-template <typename T>
-int solve_batch_host(int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, uint64_t *updates_each,
-                     const fwx_opts *o, const BatchLists *ls = nullptr, bool ragged = false,
-                     const int32_t *n_each = nullptr, bool mid = false, bool large = false)
-{
-    if (count < 0 || (!ragged && n < 0) || (ls && ls->items < 0)) return FWX_ERR_INVALID;
-    if (count == 0 || (!ragged && n == 0)) return FWX_OK;
-    if (ragged) {
-        if (!n_each || ragged_orders(count, n_each, n)) return FWX_ERR_INVALID;
-        if (n == 0) return FWX_OK;
-    }
-    if (!rate || (hops && !next)) return FWX_ERR_INVALID;
-    if (ls && (!next || (ls->items > 0 && (ls->cap < 1 || !ls->mat || !ls->src || !ls->dst || !ls->len_out ||
-                                           !ls->path_out))))
-        return FWX_ERR_INVALID;
-    Opts op;
-    int rc = read_opts(o, n, op);
-    if (rc) return rc;
-    if (ls && (op.k_begin != 0 || op.k_end != n)) return FWX_ERR_INVALID;      // the trace covers whole solves only
-    if (ragged && o && (o->k_begin != 0 || o->k_end > 0)) return FWX_ERR_INVALID;   // one range does not fit all orders
-    const int32_t max_n = large ? FWX_BATCH_LARGE_MAX_N : mid ? FWX_BATCH_MID_MAX_N : FWX_BATCH_MAX_N;
-    if ((rc = batch_range(n, op.k_begin, op.k_end, max_n))) return rc;
-    if (op.engine != FWX_ENGINE_AUTO) return FWX_ERR_UNSUPPORTED;
-    const bool to_large = large && n >= batch_large_min_n();
-    DeviceGuard g;
-    if ((rc = g.enter(op.device))) return rc;
-
-    // the ragged plan, packed for one copy: count offsets, then count orders and the tier list (count) as int32
-    std::vector<int64_t> plan;
-    int32_t tiers[4] = {0, 0, 0, 0};
-    size_t cells = (size_t)count * (size_t)n * (size_t)n;
-    if (ragged) {
-        std::vector<int64_t> offs((size_t)count + 1);
-        plan.resize(2 * (size_t)count);
-        int32_t *h_n = (int32_t *)(plan.data() + count), *h_order = h_n + count;
-        ragged_plan(count, n_each, batch_wave_max_n(), mid ? 4 : 3, batch_mid_min_n(), offs.data(), h_order, tiers);
-        std::copy(offs.begin(), offs.end() - 1, plan.begin());
-        std::copy(n_each, n_each + count, h_n);
-        cells = (size_t)offs[(size_t)count];
-    }
-    const bool counting = updates_each || op.updates_out;
-    CtxLease lease;
-    if ((rc = lease.open())) return rc;
-    CallCtx &cx = *lease.c;
-    if (op.has_stream) cx.uses_stream(op.stream);
-    hipStream_t s = op.has_stream ? op.stream : cx.s;
-    void *d_rate = nullptr, *d_next = nullptr, *d_hops = nullptr, *d_upd = nullptr;
-    fail_point();
-    if ((rc = cx.reserve(CallCtx::RATE, cells * sizeof(T), &d_rate))) return rc;
-    fail_point();
-    if (next && (rc = cx.reserve(CallCtx::NEXT, cells * sizeof(int32_t), &d_next))) return rc;
-    fail_point();
-    if (hops && (rc = cx.reserve(CallCtx::HOPS, cells * sizeof(int32_t), &d_hops))) return rc;
-    std::vector<unsigned long long> h_upd;
-    const size_t b_upd = counting ? (size_t)count * sizeof(unsigned long long) : 0;
-    const int64_t *d_offset = nullptr;
-    const int32_t *d_n_each = nullptr, *d_order = nullptr;
-    if (counting || ragged) {                    // one counter per matrix, then the plan: the context's workspace
-        fail_point();
-        void *ws = nullptr;
-        if ((rc = cx.reserve(CallCtx::WS, b_upd + plan.size() * sizeof(int64_t), &ws))) return rc;
-        if (counting) {
-            h_upd.resize((size_t)count);
-            d_upd = ws;
-            FWX_HIP(hipMemsetAsync(d_upd, 0, b_upd, s));
-        }
-        if (ragged) {
-            d_offset = (const int64_t *)((char *)ws + b_upd);
-            d_n_each = (const int32_t *)(d_offset + count);
-            d_order = d_n_each + count;
-            FWX_HIP(hipMemcpyAsync((void *)d_offset, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        }
-    }
-
-    // pinned staging while the whole batch fits (see solve_host), straight copies above
-    const size_t b_rate = cells * sizeof(T), b_idx = cells * sizeof(int32_t);
-    const size_t b_total = b_rate + (next ? b_idx : 0) + (hops ? b_idx : 0);
-    const bool staged = b_total <= CallCtx::kStageBytes;
-    char *st_rate = nullptr, *st_next = nullptr, *st_hops = nullptr;
-    if (staged) {
-        void *pinned = nullptr;
-        fail_point();
-        if ((rc = cx.reserve_pinned(b_total, &pinned))) return rc;
-        st_rate = (char *)pinned;
-        st_next = st_rate + b_rate;
-        st_hops = st_next + (next ? b_idx : 0);
-        memcpy(st_rate, rate, b_rate);
-        if (next) memcpy(st_next, next, b_idx);
-        if (hops) memcpy(st_hops, hops, b_idx);
-    }
-    FWX_HIP(hipMemcpyAsync(d_rate, staged ? (const void *)st_rate : (const void *)rate, b_rate, hipMemcpyHostToDevice, s));
-    if (next) FWX_HIP(hipMemcpyAsync(d_next, staged ? (const void *)st_next : (const void *)next, b_idx, hipMemcpyHostToDevice, s));
-    if (hops) FWX_HIP(hipMemcpyAsync(d_hops, staged ? (const void *)st_hops : (const void *)hops, b_idx, hipMemcpyHostToDevice, s));
-
-    // lists: the unsolved next-hops and the three trace arrays, then the walk's own memory for one chunk of items
-    // (triples and lengths, lists, stacks), all in the context's SMALL buffer
-    fwx::PathLog plog;
-    int32_t *d_next0 = nullptr, *d_walk = nullptr;
-    const long long chunk = ls ? std::min<long long>(batch_lists_chunk(n, ls->cap), ls->items) : 0;
-    const size_t stack_ints = FWX_EXACT_SCRATCH_INTS((size_t)n);
-    // the large tier's scratch panels: none for an empty pivot range (with ls the range is whole)
-    const size_t per_large = FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n);
-    const size_t b_scratch = to_large && op.k_end > op.k_begin
-        ? per_large * std::min<size_t>((size_t)count, std::max<size_t>(1, kBatchLargeScratchCap / per_large)) : 0;
-    static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1) % 16 == 0, "what follows the scratch panels stays 16-byte aligned");
-    void *d_scratch = nullptr;
-    if (ls) {
-        void *p = nullptr;
-        const size_t walk_ints = (size_t)chunk * (4 + (size_t)ls->cap + stack_ints);
-        fail_point();
-        if ((rc = cx.reserve(CallCtx::SMALL, b_scratch + (4 * cells + walk_ints) * sizeof(int32_t), &p))) return rc;
-        if (b_scratch) d_scratch = p;
-        d_next0 = (int32_t *)((char *)p + b_scratch);
-        plog.last = d_next0 + cells;
-        plog.at_col = plog.last + cells;
-        plog.at_row = plog.at_col + cells;
-        d_walk = plog.at_row + cells;
-        FWX_HIP(hipMemcpyAsync(d_next0, d_next, b_idx, hipMemcpyDeviceToDevice, s));
-    }
-
-    if (to_large) {
-        if (!ls) {
-            fail_point();
-            if (b_scratch && (rc = cx.reserve(CallCtx::SMALL, b_scratch, &d_scratch))) return rc;
-        }
-        rc = dev_solve_batch_large<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
-                                      op.k_begin, op.k_end, (unsigned long long *)d_upd, d_scratch, b_scratch, s, plog);
-    } else if (ragged && mid)
-        rc = dev_solve_ragged_mid<T>(count, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, d_n_each, d_offset,
-                                     d_order, tiers, (unsigned long long *)d_upd, s, plog);
-    else if (ragged)
-        rc = dev_solve_ragged<T>(count, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, d_n_each, d_offset, d_order,
-                                 tiers, (unsigned long long *)d_upd, s, plog);
-    else
-        rc = dev_solve_batch<T>(count, n, (T *)d_rate, (int32_t *)d_next, (int32_t *)d_hops, (int64_t)n * n,
-                                op.k_begin, op.k_end, (unsigned long long *)d_upd, s, plog, mid);
-    if (rc) return rc;
-
-    FWX_HIP(hipMemcpyAsync(staged ? (void *)st_rate : (void *)rate, d_rate, b_rate, hipMemcpyDeviceToHost, s));
-    if (next) FWX_HIP(hipMemcpyAsync(staged ? (void *)st_next : (void *)next, d_next, b_idx, hipMemcpyDeviceToHost, s));
-    if (hops) FWX_HIP(hipMemcpyAsync(staged ? (void *)st_hops : (void *)hops, d_hops, b_idx, hipMemcpyDeviceToHost, s));
-    if (counting)
-        FWX_HIP(hipMemcpyAsync(h_upd.data(), d_upd, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    for (long long q0 = 0; ls && q0 < ls->items; q0 += chunk) {
-        const size_t c = (size_t)std::min<long long>(chunk, ls->items - q0), cap = (size_t)ls->cap;
-        int32_t *d_mat = d_walk, *d_src = d_mat + c, *d_dst = d_src + c, *d_len = d_dst + c, *d_paths = d_len + c,
-                *d_stacks = d_paths + c * cap;
-        FWX_HIP(hipMemcpyAsync(d_mat, ls->mat + q0, c * 4, hipMemcpyHostToDevice, s));
-        FWX_HIP(hipMemcpyAsync(d_src, ls->src + q0, c * 4, hipMemcpyHostToDevice, s));
-        FWX_HIP(hipMemcpyAsync(d_dst, ls->dst + q0, c * 4, hipMemcpyHostToDevice, s));
-        if (ragged)
-            rc = fwxi::launch_exact_ragged(count, d_n_each, d_offset, n, d_next0, plog, (int)c, d_mat, d_src, d_dst,
-                                           d_len, d_paths, ls->cap, d_stacks, s);
-        else
-            rc = fwxi::launch_exact_batch(count, n, (long long)n * n, d_next0, plog, (int)c, d_mat, d_src, d_dst,
-                                          d_len, d_paths, ls->cap, d_stacks, s);
-        if (rc) return rc;
-        FWX_HIP(hipMemcpyAsync(ls->len_out + q0, d_len, c * 4, hipMemcpyDeviceToHost, s));
-        FWX_HIP(hipMemcpyAsync(ls->path_out + (size_t)q0 * cap, d_paths, c * cap * 4, hipMemcpyDeviceToHost, s));
-    }
-    FWX_HIP(hipStreamSynchronize(s));
-    if (staged) {
-        memcpy(rate, st_rate, b_rate);
-        if (next) memcpy(next, st_next, b_idx);
-        if (hops) memcpy(hops, st_hops, b_idx);
-    }
-    if (counting) {
-        uint64_t sum = 0;
-        for (int32_t b = 0; b < count; ++b) {
-            sum += h_upd[(size_t)b];
-            if (updates_each) updates_each[b] = h_upd[(size_t)b];
-        }
-        if (op.updates_out) *op.updates_out = sum;
     }
     return FWX_OK;
 }
@@ -1394,535 +1075,6 @@ int fwx_solve_f64(int32_t n, double *rate, int32_t *next, int32_t *hops, const f
 int fwx_solve_f32(int32_t n, float *rate, int32_t *next, int32_t *hops, const fwx_opts *opts)
 {
     return fwxi::guarded([&]() -> int { return solve_host<float>(n, rate, next, hops, opts); });
-}
-
-int fwx_solve_batch_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
-                        uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts);
-    });
-}
-
-int fwx_solve_batch_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
-                        uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts);
-    });
-}
-
-int fwx_dev_solve_batch(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                        int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
-                        void *stream)
-{
-    return fwxi::guarded([&]() -> int {
-        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
-        if (count == 0 || n == 0) return FWX_OK;
-        if (!rate || (hops && !next) || stride < (int64_t)n * n) return FWX_ERR_INVALID;
-        const int rc = batch_range(n, k_begin, k_end);
-        if (rc) return rc;
-        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
-        hipStream_t s = (hipStream_t)stream;
-        if (dtype == FWX_F64)
-            return dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, k_begin, k_end,
-                                           d_updates_each, s);
-        return dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, k_begin, k_end,
-                                      d_updates_each, s);
-    });
-}
-
-int fwx_test_batch_wave_max_n(void) { return batch_wave_max_n(); }
-
-int fwx_solve_batch_mid_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
-                            uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, nullptr, false, nullptr, true);
-    });
-}
-
-int fwx_solve_batch_mid_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
-                            uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, nullptr, false, nullptr, true);
-    });
-}
-
-int fwx_dev_solve_batch_mid(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                            int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
-                            void *stream)
-{
-    return fwxi::guarded([&]() -> int {
-        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
-        if (count == 0 || n == 0) return FWX_OK;
-        if (!rate || (hops && !next) || stride < (int64_t)n * n) return FWX_ERR_INVALID;
-        const int rc = batch_range(n, k_begin, k_end, FWX_BATCH_MID_MAX_N);
-        if (rc) return rc;
-        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
-        hipStream_t s = (hipStream_t)stream;
-        if (dtype == FWX_F64)
-            return dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, k_begin, k_end,
-                                           d_updates_each, s, fwx::PathLog(), true);
-        return dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, k_begin, k_end,
-                                      d_updates_each, s, fwx::PathLog(), true);
-    });
-}
-
-static_assert(FWX_BATCH_MID_MAX_N == FWX_MID_N, "fwx.h states the largest order of the mid tier");
-
-int fwx_test_batch_mid_min_n(void) { return batch_mid_min_n(); }
-
-int fwx_test_batch_mid_block(void) { return FWX_MID_B; }
-
-int fwx_solve_batch_large_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
-                              uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, nullptr, false, nullptr, true,
-                                        true);
-    });
-}
-
-int fwx_solve_batch_large_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
-                              uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, nullptr, false, nullptr, true,
-                                       true);
-    });
-}
-
-int fwx_dev_solve_batch_large(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                              int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
-                              void *scratch, size_t scratch_bytes, void *stream)
-{
-    return fwxi::guarded([&]() -> int {
-        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
-        if (count == 0 || n == 0) return FWX_OK;
-        if (!rate || (hops && !next) || stride < (int64_t)n * n) return FWX_ERR_INVALID;
-        const int rc = batch_range(n, k_begin, k_end, FWX_BATCH_LARGE_MAX_N);
-        if (rc) return rc;
-        const bool to_large = n >= batch_large_min_n();
-        // the scratch is judged only where it is used: a call routed to the large tier with pivots to apply
-        if (to_large && k_end > k_begin &&
-            (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n)))
-            return FWX_ERR_INVALID;
-        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
-        hipStream_t s = (hipStream_t)stream;
-        if (dtype == FWX_F64)
-            return to_large ? dev_solve_batch_large<double>(count, n, (double *)rate, next, hops, stride, k_begin, k_end,
-                                                            d_updates_each, scratch, scratch_bytes, s)
-                            : dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, k_begin, k_end,
-                                                      d_updates_each, s, fwx::PathLog(), true);
-        return to_large ? dev_solve_batch_large<float>(count, n, (float *)rate, next, hops, stride, k_begin, k_end,
-                                                       d_updates_each, scratch, scratch_bytes, s)
-                        : dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, k_begin, k_end,
-                                                 d_updates_each, s, fwx::PathLog(), true);
-    });
-}
-
-static_assert(FWX_BATCH_LARGE_MAX_N <= FWX_LARGE_N, "fwx.h states no order the large tier cannot take");
-static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1000) == FWX_LARGE_SCRATCH_BYTES(1000) &&
-                  FWX_BATCH_LARGE_SCRATCH_BYTES(1) == FWX_LARGE_SCRATCH_BYTES(1),
-              "fwx.h states the scratch the large tier lays out");
-
-int fwx_test_batch_large_min_n(void) { return batch_large_min_n(); }
-
-int fwx_test_batch_large_geometry(int32_t out[4])
-{
-    if (!out) return FWX_ERR_INVALID;
-    out[0] = FWX_LARGE_B;
-    out[1] = FWX_LARGE_S;
-    out[2] = FWX_LARGE_TR;
-    out[3] = FWX_LARGE_TC;
-    return FWX_OK;
-}
-
-// fwx_dev_solve_batch_traced (max_n = FWX_BATCH_MAX_N), fwx_dev_solve_batch_mid_traced (FWX_BATCH_MID_MAX_N, mid) and
-// fwx_dev_solve_batch_large_traced (FWX_BATCH_LARGE_MAX_N, mid and large): one contract, the limit apart.  large: orders
-// from FWX_BATCH_LARGE_MIN_N up run the large tier on `scratch`, which is judged there and only there, as
-// fwx_dev_solve_batch_large judges it (the range is whole, so never empty).
-static int dev_solve_batch_traced_any(int32_t max_n, bool mid, int32_t count, int32_t n, int32_t dtype, void *rate,
-                                      int32_t *next, int32_t *hops, int64_t stride, const fwx_trace *trace,
-                                      unsigned long long *d_updates_each, void *stream, bool large = false,
-                                      void *scratch = nullptr, size_t scratch_bytes = 0)
-{
-    return fwxi::guarded([&]() -> int {
-        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
-        if (count == 0 || n == 0) return FWX_OK;
-        if (!rate || !next || !trace || !trace->last || !trace->at_col || !trace->at_row ||
-            stride < (int64_t)n * n)
-            return FWX_ERR_INVALID;
-        if (n > max_n) return FWX_ERR_UNSUPPORTED;
-        const bool to_large = large && n >= batch_large_min_n();
-        if (to_large &&
-            (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n)))
-            return FWX_ERR_INVALID;
-        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
-        fwx::PathLog plog;
-        plog.last = trace->last;
-        plog.at_col = trace->at_col;
-        plog.at_row = trace->at_row;
-        hipStream_t s = (hipStream_t)stream;
-        if (dtype == FWX_F64)
-            return to_large ? dev_solve_batch_large<double>(count, n, (double *)rate, next, hops, stride, 0, n,
-                                                            d_updates_each, scratch, scratch_bytes, s, plog)
-                            : dev_solve_batch<double>(count, n, (double *)rate, next, hops, stride, 0, n,
-                                                      d_updates_each, s, plog, mid);
-        return to_large ? dev_solve_batch_large<float>(count, n, (float *)rate, next, hops, stride, 0, n, d_updates_each,
-                                                       scratch, scratch_bytes, s, plog)
-                        : dev_solve_batch<float>(count, n, (float *)rate, next, hops, stride, 0, n, d_updates_each, s,
-                                                 plog, mid);
-    });
-}
-
-int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                               int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
-                               void *stream)
-{
-    return dev_solve_batch_traced_any(FWX_BATCH_MAX_N, false, count, n, dtype, rate, next, hops, stride, trace,
-                                      d_updates_each, stream);
-}
-
-int fwx_dev_solve_batch_mid_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                                   int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
-                                   void *stream)
-{
-    return dev_solve_batch_traced_any(FWX_BATCH_MID_MAX_N, true, count, n, dtype, rate, next, hops, stride, trace,
-                                      d_updates_each, stream);
-}
-
-int fwx_dev_solve_batch_large_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                                     int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
-                                     void *scratch, size_t scratch_bytes, void *stream)
-{
-    return dev_solve_batch_traced_any(FWX_BATCH_LARGE_MAX_N, true, count, n, dtype, rate, next, hops, stride, trace,
-                                      d_updates_each, stream, true, scratch, scratch_bytes);
-}
-
-// fwx_dev_exact_paths_batch, fwx_dev_exact_paths_batch_mid and fwx_dev_exact_paths_batch_large: one walk, the limit
-// apart.
-static int dev_exact_paths_batch_any(int32_t max_n, int32_t count, int32_t n, int64_t stride, const int32_t *next0,
-                                     const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
-                                     const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                     int32_t *scratch, void *stream)
-{
-    return fwxi::guarded([&]() -> int {
-        if (count < 0 || n < 0 || items < 0) return FWX_ERR_INVALID;
-        if (count == 0 || n == 0 || items == 0) return FWX_OK;
-        if (!next0 || !trace || !trace->last || !trace->at_col || !trace->at_row || stride < (int64_t)n * n ||
-            cap < 1 || !mat || !src || !dst || !len_out || !path_out || !scratch)
-            return FWX_ERR_INVALID;
-        if (n > max_n) return FWX_ERR_UNSUPPORTED;
-        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
-        fwx::PathLog plog;
-        plog.last = trace->last;
-        plog.at_col = trace->at_col;
-        plog.at_row = trace->at_row;
-        return launch_exact_batch(count, n, (long long)stride, next0, plog, items, mat, src, dst, len_out, path_out,
-                                  cap, scratch, (hipStream_t)stream);
-    });
-}
-
-int fwx_dev_exact_paths_batch(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
-                              const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
-                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                              int32_t *scratch, void *stream)
-{
-    return dev_exact_paths_batch_any(FWX_BATCH_MAX_N, count, n, stride, next0, trace, items, mat, src, dst, len_out,
-                                     path_out, cap, scratch, stream);
-}
-
-int fwx_dev_exact_paths_batch_mid(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
-                                  const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
-                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                  int32_t *scratch, void *stream)
-{
-    return dev_exact_paths_batch_any(FWX_BATCH_MID_MAX_N, count, n, stride, next0, trace, items, mat, src, dst,
-                                     len_out, path_out, cap, scratch, stream);
-}
-
-int fwx_dev_exact_paths_batch_large(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
-                                    const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
-                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                    int32_t *scratch, void *stream)
-{
-    return dev_exact_paths_batch_any(FWX_BATCH_LARGE_MAX_N, count, n, stride, next0, trace, items, mat, src, dst,
-                                     len_out, path_out, cap, scratch, stream);
-}
-
-int fwx_solve_batch_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
-                              uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                              const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, &ls);
-    });
-}
-
-int fwx_solve_batch_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
-                              uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                              const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, &ls);
-    });
-}
-
-int fwx_solve_batch_mid_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
-                                  uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                  const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true);
-    });
-}
-
-int fwx_solve_batch_mid_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
-                                  uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                  const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true);
-    });
-}
-
-int fwx_solve_batch_large_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
-                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                    const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<double>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true, true);
-    });
-}
-
-int fwx_solve_batch_large_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
-                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                    const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<float>(count, n, rate, next, hops, updates_each, opts, &ls, false, nullptr, true, true);
-    });
-}
-
-int64_t fwx_test_batch_lists_chunk(int32_t n, int32_t cap)
-{
-    return n < 0 || cap < 1 ? (int64_t)FWX_ERR_INVALID : (int64_t)batch_lists_chunk(n, cap);
-}
-
-int fwx_ragged_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
-                    int32_t tier_count_out[3])
-{
-    return fwxi::guarded([&]() -> int {
-        int32_t n_max = 0;
-        if (count < 0 || (count > 0 && !n_each) || ragged_orders(count, n_each, n_max)) return FWX_ERR_INVALID;
-        if (n_max > FWX_BATCH_MAX_N) return FWX_ERR_UNSUPPORTED;
-        ragged_plan(count, n_each, batch_wave_max_n(), 3, 0, offset_out, order_out, tier_count_out);
-        return FWX_OK;
-    });
-}
-
-int fwx_solve_ragged_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
-                         uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<double>(count, 0, rate, next, hops, updates_each, opts, nullptr, true, n_each);
-    });
-}
-
-int fwx_solve_ragged_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
-                         uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<float>(count, 0, rate, next, hops, updates_each, opts, nullptr, true, n_each);
-    });
-}
-
-int fwx_solve_ragged_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
-                               uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                               const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                               const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<double>(count, 0, rate, next, hops, updates_each, opts, &ls, true, n_each);
-    });
-}
-
-int fwx_solve_ragged_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
-                               uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                               const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                               const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<float>(count, 0, rate, next, hops, updates_each, opts, &ls, true, n_each);
-    });
-}
-
-// The device forms cannot read the orders: what they can decide is decided from the host arguments, and the kernels
-// leave a matrix alone whose order does not fit the tier it is listed in.  fwx_dev_solve_ragged (ntiers = 3) and
-// fwx_dev_solve_ragged_mid (ntiers = 4): one contract, the number of tiers apart.
-static int dev_solve_ragged_any(int ntiers, int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                                const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
-                                const int32_t *tier_count, const fwx_trace *trace,
-                                unsigned long long *d_updates_each, void *stream)
-{
-    return fwxi::guarded([&]() -> int {
-        if (count < 0 || !tier_count || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
-        int64_t listed = 0;
-        for (int t = 0; t < ntiers; ++t) {
-            if (tier_count[t] < 0) return FWX_ERR_INVALID;
-            listed += tier_count[t];
-        }
-        if (listed > count) return FWX_ERR_INVALID;
-        if (listed == 0) return FWX_OK;
-        if (!rate || !d_n_each || !d_offset || !d_order || (hops && !next)) return FWX_ERR_INVALID;
-        if (trace && (!next || !trace->last || !trace->at_col || !trace->at_row)) return FWX_ERR_INVALID;
-        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
-        fwx::PathLog plog;
-        if (trace) {
-            plog.last = trace->last;
-            plog.at_col = trace->at_col;
-            plog.at_row = trace->at_row;
-        }
-        hipStream_t s = (hipStream_t)stream;
-        if (ntiers == 4) {
-            if (dtype == FWX_F64)
-                return dev_solve_ragged_mid<double>(count, (double *)rate, next, hops, d_n_each, d_offset, d_order,
-                                                    tier_count, d_updates_each, s, plog);
-            return dev_solve_ragged_mid<float>(count, (float *)rate, next, hops, d_n_each, d_offset, d_order,
-                                               tier_count, d_updates_each, s, plog);
-        }
-        if (dtype == FWX_F64)
-            return dev_solve_ragged<double>(count, (double *)rate, next, hops, d_n_each, d_offset, d_order, tier_count,
-                                            d_updates_each, s, plog);
-        return dev_solve_ragged<float>(count, (float *)rate, next, hops, d_n_each, d_offset, d_order, tier_count,
-                                       d_updates_each, s, plog);
-    });
-}
-
-int fwx_dev_solve_ragged(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                         const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
-                         const int32_t tier_count[3], const fwx_trace *trace, unsigned long long *d_updates_each,
-                         void *stream)
-{
-    return dev_solve_ragged_any(3, count, dtype, rate, next, hops, d_n_each, d_offset, d_order, tier_count, trace,
-                                d_updates_each, stream);
-}
-
-int fwx_dev_solve_ragged_mid(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
-                             const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
-                             const int32_t tier_count[4], const fwx_trace *trace,
-                             unsigned long long *d_updates_each, void *stream)
-{
-    return dev_solve_ragged_any(4, count, dtype, rate, next, hops, d_n_each, d_offset, d_order, tier_count, trace,
-                                d_updates_each, stream);
-}
-
-// fwx_dev_exact_paths_ragged and fwx_dev_exact_paths_ragged_mid: one walk, the limit apart.
-static int dev_exact_paths_ragged_any(int32_t max_n, int32_t count, const int32_t *d_n_each, const int64_t *d_offset,
-                                      int32_t n_max, const int32_t *next0, const fwx_trace *trace, int32_t items,
-                                      const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
-                                      int32_t *path_out, int32_t cap, int32_t *scratch, void *stream)
-{
-    return fwxi::guarded([&]() -> int {
-        if (count < 0 || n_max < 0 || items < 0) return FWX_ERR_INVALID;
-        if (count == 0 || n_max == 0 || items == 0) return FWX_OK;
-        if (!d_n_each || !d_offset || !next0 || !trace || !trace->last || !trace->at_col || !trace->at_row ||
-            cap < 1 || !mat || !src || !dst || !len_out || !path_out || !scratch)
-            return FWX_ERR_INVALID;
-        if (n_max > max_n) return FWX_ERR_UNSUPPORTED;
-        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
-        fwx::PathLog plog;
-        plog.last = trace->last;
-        plog.at_col = trace->at_col;
-        plog.at_row = trace->at_row;
-        return launch_exact_ragged(count, d_n_each, d_offset, n_max, next0, plog, items, mat, src, dst, len_out,
-                                   path_out, cap, scratch, (hipStream_t)stream);
-    });
-}
-
-int fwx_dev_exact_paths_ragged(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
-                               const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
-                               const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
-                               int32_t cap, int32_t *scratch, void *stream)
-{
-    return dev_exact_paths_ragged_any(FWX_BATCH_MAX_N, count, d_n_each, d_offset, n_max, next0, trace, items, mat, src,
-                                      dst, len_out, path_out, cap, scratch, stream);
-}
-
-int fwx_dev_exact_paths_ragged_mid(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
-                                   const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
-                                   const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
-                                   int32_t cap, int32_t *scratch, void *stream)
-{
-    return dev_exact_paths_ragged_any(FWX_BATCH_MID_MAX_N, count, d_n_each, d_offset, n_max, next0, trace, items, mat,
-                                      src, dst, len_out, path_out, cap, scratch, stream);
-}
-
-int fwx_ragged_mid_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
-                        int32_t tier_count_out[4])
-{
-    return fwxi::guarded([&]() -> int {
-        int32_t n_max = 0;
-        if (count < 0 || (count > 0 && !n_each) || ragged_orders(count, n_each, n_max)) return FWX_ERR_INVALID;
-        if (n_max > FWX_BATCH_MID_MAX_N) return FWX_ERR_UNSUPPORTED;
-        ragged_plan(count, n_each, batch_wave_max_n(), 4, batch_mid_min_n(), offset_out, order_out, tier_count_out);
-        return FWX_OK;
-    });
-}
-
-int fwx_solve_ragged_mid_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
-                             uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<double>(count, 0, rate, next, hops, updates_each, opts, nullptr, true, n_each, true);
-    });
-}
-
-int fwx_solve_ragged_mid_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
-                             uint64_t *updates_each, const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        return solve_batch_host<float>(count, 0, rate, next, hops, updates_each, opts, nullptr, true, n_each, true);
-    });
-}
-
-int fwx_solve_ragged_mid_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
-                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                   const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<double>(count, 0, rate, next, hops, updates_each, opts, &ls, true, n_each, true);
-    });
-}
-
-int fwx_solve_ragged_mid_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
-                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
-                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
-                                   const fwx_opts *opts)
-{
-    return fwxi::guarded([&]() -> int {
-        const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
-        return solve_batch_host<float>(count, 0, rate, next, hops, updates_each, opts, &ls, true, n_each, true);
-    });
 }
 
 int fwx_follow_path(int32_t n, const int32_t *next, int32_t src, int32_t dst, int32_t *out,

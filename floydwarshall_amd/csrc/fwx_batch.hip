@@ -1,0 +1,843 @@
+// fwx_batch.hip -- the batched solves of the C ABI (include/fwx.h): fwx_solve_batch_* / fwx_solve_ragged_* with
+// their _mid, _large and _lists forms, the device forms fwx_dev_solve_batch* / fwx_dev_solve_ragged* /
+// fwx_dev_exact_paths_*, the ragged plans and the fwx_test_batch_* hooks.  Host code only: the kernels and their
+// launchers are fwx_kernels.hip, fwx_mid.hip and fwx_large.hip, the exact walk (launch_exact_batch,
+// launch_exact_ragged; fwx_query.h) is fwx_api.hip, which the handles share it with.
+//
+// A family of entry points is one BatchFamily value; every contract has one body that takes it:
+//   dev_solve_uniform      fwx_dev_solve_batch{,_mid,_large}{,_traced}
+//   dev_solve_ragged       fwx_dev_solve_ragged{,_mid}
+//   dev_exact_paths_batch  fwx_dev_exact_paths_batch{,_mid,_large}
+//   dev_exact_paths_ragged fwx_dev_exact_paths_ragged{,_mid}
+//   solve_batch_host       every host form
+// and the tier of an order is decided in one place, BatchFamily::tier, which run_uniform acts on.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "fwx.h"
+#include "fwx_guard.h"
+#include "fwx_internal.h"
+#include "fwx_kernels.h"
+#include "fwx_query.h"
+
+using namespace fwxi;
+
+static_assert(FWX_BATCH_MID_MAX_N == FWX_MID_N, "fwx.h states the largest order of the mid tier");
+static_assert(FWX_BATCH_LARGE_MAX_N <= FWX_LARGE_N, "fwx.h states no order the large tier cannot take");
+static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1000) == FWX_LARGE_SCRATCH_BYTES(1000) &&
+                  FWX_BATCH_LARGE_SCRATCH_BYTES(1) == FWX_LARGE_SCRATCH_BYTES(1),
+              "fwx.h states the scratch the large tier lays out");
+
+namespace {
+
+enum Tier { TIER_SMALL, TIER_MID, TIER_LARGE };
+
+// One family of entry points: the largest order it takes, the tiers it may route to beyond the small ones (the
+// wave and workgroup tiers of fwx_kernels.hip, which every family has) and the tiers of its ragged plan --
+// ragged_tiers == 0: the family has no ragged form.
+struct BatchFamily {
+    int32_t max_n;
+    bool mid, large;
+    int ragged_tiers;
+    // Where a uniform batch of order n runs: orders from FWX_BATCH_LARGE_MIN_N up the large tier, below it from
+    // FWX_BATCH_MID_MIN_N up the mid tier, the rest the small tiers -- the same bits wherever.
+    Tier tier(int32_t n) const
+    {
+        return large && n >= batch_large_min_n() ? TIER_LARGE : mid && n >= batch_mid_min_n() ? TIER_MID : TIER_SMALL;
+    }
+    // The large tier's scratch panels are used, and judged, only by a call routed there with pivots to apply.
+    bool needs_scratch(int32_t n, int32_t k_begin, int32_t k_end) const
+    {
+        return tier(n) == TIER_LARGE && k_end > k_begin;
+    }
+};
+constexpr BatchFamily kPlain = {FWX_BATCH_MAX_N, false, false, 3};
+constexpr BatchFamily kMid = {FWX_BATCH_MID_MAX_N, true, false, 4};
+constexpr BatchFamily kLarge = {FWX_BATCH_LARGE_MAX_N, true, true, 0};
+
+// body(rate as double * or float *), by the dtype code of a device form (checked by the caller).
+template <typename F> int with_dtype(int32_t dtype, void *rate, F &&body)
+{
+    return dtype == FWX_F64 ? body((double *)rate) : body((float *)rate);
+}
+
+bool trace_complete(const fwx_trace *t) { return t && t->last && t->at_col && t->at_row; }
+
+// A null trace: no trace.
+fwx::PathLog plog_of(const fwx_trace *t)
+{
+    fwx::PathLog plog{};
+    if (t) {
+        plog.last = t->last;
+        plog.at_col = t->at_col;
+        plog.at_row = t->at_row;
+    }
+    return plog;
+}
+
+bool large_scratch_ok(int32_t n, const void *scratch, size_t bytes)
+{
+    return scratch && !((uintptr_t)scratch & 15) && bytes >= FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n);
+}
+
+// What a launcher refuses (a trace without next or over a part of the pivots, scratch it cannot use) is the caller's
+// mistake.
+int launch_status(hipError_t e)
+{
+    if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
+    FWX_HIP(e);
+    return FWX_OK;
+}
+
+// What the batch entry points decide before any device call (fwx.h): the pivot range against n, then the
+// order against the family's limit.  k_end <= 0 means n.
+int batch_range(const BatchFamily &f, int32_t n, int32_t k_begin, int32_t &k_end)
+{
+    if (k_end <= 0) k_end = n;
+    if (k_begin < 0 || k_begin > k_end || k_end > n) return FWX_ERR_INVALID;
+    return n > f.max_n ? FWX_ERR_UNSUPPORTED : FWX_OK;
+}
+
+// `count` matrices of one order on the tier the family routes it to, queued on s.  The large tier runs groups of as
+// many matrices as the scratch holds, one after the other; plog: the path trace, whole pivot range only.
+template <typename T>
+int run_uniform(const BatchFamily &f, int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops, int64_t stride,
+                int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each, void *scratch, size_t scratch_bytes,
+                hipStream_t s, const fwx::PathLog &plog)
+{
+    switch (f.tier(n)) {
+    case TIER_LARGE:
+        return launch_status(fwx::launch_batch_large<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
+                                                        d_updates_each, scratch, scratch_bytes, s, plog));
+    case TIER_MID:
+        return launch_status(fwx::launch_batch_mid<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
+                                                      d_updates_each, s, plog));
+    default:
+        return launch_status(fwx::launch_batch_solve<T>(rate, next, hops, count, n, (long long)stride, k_begin, k_end,
+                                                        d_updates_each, batch_wave_max_n(), s, plog));
+    }
+}
+
+// A planned ragged batch, queued on s.  With four tiers the mid tier first -- its workgroups run longest -- then the
+// three small tiers.
+template <typename T>
+int run_ragged(int tiers, int32_t count, T *rate, int32_t *next, int32_t *hops, const int32_t *d_n_each,
+               const int64_t *d_offset, const int32_t *d_order, const int32_t *tier_count,
+               unsigned long long *d_updates_each, hipStream_t s, const fwx::PathLog &plog)
+{
+    if (tiers == 4) {
+        const long long small = (long long)tier_count[0] + tier_count[1] + tier_count[2];
+        const int rc = launch_status(fwx::launch_ragged_mid<T>(rate, next, hops, count, d_n_each, d_offset,
+                                                               d_order + small, tier_count[3], d_updates_each, s, plog));
+        if (rc || small == 0) return rc;
+    }
+    return launch_status(fwx::launch_ragged_solve<T>(rate, next, hops, count, d_n_each, d_offset, d_order, tier_count,
+                                                     d_updates_each, s, plog));
+}
+
+// Ragged batches: what the orders alone decide.  FWX_ERR_INVALID for a negative order; n_max is the largest
+// order, whatever it is -- the caller compares it with the family's limit.
+int ragged_orders(int32_t count, const int32_t *n_each, int32_t &n_max)
+{
+    n_max = 0;
+    for (int32_t b = 0; b < count; ++b) {
+        if (n_each[b] < 0) return FWX_ERR_INVALID;
+        n_max = std::max(n_max, n_each[b]);
+    }
+    return FWX_OK;
+}
+
+// The plan of a family's ragged form (fwx_ragged_plan: three tiers, fwx_ragged_mid_plan: four) for orders that
+// ragged_orders accepted and the family's limit admits: the packed offsets (count + 1 entries), the matrices with
+// n >= 1 grouped by tier -- wave (n <= FWX_BATCH_WAVE_MAX_N), 64-wide, 128-wide and, with four tiers, mid (n >=
+// FWX_BATCH_MID_MIN_N, which wins where the wave tier claims the order too) -- and within a tier by descending order,
+// ties by ascending index (a counting sort over the orders: the tier is monotone in the order), the rest of `order`
+// -1.  tier_count has f.ragged_tiers entries.  Any output may be null.
+void ragged_plan(const BatchFamily &f, int32_t count, const int32_t *n_each, int64_t *offset, int32_t *order,
+                 int32_t *tier_count)
+{
+    const int ntiers = f.ragged_tiers, wave_max_n = batch_wave_max_n(), mid_min_n = batch_mid_min_n();
+    auto tier_of = [&](int n) { return ntiers == 4 && n >= mid_min_n ? 3 : n <= wave_max_n ? 0 : n <= 64 ? 1 : 2; };
+    int64_t at[FWX_BATCH_MID_MAX_N + 2] = {0};  // at[n]: matrices of order n, then where the next one of order n goes
+    int32_t tiers[4] = {0, 0, 0, 0};
+    int64_t cells = 0;
+    for (int32_t b = 0; b < count; ++b) {
+        const int n = n_each[b];
+        if (offset) offset[b] = cells;
+        cells += (int64_t)n * n;
+        if (n >= 1) { ++at[n]; ++tiers[tier_of(n)]; }
+    }
+    if (offset) offset[count] = cells;
+    if (tier_count) std::copy(tiers, tiers + ntiers, tier_count);
+    if (!order) return;
+    int64_t pos = 0;
+    for (int tier = 0; tier < ntiers; ++tier)
+        for (int n = f.max_n; n >= 1; --n)
+            if (tier_of(n) == tier) { const int64_t c = at[n]; at[n] = pos; pos += c; }
+    for (int32_t b = 0; b < count; ++b)
+        if (n_each[b] >= 1) order[at[n_each[b]]++] = b;
+    for (int64_t i = pos; i < count; ++i) order[i] = -1;
+}
+
+// fwx_ragged_plan and fwx_ragged_mid_plan.
+int ragged_plan_checked(const BatchFamily &f, int32_t count, const int32_t *n_each, int64_t *offset_out,
+                        int32_t *order_out, int32_t *tier_count_out)
+{
+    return guarded([&]() -> int {
+        int32_t n_max = 0;
+        if (count < 0 || (count > 0 && !n_each) || ragged_orders(count, n_each, n_max)) return FWX_ERR_INVALID;
+        if (n_max > f.max_n) return FWX_ERR_UNSUPPORTED;
+        ragged_plan(f, count, n_each, offset_out, order_out, tier_count_out);
+        return FWX_OK;
+    });
+}
+
+// fwx_dev_solve_batch{,_mid,_large} (traced = false; trace, and scratch outside the large family, unused) and their
+// _traced forms (traced: next and a complete trace are required and the pivot range is whole, k_begin = 0 and k_end = n
+// from the entry point): one contract, the family apart.  The order of the checks is fwx.h's: the arguments and the
+// pivot range (FWX_ERR_INVALID), the order against the limit (FWX_ERR_UNSUPPORTED), the scratch where it is used
+// (FWX_ERR_INVALID), the device (FWX_ERR_NO_DEVICE).
+int dev_solve_uniform(const BatchFamily &f, int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next,
+                      int32_t *hops, int64_t stride, int32_t k_begin, int32_t k_end, bool traced, const fwx_trace *trace,
+                      unsigned long long *d_updates_each, void *scratch, size_t scratch_bytes, void *stream)
+{
+    return guarded([&]() -> int {
+        if (count < 0 || n < 0 || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
+        if (count == 0 || n == 0) return FWX_OK;
+        if (!rate || (hops && !next) || stride < (int64_t)n * n) return FWX_ERR_INVALID;
+        if (traced && (!next || !trace_complete(trace))) return FWX_ERR_INVALID;
+        const int rc = batch_range(f, n, k_begin, k_end);
+        if (rc) return rc;
+        if (f.needs_scratch(n, k_begin, k_end) && !large_scratch_ok(n, scratch, scratch_bytes)) return FWX_ERR_INVALID;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        return with_dtype(dtype, rate, [&](auto *r) {
+            return run_uniform(f, count, n, r, next, hops, stride, k_begin, k_end, d_updates_each, scratch, scratch_bytes,
+                               (hipStream_t)stream, plog_of(traced ? trace : nullptr));
+        });
+    });
+}
+
+// fwx_dev_solve_ragged and fwx_dev_solve_ragged_mid: one contract, the number of tiers apart.  The device forms cannot
+// read the orders: what they can decide is decided from the host arguments, and the kernels leave a matrix alone
+// whose order does not fit the tier it is listed in.
+int dev_solve_ragged(const BatchFamily &f, int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                     const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                     const int32_t *tier_count, const fwx_trace *trace, unsigned long long *d_updates_each,
+                     void *stream)
+{
+    return guarded([&]() -> int {
+        if (count < 0 || !tier_count || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
+        int64_t listed = 0;
+        for (int t = 0; t < f.ragged_tiers; ++t) {
+            if (tier_count[t] < 0) return FWX_ERR_INVALID;
+            listed += tier_count[t];
+        }
+        if (listed > count) return FWX_ERR_INVALID;
+        if (listed == 0) return FWX_OK;
+        if (!rate || !d_n_each || !d_offset || !d_order || (hops && !next)) return FWX_ERR_INVALID;
+        if (trace && (!next || !trace_complete(trace))) return FWX_ERR_INVALID;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        return with_dtype(dtype, rate, [&](auto *r) {
+            return run_ragged(f.ragged_tiers, count, r, next, hops, d_n_each, d_offset, d_order, tier_count,
+                              d_updates_each, (hipStream_t)stream, plog_of(trace));
+        });
+    });
+}
+
+// fwx_dev_exact_paths_batch{,_mid,_large}: one walk, the limit apart.
+int dev_exact_paths_batch(const BatchFamily &f, int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                          const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                          const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap, int32_t *scratch,
+                          void *stream)
+{
+    return guarded([&]() -> int {
+        if (count < 0 || n < 0 || items < 0) return FWX_ERR_INVALID;
+        if (count == 0 || n == 0 || items == 0) return FWX_OK;
+        if (!next0 || !trace_complete(trace) || stride < (int64_t)n * n || cap < 1 || !mat || !src || !dst ||
+            !len_out || !path_out || !scratch)
+            return FWX_ERR_INVALID;
+        if (n > f.max_n) return FWX_ERR_UNSUPPORTED;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        return launch_exact_batch(count, n, (long long)stride, next0, plog_of(trace), items, mat, src, dst, len_out,
+                                  path_out, cap, scratch, (hipStream_t)stream);
+    });
+}
+
+// fwx_dev_exact_paths_ragged{,_mid}: the same over a ragged batch, n_max against the limit.
+int dev_exact_paths_ragged(const BatchFamily &f, int32_t count, const int32_t *d_n_each, const int64_t *d_offset,
+                           int32_t n_max, const int32_t *next0, const fwx_trace *trace, int32_t items,
+                           const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
+                           int32_t *path_out, int32_t cap, int32_t *scratch, void *stream)
+{
+    return guarded([&]() -> int {
+        if (count < 0 || n_max < 0 || items < 0) return FWX_ERR_INVALID;
+        if (count == 0 || n_max == 0 || items == 0) return FWX_OK;
+        if (!d_n_each || !d_offset || !next0 || !trace_complete(trace) || cap < 1 || !mat || !src || !dst ||
+            !len_out || !path_out || !scratch)
+            return FWX_ERR_INVALID;
+        if (n_max > f.max_n) return FWX_ERR_UNSUPPORTED;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        return launch_exact_ragged(count, d_n_each, d_offset, n_max, next0, plog_of(trace), items, mat, src, dst,
+                                   len_out, path_out, cap, scratch, (hipStream_t)stream);
+    });
+}
+
+// What the _lists forms add to a batch solve: the exact lists of `items` triples, host arrays.
+struct BatchLists {
+    int32_t items;
+    const int32_t *mat, *src, *dst;
+    int32_t *len_out, *path_out;
+    int32_t cap;
+};
+
+// Which host form a call is: the family; ragged (fwx_solve_ragged_*: matrix b has order n_each[b] and the batch is
+// packed, matrix b at the sum of the squares before it; only families with ragged_tiers != 0); lists (null: none).
+struct HostForm {
+    BatchFamily family;
+    bool ragged;
+    const int32_t *n_each;
+    const BatchLists *lists;
+};
+
+constexpr size_t kBatchLargeScratchCap = (size_t)256 << 20;
+static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1) % 16 == 0, "what follows the scratch panels stays 16-byte aligned");
+
+// One call of a host form: `count` matrices from / to host arrays, pitch n, no padding (the batch kernels load
+// scalars), the arrays of the batch back to back on the device.  run() is the stages in order.  Every reservation of
+// the pooled context, each behind its fail_point(), lies in reserve_and_upload, and nothing of the caller's is
+// written before the last of them.
+template <typename T> struct HostCall {
+    const HostForm &form;
+    int32_t count, n;                  // ragged: n becomes the largest order (the walk's stacks and chunks go by it)
+    T *rate;
+    int32_t *next, *hops;
+    uint64_t *updates_each;
+    const BatchLists *const ls = form.lists;
+
+    Opts op{};
+    DeviceGuard g{};
+    CtxLease lease{};
+    hipStream_t s = nullptr;
+    size_t cells = 0;
+    // rate, next, hops (CallCtx::RATE + f): the caller's array (null: not given), its copy on the device and, while the
+    // whole batch fits the pinned staging (see solve_host), in there
+    struct Field { void *host; size_t bytes; void *dev; char *stage; } fld[3] = {};
+    bool staged = false;
+    // ragged: the plan, packed for one copy -- count offsets, then count orders and the tier list (count) as int32 --
+    // and where it lies in the context's workspace, behind the counters
+    std::vector<int64_t> plan{};
+    int32_t tiers[4] = {0, 0, 0, 0};
+    const int64_t *d_offset = nullptr;
+    const int32_t *d_n_each = nullptr, *d_order = nullptr;
+    bool counting = false;
+    std::vector<unsigned long long> h_upd{};
+    unsigned long long *d_upd = nullptr;
+    void *d_scratch = nullptr;
+    size_t b_scratch = 0;
+    // lists: the unsolved next-hops and the trace, then the walk's memory for one chunk of items
+    fwx::PathLog plog{};
+    int32_t *d_next0 = nullptr, *d_walk = nullptr;
+    long long chunk = 0;
+
+    // 1. What is decided before any device call, in fwx.h's order; FWX_OK with done set: nothing to do.
+    int validate(const fwx_opts *o, bool &done)
+    {
+        const bool ragged = form.ragged;
+        done = true;
+        if (count < 0 || (!ragged && n < 0) || (ls && ls->items < 0)) return FWX_ERR_INVALID;
+        if (count == 0 || (!ragged && n == 0)) return FWX_OK;
+        if (ragged) {
+            if (!form.n_each || ragged_orders(count, form.n_each, n)) return FWX_ERR_INVALID;
+            if (n == 0) return FWX_OK;
+        }
+        if (!rate || (hops && !next)) return FWX_ERR_INVALID;
+        if (ls && (!next || (ls->items > 0 && (ls->cap < 1 || !ls->mat || !ls->src || !ls->dst || !ls->len_out ||
+                                               !ls->path_out))))
+            return FWX_ERR_INVALID;
+        int rc = read_opts(o, n, op);
+        if (rc) return rc;
+        if (ls && (op.k_begin != 0 || op.k_end != n)) return FWX_ERR_INVALID;      // the trace covers whole solves only
+        if (ragged && o && (o->k_begin != 0 || o->k_end > 0)) return FWX_ERR_INVALID;   // one range does not fit all orders
+        if ((rc = batch_range(form.family, n, op.k_begin, op.k_end))) return rc;
+        if (op.engine != FWX_ENGINE_AUTO) return FWX_ERR_UNSUPPORTED;
+        done = false;
+        return FWX_OK;
+    }
+
+    // 2. The cells of the batch and, ragged, the plan.
+    void plan_batch()
+    {
+        cells = (size_t)count * (size_t)n * (size_t)n;
+        if (!form.ragged) return;
+        std::vector<int64_t> offs((size_t)count + 1);
+        plan.resize(2 * (size_t)count);
+        int32_t *h_n = (int32_t *)(plan.data() + count), *h_order = h_n + count;
+        ragged_plan(form.family, count, form.n_each, offs.data(), h_order, tiers);
+        std::copy(offs.begin(), offs.end() - 1, plan.begin());
+        std::copy(form.n_each, form.n_each + count, h_n);
+        cells = (size_t)offs[(size_t)count];
+    }
+
+    // 3. The context's buffers and the input on its way to them.
+    int reserve_and_upload()
+    {
+        int rc;
+        if ((rc = lease.open())) return rc;
+        CallCtx &cx = *lease.c;
+        if (op.has_stream) cx.uses_stream(op.stream);
+        s = op.has_stream ? op.stream : cx.s;
+        fld[0] = {rate, cells * sizeof(T), nullptr, nullptr};
+        fld[1] = {next, cells * sizeof(int32_t), nullptr, nullptr};
+        fld[2] = {hops, cells * sizeof(int32_t), nullptr, nullptr};
+        size_t b_total = 0;
+        for (int f = 0; f < 3; ++f) {                // a point for each of the three, given or not
+            fail_point();
+            if (!fld[f].host) continue;
+            if ((rc = cx.reserve(CallCtx::RATE + f, fld[f].bytes, &fld[f].dev))) return rc;
+            b_total += fld[f].bytes;
+        }
+        const size_t b_upd = counting ? (size_t)count * sizeof(unsigned long long) : 0;
+        if (counting || form.ragged) {               // one counter per matrix, then the plan: the context's workspace
+            fail_point();
+            void *ws = nullptr;
+            if ((rc = cx.reserve(CallCtx::WS, b_upd + plan.size() * sizeof(int64_t), &ws))) return rc;
+            if (counting) {
+                h_upd.resize((size_t)count);
+                d_upd = (unsigned long long *)ws;
+                FWX_HIP(hipMemsetAsync(d_upd, 0, b_upd, s));
+            }
+            if (form.ragged) {
+                d_offset = (const int64_t *)((char *)ws + b_upd);
+                d_n_each = (const int32_t *)(d_offset + count);
+                d_order = d_n_each + count;
+                FWX_HIP(hipMemcpyAsync((void *)d_offset, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            }
+        }
+        staged = b_total <= CallCtx::kStageBytes;    // straight copies above that
+        if (staged) {
+            void *pinned = nullptr;
+            fail_point();
+            if ((rc = cx.reserve_pinned(b_total, &pinned))) return rc;
+            char *at = (char *)pinned;
+            for (Field &a : fld)
+                if (a.host) { a.stage = at; at += a.bytes; memcpy(a.stage, a.host, a.bytes); }
+        }
+        for (const Field &a : fld)
+            if (a.host) FWX_HIP(hipMemcpyAsync(a.dev, staged ? a.stage : a.host, a.bytes, hipMemcpyHostToDevice, s));
+
+        // the context's SMALL buffer, ONE reservation: the large tier's scratch panels first -- at most
+        // kBatchLargeScratchCap, larger batches run in groups; the buffer's own alignment, and every matrix's part a
+        // multiple of 16 bytes -- then, with lists, the unsolved next-hops, the three trace arrays and the walk's
+        // memory for one chunk of items (triples and lengths, lists, stacks)
+        const size_t per_large = FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n);
+        if (form.family.needs_scratch(n, op.k_begin, op.k_end))
+            b_scratch = per_large * std::min<size_t>((size_t)count, std::max<size_t>(1, kBatchLargeScratchCap / per_large));
+        if (ls) {
+            void *p = nullptr;
+            chunk = std::min<long long>(batch_lists_chunk(n, ls->cap), ls->items);
+            const size_t walk_ints = (size_t)chunk * (4 + (size_t)ls->cap + FWX_EXACT_SCRATCH_INTS((size_t)n));
+            fail_point();
+            if ((rc = cx.reserve(CallCtx::SMALL, b_scratch + (4 * cells + walk_ints) * sizeof(int32_t), &p))) return rc;
+            if (b_scratch) d_scratch = p;
+            d_next0 = (int32_t *)((char *)p + b_scratch);
+            plog.last = d_next0 + cells;
+            plog.at_col = plog.last + cells;
+            plog.at_row = plog.at_col + cells;
+            d_walk = plog.at_row + cells;
+            FWX_HIP(hipMemcpyAsync(d_next0, fld[1].dev, fld[1].bytes, hipMemcpyDeviceToDevice, s));
+        } else if (form.family.tier(n) == TIER_LARGE) {     // a point of its own, scratch or none (an empty pivot range)
+            fail_point();
+            if (b_scratch && (rc = cx.reserve(CallCtx::SMALL, b_scratch, &d_scratch))) return rc;
+        }
+        return FWX_OK;
+    }
+
+    // 4. The solve, queued.
+    int solve()
+    {
+        T *r = (T *)fld[0].dev;
+        int32_t *x = (int32_t *)fld[1].dev, *h = (int32_t *)fld[2].dev;
+        if (form.ragged)
+            return run_ragged(form.family.ragged_tiers, count, r, x, h, d_n_each, d_offset, d_order, tiers, d_upd, s, plog);
+        return run_uniform(form.family, count, n, r, x, h, (int64_t)n * n, op.k_begin, op.k_end, d_upd, d_scratch,
+                           b_scratch, s, plog);
+    }
+
+    // 5. The results on their way back (queued before the walk, which reads none of them), then the lists,
+    //    batch_lists_chunk items per launch.
+    int download_and_walk()
+    {
+        for (const Field &a : fld)
+            if (a.host) FWX_HIP(hipMemcpyAsync(staged ? a.stage : a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, s));
+        if (counting)
+            FWX_HIP(hipMemcpyAsync(h_upd.data(), d_upd, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        for (long long q0 = 0; ls && q0 < ls->items; q0 += chunk) {
+            const size_t c = (size_t)std::min<long long>(chunk, ls->items - q0), cap = (size_t)ls->cap;
+            int32_t *d_mat = d_walk, *d_src = d_mat + c, *d_dst = d_src + c, *d_len = d_dst + c, *d_paths = d_len + c,
+                    *d_stacks = d_paths + c * cap;
+            FWX_HIP(hipMemcpyAsync(d_mat, ls->mat + q0, c * 4, hipMemcpyHostToDevice, s));
+            FWX_HIP(hipMemcpyAsync(d_src, ls->src + q0, c * 4, hipMemcpyHostToDevice, s));
+            FWX_HIP(hipMemcpyAsync(d_dst, ls->dst + q0, c * 4, hipMemcpyHostToDevice, s));
+            const int rc = form.ragged
+                ? launch_exact_ragged(count, d_n_each, d_offset, n, d_next0, plog, (int)c, d_mat, d_src, d_dst, d_len,
+                                      d_paths, ls->cap, d_stacks, s)
+                : launch_exact_batch(count, n, (long long)n * n, d_next0, plog, (int)c, d_mat, d_src, d_dst, d_len,
+                                     d_paths, ls->cap, d_stacks, s);
+            if (rc) return rc;
+            FWX_HIP(hipMemcpyAsync(ls->len_out + q0, d_len, c * 4, hipMemcpyDeviceToHost, s));
+            FWX_HIP(hipMemcpyAsync(ls->path_out + (size_t)q0 * cap, d_paths, c * cap * 4, hipMemcpyDeviceToHost, s));
+        }
+        return FWX_OK;
+    }
+
+    // 6. Everything has arrived: the caller's arrays out of the staging, the counters.
+    int finish()
+    {
+        FWX_HIP(hipStreamSynchronize(s));
+        for (const Field &a : fld)
+            if (staged && a.host) memcpy(a.host, a.stage, a.bytes);
+        uint64_t sum = 0;
+        for (int32_t b = 0; counting && b < count; ++b) {
+            sum += h_upd[(size_t)b];
+            if (updates_each) updates_each[b] = h_upd[(size_t)b];
+        }
+        if (op.updates_out) *op.updates_out = sum;
+        return FWX_OK;
+    }
+
+    int run(const fwx_opts *o)
+    {
+        bool done = false;
+        int rc = validate(o, done);
+        if (rc || done) return rc;
+        if ((rc = g.enter(op.device))) return rc;
+        plan_batch();
+        counting = updates_each || op.updates_out;
+        if ((rc = reserve_and_upload())) return rc;
+        if ((rc = solve())) return rc;
+        if ((rc = download_and_walk())) return rc;
+        return finish();
+    }
+};
+
+template <typename T>
+int solve_batch_host(const HostForm &form, int32_t count, int32_t n, T *rate, int32_t *next, int32_t *hops,
+                     uint64_t *updates_each, const fwx_opts *o)
+{
+    return guarded([&]() -> int { return HostCall<T>{form, count, n, rate, next, hops, updates_each}.run(o); });
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- uniform batches: host forms ----------------------------------------------------------------------------------
+
+int fwx_solve_batch_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                        uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<double>({kPlain, false, nullptr, nullptr}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                        uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<float>({kPlain, false, nullptr, nullptr}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_mid_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                            uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<double>({kMid, false, nullptr, nullptr}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_mid_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                            uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<float>({kMid, false, nullptr, nullptr}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_large_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<double>({kLarge, false, nullptr, nullptr}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_large_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<float>({kLarge, false, nullptr, nullptr}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<double>({kPlain, false, nullptr, &ls}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                              uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<float>({kPlain, false, nullptr, &ls}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_mid_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                                  uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                  const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<double>({kMid, false, nullptr, &ls}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_mid_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                                  uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                  const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<float>({kMid, false, nullptr, &ls}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_large_lists_f64(int32_t count, int32_t n, double *rate, int32_t *next, int32_t *hops,
+                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                    const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<double>({kLarge, false, nullptr, &ls}, count, n, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_batch_large_lists_f32(int32_t count, int32_t n, float *rate, int32_t *next, int32_t *hops,
+                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                    const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<float>({kLarge, false, nullptr, &ls}, count, n, rate, next, hops, updates_each, opts);
+}
+
+// ---- uniform batches: device forms --------------------------------------------------------------------------------
+
+int fwx_dev_solve_batch(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                        int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
+                        void *stream)
+{
+    return dev_solve_uniform(kPlain, count, n, dtype, rate, next, hops, stride, k_begin, k_end, false, nullptr,
+                             d_updates_each, nullptr, 0, stream);
+}
+
+int fwx_dev_solve_batch_mid(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                            int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
+                            void *stream)
+{
+    return dev_solve_uniform(kMid, count, n, dtype, rate, next, hops, stride, k_begin, k_end, false, nullptr,
+                             d_updates_each, nullptr, 0, stream);
+}
+
+int fwx_dev_solve_batch_large(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                              int64_t stride, int32_t k_begin, int32_t k_end, unsigned long long *d_updates_each,
+                              void *scratch, size_t scratch_bytes, void *stream)
+{
+    return dev_solve_uniform(kLarge, count, n, dtype, rate, next, hops, stride, k_begin, k_end, false, nullptr,
+                             d_updates_each, scratch, scratch_bytes, stream);
+}
+
+int fwx_dev_solve_batch_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                               int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
+                               void *stream)
+{
+    return dev_solve_uniform(kPlain, count, n, dtype, rate, next, hops, stride, 0, n, true, trace, d_updates_each,
+                             nullptr, 0, stream);
+}
+
+int fwx_dev_solve_batch_mid_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                                   int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
+                                   void *stream)
+{
+    return dev_solve_uniform(kMid, count, n, dtype, rate, next, hops, stride, 0, n, true, trace, d_updates_each,
+                             nullptr, 0, stream);
+}
+
+int fwx_dev_solve_batch_large_traced(int32_t count, int32_t n, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                                     int64_t stride, const fwx_trace *trace, unsigned long long *d_updates_each,
+                                     void *scratch, size_t scratch_bytes, void *stream)
+{
+    return dev_solve_uniform(kLarge, count, n, dtype, rate, next, hops, stride, 0, n, true, trace, d_updates_each,
+                             scratch, scratch_bytes, stream);
+}
+
+int fwx_dev_exact_paths_batch(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                              const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                              const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                              int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_batch(kPlain, count, n, stride, next0, trace, items, mat, src, dst, len_out, path_out, cap,
+                                 scratch, stream);
+}
+
+int fwx_dev_exact_paths_batch_mid(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                                  const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                                  const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                  int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_batch(kMid, count, n, stride, next0, trace, items, mat, src, dst, len_out, path_out, cap,
+                                 scratch, stream);
+}
+
+int fwx_dev_exact_paths_batch_large(int32_t count, int32_t n, int64_t stride, const int32_t *next0,
+                                    const fwx_trace *trace, int32_t items, const int32_t *mat, const int32_t *src,
+                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                    int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_batch(kLarge, count, n, stride, next0, trace, items, mat, src, dst, len_out, path_out, cap,
+                                 scratch, stream);
+}
+
+// ---- ragged batches -----------------------------------------------------------------------------------------------
+
+int fwx_ragged_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
+                    int32_t tier_count_out[3])
+{
+    return ragged_plan_checked(kPlain, count, n_each, offset_out, order_out, tier_count_out);
+}
+
+int fwx_ragged_mid_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
+                        int32_t tier_count_out[4])
+{
+    return ragged_plan_checked(kMid, count, n_each, offset_out, order_out, tier_count_out);
+}
+
+int fwx_solve_ragged_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                         uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<double>({kPlain, true, n_each, nullptr}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                         uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<float>({kPlain, true, n_each, nullptr}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_mid_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                             uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<double>({kMid, true, n_each, nullptr}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_mid_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                             uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<float>({kMid, true, n_each, nullptr}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                               const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                               const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<double>({kPlain, true, n_each, &ls}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                               const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                               const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<float>({kPlain, true, n_each, &ls}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_mid_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                   const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<double>({kMid, true, n_each, &ls}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_mid_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                                   uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                   const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                   const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<float>({kMid, true, n_each, &ls}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_dev_solve_ragged(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                         const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                         const int32_t tier_count[3], const fwx_trace *trace, unsigned long long *d_updates_each,
+                         void *stream)
+{
+    return dev_solve_ragged(kPlain, count, dtype, rate, next, hops, d_n_each, d_offset, d_order, tier_count, trace,
+                            d_updates_each, stream);
+}
+
+int fwx_dev_solve_ragged_mid(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                             const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                             const int32_t tier_count[4], const fwx_trace *trace,
+                             unsigned long long *d_updates_each, void *stream)
+{
+    return dev_solve_ragged(kMid, count, dtype, rate, next, hops, d_n_each, d_offset, d_order, tier_count, trace,
+                            d_updates_each, stream);
+}
+
+int fwx_dev_exact_paths_ragged(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                               const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
+                               const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                               int32_t cap, int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_ragged(kPlain, count, d_n_each, d_offset, n_max, next0, trace, items, mat, src, dst, len_out,
+                                  path_out, cap, scratch, stream);
+}
+
+int fwx_dev_exact_paths_ragged_mid(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                                   const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
+                                   const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                                   int32_t cap, int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_ragged(kMid, count, d_n_each, d_offset, n_max, next0, trace, items, mat, src, dst, len_out,
+                                  path_out, cap, scratch, stream);
+}
+
+// ---- test hooks ---------------------------------------------------------------------------------------------------
+
+int fwx_test_batch_wave_max_n(void) { return batch_wave_max_n(); }
+
+int fwx_test_batch_mid_min_n(void) { return batch_mid_min_n(); }
+
+int fwx_test_batch_mid_block(void) { return FWX_MID_B; }
+
+int fwx_test_batch_large_min_n(void) { return batch_large_min_n(); }
+
+int fwx_test_batch_large_geometry(int32_t out[4])
+{
+    if (!out) return FWX_ERR_INVALID;
+    out[0] = FWX_LARGE_B;
+    out[1] = FWX_LARGE_S;
+    out[2] = FWX_LARGE_TR;
+    out[3] = FWX_LARGE_TC;
+    return FWX_OK;
+}
+
+int64_t fwx_test_batch_lists_chunk(int32_t n, int32_t cap)
+{
+    return n < 0 || cap < 1 ? (int64_t)FWX_ERR_INVALID : (int64_t)batch_lists_chunk(n, cap);
+}
+
+}  // extern "C"

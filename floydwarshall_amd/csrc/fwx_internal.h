@@ -1,5 +1,6 @@
 // fwx_internal.h -- pieces shared by the translation units behind the C ABI (fwx_api.hip: one
-// device; fwx_multi.hip: the row-partitioned multi-device handle).  Not installed, not part of the ABI.
+// device; fwx_batch.hip: the batched solves; fwx_multi.hip: the row-partitioned multi-device handle).  Not
+// installed, not part of the ABI.
 #ifndef FWX_INTERNAL_H
 #define FWX_INTERNAL_H
 
@@ -9,7 +10,6 @@
 #include <new>
 #include <type_traits>
 #include <vector>
-#include <errno.h>
 #include <limits.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -471,6 +471,18 @@ inline int perk_store_bytes()
     return FWX_PERK_STORE_BYTES_DEFAULT;
 }
 
+// The digits-only environment switches, read on every call: the first character is a digit (no sign, no blank), the
+// whole string is consumed and the value lies in [lo, hi]; anything else, or unset, gives dflt.  A value too large
+// for strtoll saturates and fails the range.
+inline long long env_digits(const char *name, long long lo, long long hi, long long dflt)
+{
+    const char *e = getenv(name);
+    if (!e || *e < '0' || *e > '9') return dflt;
+    char *end = nullptr;
+    const long long v = strtoll(e, &end, 10);
+    return *end == '\0' && v >= lo && v <= hi ? v : dflt;
+}
+
 // Pivots per streaming pass of the per-k engine's rates-only whole-matrix solves (relax_kt):
 // FWX_PERK_PIVOTS=<1|2|4|8> overrides FWX_PERK_PIVOTS_DEFAULT, read on every call; any other value: the
 // default.  1 = one relax_k launch per pivot, launch for launch the engine before relax_kt existed.  No
@@ -530,17 +542,7 @@ inline bool perk_deep()
 // the remedy for inputs whose operands carry sign bits everywhere.  No result bit
 // depends on it.
 #define FWX_PERK_TILE_MIN_N_DEFAULT 1024
-inline int perk_tile_min_n()
-{
-    if (const char *e = getenv("FWX_PERK_TILE_MIN_N")) {
-        char *end = nullptr;
-        errno = 0;
-        const long v = strtol(e, &end, 10);
-        // digits only: no sign, no blank
-        if (*e >= '0' && *e <= '9' && *end == '\0' && errno == 0 && v >= 0 && v <= INT_MAX) return (int)v;
-    }
-    return FWX_PERK_TILE_MIN_N_DEFAULT;
-}
+inline int perk_tile_min_n() { return (int)env_digits("FWX_PERK_TILE_MIN_N", 0, INT_MAX, FWX_PERK_TILE_MIN_N_DEFAULT); }
 
 // The fold of relax_kt's non-counting f32 sweeps: FWX_PERK_FOLD=compare forces the compare form in every tile, read on
 // every call; anything else, or unset: automatic (each wave takes the max form where the operands it has loaded
@@ -559,13 +561,7 @@ inline bool perk_fold_compare()
 #define FWX_BATCH_WAVE_MAX_N_DEFAULT FWX_BATCH_WAVE_N
 inline int batch_wave_max_n()
 {
-    if (const char *e = getenv("FWX_BATCH_WAVE_MAX_N")) {
-        char *end = nullptr;
-        const long v = strtol(e, &end, 10);
-        // digits only: no sign, no blank
-        if (*e >= '0' && *e <= '9' && *end == '\0' && v >= 0 && v <= FWX_BATCH_WAVE_N) return (int)v;
-    }
-    return FWX_BATCH_WAVE_MAX_N_DEFAULT;
+    return (int)env_digits("FWX_BATCH_WAVE_MAX_N", 0, FWX_BATCH_WAVE_N, FWX_BATCH_WAVE_MAX_N_DEFAULT);
 }
 
 // Routing of the mid-size batch entry points (fwx_solve_batch_mid_*, fwx_dev_solve_batch_mid): orders below
@@ -577,13 +573,7 @@ inline int batch_wave_max_n()
 #define FWX_BATCH_MID_MIN_N_DEFAULT (FWX_BATCH_MAX_N + 1)
 inline int batch_mid_min_n()
 {
-    if (const char *e = getenv("FWX_BATCH_MID_MIN_N")) {
-        char *end = nullptr;
-        const long v = strtol(e, &end, 10);
-        // digits only: no sign, no blank
-        if (*e >= '0' && *e <= '9' && *end == '\0' && v >= 1 && v <= FWX_BATCH_MID_MIN_N_DEFAULT) return (int)v;
-    }
-    return FWX_BATCH_MID_MIN_N_DEFAULT;
+    return (int)env_digits("FWX_BATCH_MID_MIN_N", 1, FWX_BATCH_MID_MIN_N_DEFAULT, FWX_BATCH_MID_MIN_N_DEFAULT);
 }
 
 // Routing of the large batch entry points (fwx_solve_batch_large_*, fwx_dev_solve_batch_large): orders below
@@ -593,13 +583,7 @@ inline int batch_mid_min_n()
 #define FWX_BATCH_LARGE_MIN_N_DEFAULT (FWX_BATCH_MID_MAX_N + 1)
 inline int batch_large_min_n()
 {
-    if (const char *e = getenv("FWX_BATCH_LARGE_MIN_N")) {
-        char *end = nullptr;
-        const long v = strtol(e, &end, 10);
-        // digits only: no sign, no blank
-        if (*e >= '0' && *e <= '9' && *end == '\0' && v >= 1 && v <= FWX_BATCH_LARGE_MIN_N_DEFAULT) return (int)v;
-    }
-    return FWX_BATCH_LARGE_MIN_N_DEFAULT;
+    return (int)env_digits("FWX_BATCH_LARGE_MIN_N", 1, FWX_BATCH_LARGE_MIN_N_DEFAULT, FWX_BATCH_LARGE_MIN_N_DEFAULT);
 }
 
 // fwx_solve_batch_lists_*: items walked per launch.  The lists (cap int32 per item), the walk stacks
@@ -612,13 +596,7 @@ inline long long batch_lists_chunk(int n, int cap)
     const long long per_item = 4ll * ((long long)cap + 3ll * ((long long)n + 2) + 4);
     long long fit = FWX_BATCH_LISTS_BUDGET_BYTES / per_item;
     if (fit < 1) fit = 1;
-    if (const char *e = getenv("FWX_BATCH_LISTS_CHUNK")) {
-        char *end = nullptr;
-        errno = 0;
-        const long long v = strtoll(e, &end, 10);
-        if (*e >= '0' && *e <= '9' && *end == '\0' && errno == 0 && v >= 1 && v < fit) return v;
-    }
-    return fit;
+    return env_digits("FWX_BATCH_LISTS_CHUNK", 1, fit - 1, fit);
 }
 
 // Launches of the multi-pivot schedule by pivots per launch: [0] relax_k (ragged single pivots), [1] / [2] /

@@ -89,6 +89,7 @@ int run_follow(const EntryTab &tab, int n_real, hipStream_t s, int32_t *scratch,
 int run_exact_batch(const EntryTab &tab, int n_real, hipStream_t s, int32_t count, const int32_t *src,
                     const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap);
 
+// For the batched solves (fwx_batch.hip; defined in fwx_api.hip beside the walk they share with the handles).
 // The exact lists of `items` triples (mat, src, dst) of a traced batch, everything on the device, one launch on `s`,
 // nothing allocated or synchronised: len_out[q] = length or the error of item q, paths + q * cap its list;
 // stacks: items * 3 * (n + 2) ints.

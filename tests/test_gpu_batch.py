@@ -18,6 +18,7 @@ import pytest
 
 import oracle
 from floydwarshall_amd import _lib, engine, synth
+from oracle import list_ropes
 
 from helpers import assert_bits_equal, dev, host
 from hostile_inputs import hostile_matrix_mix
@@ -251,33 +252,101 @@ def test_allocation_failures_leave_the_arrays_alone(dtype, monkeypatch):
     counters has five: three device reservations, the host counters, the pinned staging): each returns FWX_ERR_OOM
     with the caller's arrays and counters untouched, and the next call works.  A countdown past the last point is
     not reached: that call succeeds."""
-    monkeypatch.delenv("FWX_BATCH_WAVE_MAX_N", raising=False)
-    name = np.dtype(dtype).name
-    n, count, points = 16, 5, 5
-    batch = _synth_batch(n, count, name)
-    want = _want(("synth", n, count, name), batch)
-    L = _lib.lib()
-    fn = L.fwx_solve_batch_f64 if dtype == np.float64 else L.fwx_solve_batch_f32
+    _walk_allocation_points("batch", dtype, monkeypatch)
 
-    def call(arrays, each, total):
+
+# Host form -> (orders of the batch, items, cap, allocation points).  The three other forms are the smallest batches
+# that reach a reservation the plain form has not: the lists' memory and the large tier's scratch panels (both the
+# context's small buffer) and the ragged plan (in the workspace, behind the counters).
+FAIL_FORMS = {
+    "batch": ((16,) * 5, 0, 0, 5),
+    "batch_lists": ((16,) * 5, 4, 16, 6),
+    "batch_large": ((257,) * 2, 0, 0, 5),
+    "ragged_mid_lists": ((3, 17, 130), 3, 130, 6),
+}
+LEN_SENTINEL, PATH_SENTINEL = -99, -7
+
+
+@functools.lru_cache(maxsize=None)
+def _fail_case(form, dtype_name):
+    """(input, oracle's answer, [U_b], items, their lists) of one form: matrix b is _synth_batch's (kind KINDS[b % 4],
+    seed BASE_SEED + 1000 + b) at its own order, the arrays packed back to back -- what a uniform batch is too.  Item
+    q asks matrix q for its longest list that fits cap, so every item has vertices to write."""
+    orders, items, cap, _ = FAIL_FORMS[form]
+    dtype = np.dtype(dtype_name).type
+    mats = [synth.make(KINDS[b % 4], n, dtype, seed=synth.BASE_SEED + 1000 + b) for b, n in enumerate(orders)]
+    done = [tuple(a.copy() for a in m) for m in mats]
+    us = [oracle.relax(*m) for m in done]
+    assert all(u > 0 for u, n in zip(us, orders) if n >= 4)
+    triples, lists = [], []
+    for q in range(items):
+        ropes = list_ropes.solve(mats[q][0], mats[q][1])
+        fits = np.where(ropes.lengths <= cap, ropes.lengths, 0)
+        i, j = (int(v) for v in np.unravel_index(np.argmax(fits), fits.shape))
+        assert fits[i, j] >= 1
+        triples.append((q, i, j))
+        lists.append(ropes.path(i, j))
+    pack = lambda ms: _frozen(*(np.concatenate([m[f].reshape(-1) for m in ms]) for f in range(3)))  # noqa: E731
+    return pack(mats), pack(done), us, triples, lists
+
+
+def _walk_allocation_points(form, dtype, monkeypatch):
+    for var in ("FWX_BATCH_WAVE_MAX_N", "FWX_BATCH_MID_MIN_N", "FWX_BATCH_LARGE_MIN_N", "FWX_BATCH_LISTS_CHUNK"):
+        monkeypatch.delenv(var, raising=False)
+    orders, items, cap, points = FAIL_FORMS[form]
+    count = len(orders)
+    batch, want, want_us, triples, lists = _fail_case(form, np.dtype(dtype).name)
+    L = _lib.lib()
+    fn = getattr(L, "fwx_solve_%s_%s" % (form, "f64" if dtype == np.float64 else "f32"))
+    n_each = np.array(orders, dtype=np.int32)
+    mat, src, dst = (np.ascontiguousarray([t[f] for t in triples], dtype=np.int32) for f in range(3))
+
+    def call(arrays, each, total, lens, paths):
         o = _lib.FwxOpts()
         o.struct_size, o.device = ctypes.sizeof(_lib.FwxOpts), -1
         o.updates_out = ctypes.pointer(total)
-        return fn(count, n, arrays[0].ctypes.data, arrays[1].ctypes.data, arrays[2].ctypes.data, each.ctypes.data,
+        head = (count, n_each.ctypes.data) if form.startswith("ragged") else (count, orders[0])
+        tail = (items, mat.ctypes.data, src.ctypes.data, dst.ctypes.data, lens.ctypes.data, paths.ctypes.data,
+                cap) if items else ()
+        return fn(*head, arrays[0].ctypes.data, arrays[1].ctypes.data, arrays[2].ctypes.data, each.ctypes.data, *tail,
                   ctypes.byref(o))
 
     for countdown in range(1, points + 2):
         arrays = [a.copy() for a in batch]
         each, total = np.full(count, 99, dtype=np.uint64), ctypes.c_uint64(99)
+        lens = np.full(max(items, 1), LEN_SENTINEL, dtype=np.int32)
+        paths = np.full((max(items, 1), max(cap, 1)), PATH_SENTINEL, dtype=np.int32)
         assert L.fwx_test_fail_after(countdown) == _lib.FWX_OK
-        rc = call(arrays, each, total)
+        rc = call(arrays, each, total, lens, paths)
         assert L.fwx_test_fail_after(0) == _lib.FWX_OK
         if countdown <= points:
             assert rc == _lib.FWX_ERR_OOM, (countdown, rc)
             for a, b, field in zip(arrays, batch, ("rate", "next", "hops")):
                 assert_bits_equal(a, b, "%s after a failure at allocation point %d" % (field, countdown))
             assert [int(u) for u in each] == [99] * count and total.value == 99
-            rc = call(arrays, each, total)                      # the next call works
+            assert (lens == LEN_SENTINEL).all() and (paths == PATH_SENTINEL).all(), countdown
+            rc = call(arrays, each, total, lens, paths)         # the next call works
         assert rc == _lib.FWX_OK, (countdown, rc)
-        _compare((arrays[0], arrays[1], arrays[2], [int(u) for u in each]), want, "after countdown %d" % countdown)
-        assert total.value == sum(want[3])
+        for a, w, field in zip(arrays, want, ("rate", "next", "hops")):
+            assert_bits_equal(a, w, "%s after countdown %d" % (field, countdown))
+        assert [int(u) for u in each] == want_us and total.value == sum(want_us)
+        for q, path in enumerate(lists):
+            assert int(lens[q]) == len(path) and tuple(paths[q, :len(path)].tolist()) == path, (countdown, q)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("form", ["batch_lists", "batch_large", "ragged_mid_lists"])
+def test_allocation_failures_in_the_other_host_forms(form, dtype, monkeypatch):
+    """The same walk through the host forms that reserve more than the plain one, each with next, hops, updates_each
+    and updates_out; len_out and path_out stay untouched too.  Allocation points counted on the library before the
+    batched family moved to fwx_batch.hip, and unchanged since:
+      fwx_solve_batch_lists_*       n = 16, count = 5, 4 items, cap = 16           6  the plain form's five and the
+                                                                                     lists' memory
+      fwx_solve_batch_large_*       n = 257, count = 2                             5  three arrays, the counters, the
+                                                                                     scratch panels; at 2 x 257^2 cells
+                                                                                     the arrays are past the staging
+                                                                                     limit, so no pinned staging
+      fwx_solve_ragged_mid_lists_*  orders (3, 17, 130), 3 items, cap = 130        6  three arrays, counters + plan,
+                                                                                     staging, the lists' memory
+    A countdown of points + 1 is not reached, which pins the counts from above as well."""
+    _walk_allocation_points(form, dtype, monkeypatch)
