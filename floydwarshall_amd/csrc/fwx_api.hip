@@ -1032,6 +1032,14 @@ int fwx_test_perk_tile(uint64_t *launches, int reset)
     return perk_tile_min_n();
 }
 
+int fwx_test_perk_pair(uint64_t *launches, int reset)
+{
+    const uint64_t v = reset ? g_perk_pair_launches.exchange(0, std::memory_order_relaxed)
+                             : g_perk_pair_launches.load(std::memory_order_relaxed);
+    if (launches) *launches = v;
+    return perk_pair_min_n();
+}
+
 int fwx_test_perk_wide(uint64_t *wide_launches, int reset)
 {
     const uint64_t v = reset ? g_perk_wide_launches.exchange(0, std::memory_order_relaxed)

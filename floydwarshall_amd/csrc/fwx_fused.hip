@@ -1193,6 +1193,12 @@ __global__ __launch_bounds__(256, MINW) void fused_main_max(float *rate, int row
 //
 // In place without a race: a tile reads only the two panels, which no tile writes, and its own
 // entries (the diagonal restore included), which no other tile touches.
+//
+// Round 29: the stage count is a run-time argument, ns = 4 (a block) or 8 (a pair of blocks whose panels are 128
+// contiguous rows of W and lines of Ct) -- the fold above over t = 0 .. 16 * ns - 1, nothing else changes: the NaN
+// patch's column index advances with every commit -- and (sel, tx) names the tiles of the launch (TileSel,
+// fwx_kernels.h): all, all but tile row and tile column tx, or only those two.  The pair schedule of relax_range_kt
+// (fwx_internal.h) runs the second beside a chain of the third on another stream; the two never touch the same tile.
 // ------------------------------------------------------------------------------------------------
 
 // One pivot pair of the compare-form fold on the register tile: pivot u = 0 on every entry, then u = 1
@@ -1239,19 +1245,38 @@ __device__ __forceinline__ int sign_bits(F32x4 v)
 
 template <int MINW, int RI, int NH>
 __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int k0, const float *w,
-                                                        const float *ct, int ct_ld, int force_cmp)
+                                                        const float *ct, int ct_ld, int force_cmp, int ns, int sel,
+                                                        int tx)
 {
     typedef float V4 __attribute__((ext_vector_type(4)));
-    constexpr int TI = 16 * RI, TJ = 64 * NH, HJ = 64, BS = 16, HP = BS / 2, NS = B / BS;
+    constexpr int TI = 16 * RI, TJ = 64 * NH, HJ = 64, BS = 16, HP = BS / 2;
     static_assert(TI == 128 && TJ == 128, "every thread stages both operands: 8 pivot pairs x 32 vectors");
 
     __shared__ __attribute__((aligned(16))) float sW[2][HP][2][TJ];
     __shared__ __attribute__((aligned(16))) float sC[2][HP][2][TI];
     __shared__ __attribute__((aligned(16))) int sVote[2][4];   // [stage parity][wave]: the wave staged a sign bit
 
+    // Which tile (workgroup-uniform).  TILES_ALL: the grid is the tile grid.  TILES_EXCEPT: a grid one tile shorter each
+    // way that steps over tile row tx and tile column tx.  TILES_CROSS: a one-dimensional grid of 2 * tiles - 1, tile
+    // row tx first, then the rest of tile column tx; a launch of the look-ahead chain beside a main launch.
+    int bx = blockIdx.x, by = blockIdx.y;
+    if (sel == TILES_EXCEPT) {
+        bx += bx >= tx ? 1 : 0;
+        by += by >= tx ? 1 : 0;
+    } else if (sel == TILES_CROSS) {
+        __builtin_amdgcn_s_setprio(2);
+        const int tiles = ((int)gridDim.x + 1) >> 1;
+        if (bx < tiles) {
+            by = tx;
+        } else {
+            by = bx - tiles;
+            by += by >= tx ? 1 : 0;
+            bx = tx;
+        }
+    }
     const int tid = threadIdx.x;
-    const int i_base = blockIdx.y * TI;
-    const int j_base = blockIdx.x * TJ;
+    const int i_base = by * TI;
+    const int j_base = bx * TJ;
     const int ti = tid >> 4, tj = tid & 15;
     const int i0 = i_base + ti * RI;
     const int sp = tid >> 5, sv = tid & 31;      // staging role: pivot pair sp, 4 columns / rows at sv * 4
@@ -1281,7 +1306,7 @@ __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int 
     // second copy of the folds costs registers the tile does not have (see main_max_interior).
     const bool interior = i_base + TI <= n && j_base + TJ <= n &&
                           !(i_base < j_base + TJ && j_base < i_base + TI) &&   // off the diagonal
-                          (k0 + B <= j_base || k0 >= j_base + TJ);             // no pivot column
+                          (k0 + ns * BS <= j_base || k0 >= j_base + TJ);       // no pivot column
 
     // Staging: addresses clamped into the panels, so every load is unconditional and nothing waits for it before
     // commit(), which replaces what lies outside the matrix and the pivot's own column (skip j == k) by NaN.
@@ -1346,8 +1371,8 @@ __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int 
     bool cmp = force_cmp != 0;                     // the compare form has begun (it persists)
     int buf = 0;
 #pragma unroll 1
-    for (int s = 0; s < NS; ++s, buf ^= 1) {
-        const bool more = s + 1 < NS;              // workgroup-uniform
+    for (int s = 0; s < ns; ++s, buf ^= 1) {
+        const bool more = s + 1 < ns;              // workgroup-uniform
         cmp |= voted(buf);
         if (more) prefetch();                      // in flight during the fold below
         // two loops one behind the other, one of them empty: an if / else of the two forms makes the compiler keep
@@ -2899,19 +2924,25 @@ hipError_t launch_fused_panels(const FusedArgs<T> &a, T *w_out, int32_t *wh_out,
 template hipError_t launch_fused_panels<float>(const FusedArgs<float> &, float *, int32_t *, hipStream_t);
 template hipError_t launch_fused_panels<double>(const FusedArgs<double> &, double *, int32_t *, hipStream_t);
 
-// The per-k engine's tile sweep (relax_tile): pivots [a.k, a.k + 64) on the whole matrix in place, one launch.
-// a.flip, a.temporal_bytes, a.store_bytes and a.walk are not read: a tile is loaded once and stored once whatever
-// the order of the tiles, and no result bit depends on them.
-hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s)
+// The per-k engine's tile sweep (relax_tile): pivots [a.k, a.k + a.np), a.np 64 or 128, in place and in one launch, on
+// the tiles that (sel, tx) names: all of them, all but tile row and tile column tx, or those two alone (an empty
+// choice launches nothing).  a.flip, a.temporal_bytes, a.store_bytes and a.walk are not read: a tile is loaded once and
+// stored once whatever the order of the tiles, and no result bit depends on them.
+hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s, TileSel sel, int tx)
 {
     if (a.n <= 0) return hipSuccess;
-    if (a.np != B || a.n < B || a.n % 4 || a.ct_ld % 4 || a.ct_ld < a.n || (uintptr_t)a.rate % 16 || (uintptr_t)a.w % 16 ||
-        (uintptr_t)a.ct % 16 || a.k < 0 || a.k + a.np > a.n || a.updates)
+    if ((a.np != B && a.np != 2 * B) || a.n < B || a.n % 4 || a.ct_ld % 4 || a.ct_ld < a.n || (uintptr_t)a.rate % 16 ||
+        (uintptr_t)a.w % 16 || (uintptr_t)a.ct % 16 || a.k < 0 || a.k + a.np > a.n || a.updates)
         return hipErrorInvalidValue;
-    const unsigned tiles = (unsigned)((a.n + 127) / 128);
+    const int tiles = (a.n + 127) / 128;
+    if (sel != TILES_ALL && (tx < 0 || tx >= tiles)) return hipErrorInvalidValue;
+    const dim3 grid = sel == TILES_ALL      ? dim3((unsigned)tiles, (unsigned)tiles)
+                      : sel == TILES_EXCEPT ? dim3((unsigned)(tiles - 1), (unsigned)(tiles - 1))
+                                            : dim3((unsigned)(2 * tiles - 1));
+    if (grid.x == 0) return hipSuccess;
     note_form(KF_RELAX_K);
-    hipLaunchKernelGGL((relax_tile<3, 8, 2>), dim3(tiles, tiles), dim3(256), 0, s, a.rate, a.n, a.k, a.w, a.ct,
-                       a.ct_ld, a.fold_compare ? 1 : 0);
+    hipLaunchKernelGGL((relax_tile<3, 8, 2>), grid, dim3(256), 0, s, a.rate, a.n, a.k, a.w, a.ct, a.ct_ld,
+                       a.fold_compare ? 1 : 0, a.np / 16, (int)sel, tx);
     return hipGetLastError();
 }
 

@@ -544,6 +544,21 @@ inline bool perk_deep()
 #define FWX_PERK_TILE_MIN_N_DEFAULT 1024
 inline int perk_tile_min_n() { return (int)env_digits("FWX_PERK_TILE_MIN_N", 0, INT_MAX, FWX_PERK_TILE_MIN_N_DEFAULT); }
 
+// The pair schedule (round 29): a call that takes the tile sweep, starts on a multiple of 64, has at least four full
+// blocks from its first pivot that is a multiple of 128, runs on the stream's own scratch entry and on a stream that
+// is not capturing, at n >= FWX_PERK_PAIR_MIN_N, applies its full blocks two at a time: one 128-pivot relax_tile
+// launch per pair on the caller's stream, the panels of the next pair made beside it on a look-ahead stream
+// (relax_range_kt).  Digits only, read on every call: 0 = never, otherwise the smallest order that takes it; any other
+// text means the default.  Every older hook's counters read the same either way (a 128-pivot launch is sixteen 8-pivot
+// groups, eight wide, four deep and two tile launches); the 128-pivot launches themselves are g_perk_pair_launches.
+// No result bit depends on it.
+// The default: serial / pair, ms per whole solve (profiles/r29_pair_crossover.txt): 2048 1.27 / 1.76, 3072 2.58 / 2.75,
+// 4096 4.23 / 4.58, 5120 6.90 / 6.09, 6144 10.12 / 9.19, 8192 20.7 / 18.9, 12288 69.5 / 62.1, 16384 158.5 / 142.9 -- up
+// to 4096 the look-ahead chain (four launches per 128 pivots) is the critical path, as it is for the fused engine's
+// double pass below its own crossover.
+#define FWX_PERK_PAIR_MIN_N_DEFAULT 5120
+inline int perk_pair_min_n() { return (int)env_digits("FWX_PERK_PAIR_MIN_N", 0, INT_MAX, FWX_PERK_PAIR_MIN_N_DEFAULT); }
+
 // The fold of relax_kt's non-counting f32 sweeps: FWX_PERK_FOLD=compare forces the compare form in every tile, read on
 // every call; anything else, or unset: automatic (each wave takes the max form where the operands it has loaded
 // are all NaN or sign-clear).  For tests and A/B runs in one binary.  No result bit depends on it (DESIGN.md
@@ -611,6 +626,10 @@ inline std::atomic<uint64_t> g_perk_deep_launches;
 // A tile sweep (round 26) applies a whole 64-pivot block: 8 to [3], 4 to g_perk_wide_launches, 2 to g_perk_deep_launches,
 // for the same reason, and 1 to g_perk_tile_launches (fwx_test_perk_tile).
 inline std::atomic<uint64_t> g_perk_tile_launches;
+// A 128-pivot main launch of the pair schedule (round 29) applies two blocks: 16 to [3], 8 / 4 / 2 to the three counters
+// above, and 1 to g_perk_pair_launches (fwx_test_perk_pair).  The cross launches of its look-ahead chain add nothing:
+// each entry still sees every pivot once in these counts.
+inline std::atomic<uint64_t> g_perk_pair_launches;
 
 // Snapshot panels (W and Ct of one 64-pivot block) of the multi-pivot schedule: perk_kt_ws_bytes.  A blocking
 // entry point that holds a per-call context passes that context's workspace.  fwx_dev_relax* has no workspace
@@ -627,9 +646,19 @@ template <typename T> inline size_t perk_kt_ws_bytes(int n)
     const size_t ld = ((size_t)n + 3) & ~(size_t)3;
     return (size_t)FWX_FUSED_B * ((size_t)n + ld) * sizeof(T);
 }
+// The pair schedule (round 29) keeps more in the stream's entry: four panel sets instead of one (asked for only by the
+// calls that take it), and a look-ahead stream with its two events.  Those are created by the first such call on the
+// stream, on the stream's device -- the stream non-blocking, so that it orders itself against the caller's stream (the
+// null stream included) through the events alone; the events without timing -- and destroyed with the entry.  Every call
+// makes the caller's stream wait for the look-ahead stream before it returns, so "this stream's launches are the
+// buffer's only readers" holds as before.
+struct PerkSide {
+    hipStream_t s = nullptr;
+    hipEvent_t main_done = nullptr, chain_done = nullptr;
+};
 class PerkScratch {
 public:
-    static int get(hipStream_t s, size_t bytes, void **out)
+    static int get(hipStream_t s, size_t bytes, void **out, PerkSide *side = nullptr)
     {
         int dev = 0, cur = 0;
         FWX_HIP(hipGetDevice(&cur));
@@ -646,9 +675,10 @@ public:
                 for (size_t i = 1; i < p.all.size(); ++i)
                     if (p.all[i].used < p.all[lru].used) lru = i;
                 if (p.all[lru].p) (void)hipFree(p.all[lru].p);
+                release(p.all[lru].side);          // behind the hipFree, which has waited for the device
                 p.all.erase(p.all.begin() + (long)lru);
             }
-            p.all.push_back(Entry{dev, s, nullptr, 0, 0});
+            p.all.push_back(Entry{dev, s, nullptr, 0, 0, PerkSide()});
             e = &p.all.back();
         }
         e->used = ++p.clock;
@@ -664,13 +694,30 @@ public:
             FWX_HIP(err);
             e->cap = bytes;
         }
+        if (side && !e->side.chain_done) {         // all three or none: a failure half way releases what it made
+            if (dev != cur) FWX_HIP(hipSetDevice(dev));
+            hipError_t err = hipStreamCreateWithFlags(&e->side.s, hipStreamNonBlocking);
+            if (err == hipSuccess) err = hipEventCreateWithFlags(&e->side.main_done, hipEventDisableTiming);
+            if (err == hipSuccess) err = hipEventCreateWithFlags(&e->side.chain_done, hipEventDisableTiming);
+            if (err != hipSuccess) release(e->side);
+            if (dev != cur) (void)hipSetDevice(cur);
+            FWX_HIP(err);
+        }
+        if (side) *side = e->side;
         *out = e->p;
         return FWX_OK;
     }
 
 private:
     static constexpr size_t kMax = 16;
-    struct Entry { int dev; hipStream_t s; void *p; size_t cap; uint64_t used; };
+    struct Entry { int dev; hipStream_t s; void *p; size_t cap; uint64_t used; PerkSide side; };
+    static void release(PerkSide &d)
+    {
+        if (d.main_done) (void)hipEventDestroy(d.main_done);
+        if (d.chain_done) (void)hipEventDestroy(d.chain_done);
+        if (d.s) (void)hipStreamDestroy(d.s);
+        d = PerkSide();
+    }
     struct Pool { std::mutex mu; std::vector<Entry> all; uint64_t clock = 0; };
     static Pool &pool() { static Pool *p = new Pool(); return *p; }   // leaked on purpose
 };
@@ -685,16 +732,47 @@ private:
 // starts at 32 (perk_deep), one streaming pass per half block.
 // A FULL block of such a call at n >= perk_tile_min_n() takes one relax_tile launch instead of the two 32-pivot sweeps
 // (round 26): the block's 64 pivots in one pass on register tiles, the operands through LDS.
+// From n >= perk_pair_min_n() such a call applies its full blocks two at a time behind a look-ahead chain on a second
+// stream (round 29: the pair schedule, below); when it returns, `s` waits for everything it queued there.
 template <typename T>
 inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine, int np,
                           unsigned long long *d_updates, hipStream_t s, void *ws)
 {
+    constexpr int Bq = FWX_FUSED_B;
     const size_t ld = ((size_t)n + 3) & ~(size_t)3;
+    const bool wide = np == 8 && !d_updates && std::is_same<T, float>::value && perk_wide();
+    const int g_top = wide ? (perk_walk() && perk_deep() ? 32 : 16) : np;
+    // a full block where the ladder would start at 32: one tile sweep (round 26) instead of the two 32-pivot sweeps
+    const int tile_min_n = perk_tile_min_n();
+    const bool tile = g_top == 32 && tile_min_n > 0 && n >= tile_min_n && n >= Bq;
+    // The pair schedule (round 29; the comment above perk_pair_min_n): the stream's own scratch entry only, since a
+    // caller's workspace holds one panel set and no look-ahead stream.
+    const int k_a = (k_begin + 2 * Bq - 1) / (2 * Bq) * (2 * Bq);     // the first pair starts on a tile boundary
+    const int pair_min_n = perk_pair_min_n();
+    bool pair = tile && !ws && pair_min_n > 0 && n >= pair_min_n && k_begin % Bq == 0 && k_end - k_a >= 4 * Bq;
+    if (pair) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess) {            // (a null stream beside a global capture)
+            (void)hipGetLastError();
+            pair = false;
+        } else if (cap != hipStreamCaptureStatusNone) {
+            pair = false;                                             // a captured graph gets no parallel branches
+        }
+    }
+    const int sets = pair ? 4 : 1;
+    PerkSide side;
     if (!ws) {
-        const int rc0 = PerkScratch::get(s, perk_kt_ws_bytes<T>(n), &ws);
+        const int rc0 = PerkScratch::get(s, (size_t)sets * perk_kt_ws_bytes<T>(n), &ws, pair ? &side : nullptr);
         if (rc0) return rc0;
     }
-    T *const w = (T *)ws, *const ct = w + (size_t)FWX_FUSED_B * n;
+    // `sets` panel sets: the W rows of all sets, then the Ct lines of all sets, so that with four sets -- block q of the
+    // pair schedule in set q & 3 -- the panels of a pair (2P, 2P + 1) are 128 contiguous rows of W and lines of Ct
+    T *const w_all = (T *)ws, *const ct_all = w_all + (size_t)sets * Bq * n;
+    T *w = w_all, *ct = ct_all;                    // the set in use
+    auto use_set = [&](int q) {
+        w = w_all + (size_t)(q & (sets - 1)) * Bq * n;
+        ct = ct_all + (size_t)(q & (sets - 1)) * Bq * ld;
+    };
 
     fwx::FusedArgs<T> pa;
     pa.rate = rate; pa.next = nullptr; pa.rows = n; pa.n = n; pa.row0 = 0; pa.w = nullptr; pa.ct = ct;
@@ -714,30 +792,39 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
     auto after = [&](hipError_t e, int slot, int groups = 1) -> int {
         if (e == hipErrorInvalidValue) return FWX_ERR_INVALID;
         FWX_HIP(e);
-        g_perk_launches[slot].fetch_add((uint64_t)groups, std::memory_order_relaxed);
-        if (groups >= 2) g_perk_wide_launches.fetch_add((uint64_t)groups / 2, std::memory_order_relaxed);
-        if (groups >= 4) g_perk_deep_launches.fetch_add((uint64_t)groups / 4, std::memory_order_relaxed);
-        if (groups == 8) g_perk_tile_launches.fetch_add(1, std::memory_order_relaxed);
+        if (slot >= 0) {                           // (a cross launch of the pair schedule counts nowhere)
+            g_perk_launches[slot].fetch_add((uint64_t)groups, std::memory_order_relaxed);
+            if (groups >= 2) g_perk_wide_launches.fetch_add((uint64_t)groups / 2, std::memory_order_relaxed);
+            if (groups >= 4) g_perk_deep_launches.fetch_add((uint64_t)groups / 4, std::memory_order_relaxed);
+            if (groups >= 8) g_perk_tile_launches.fetch_add((uint64_t)groups / 8, std::memory_order_relaxed);
+            if (groups == 16) g_perk_pair_launches.fetch_add(1, std::memory_order_relaxed);
+        }
         return thr.tick(s);
     };
-    const bool wide = np == 8 && !d_updates && std::is_same<T, float>::value && perk_wide();
-    const int g_top = wide ? (a.walk && perk_deep() ? 32 : 16) : np;
-    // a full block where the ladder would start at 32: one tile sweep (round 26) instead of the two 32-pivot sweeps
-    const int tile_min_n = perk_tile_min_n();
-    const bool tile = g_top == 32 && tile_min_n > 0 && n >= tile_min_n && n >= FWX_FUSED_B;
-    for (int k0 = k_begin; k0 < k_end; k0 += FWX_FUSED_B) {
-        const int bt = std::min(FWX_FUSED_B, k_end - k0);
+    // both panels of the block at k0 (bt pivots) into the set in use, from the matrix as `st` finds it
+    auto panels = [&](int k0, int bt, hipStream_t st) -> int {
+        pa.k0 = k0; pa.bt = bt; pa.ct = ct; pa.side = st != s;
+        return after(fwx::launch_fused_panels<T>(pa, w, nullptr, st), 4);
+    };
+    // pivots [k0, k0 + bt) in one relax_tile launch, the panels from the set in use (bt 128: from it and the next one)
+    auto tiles = [&](int k0, int bt, hipStream_t st, fwx::TileSel sel, int tx) -> int {
+        if constexpr (std::is_same<T, float>::value) {
+            a.k = k0; a.np = bt; a.w = w; a.ct = ct;
+            a.flip = 0;                            // not read: a tile is loaded and stored once, in any order
+            return after(fwx::launch_relax_tile(a, st, sel, tx), sel == fwx::TILES_CROSS ? -1 : 3, bt / 8);
+        } else {
+            return FWX_ERR_INVALID;                // (tile is false for f64)
+        }
+    };
+    // one block as the serial schedule runs it, everything on `s`: its panels, then a tile sweep or the ladder
+    auto block = [&](int k0, int bt, bool panels_ready) -> int {
         int t = 0;
         if (bt >= 2) {
-            pa.k0 = k0; pa.bt = bt;
-            if (const int rc = after(fwx::launch_fused_panels<T>(pa, w, nullptr, s), 4)) return rc;
-            if constexpr (std::is_same<T, float>::value) {
-                if (tile && bt == FWX_FUSED_B) {
-                    a.k = k0; a.np = bt; a.w = w; a.ct = ct;
-                    a.flip = 0;                    // not read: a tile is loaded and stored once, in any order
-                    if (const int rc = after(fwx::launch_relax_tile(a, s), 3, 8)) return rc;
-                    t = bt;
-                }
+            if (!panels_ready)
+                if (const int rc = panels(k0, bt, s)) return rc;
+            if (tile && bt == Bq) {
+                if (const int rc = tiles(k0, bt, s, fwx::TILES_ALL, 0)) return rc;
+                t = bt;
             }
             for (int g = g_top; g >= 2; g >>= 1)
                 for (; bt - t >= g; t += g) {
@@ -752,8 +839,75 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
             a1.flip = serpentine ? rev * (sweeps++ & 1) : 0;
             if (const int rc = after(fwx::launch_relax<T>(a1, s), 0)) return rc;
         }
+        return FWX_OK;
+    };
+    if (!pair) {
+        for (int k0 = k_begin; k0 < k_end; k0 += Bq)
+            if (const int rc = block(k0, std::min(Bq, k_end - k0), false)) return rc;
+        return FWX_OK;
     }
-    return FWX_OK;
+
+    // ---- the pair schedule (the model is the double pass of fused_range) ------------
+    // Blocks are numbered from k_a; a leading block at k_begin = k_a - 64 is q = -1 and runs as above.  Pair P = blocks
+    // (2P, 2P + 1) = the 128 pivots of tile row / column X = k_a / 128 + P.  While the main launch applies pair P to
+    // every tile but the cross X + 1 (tile row and tile column of the next pair), the chain on the look-ahead stream
+    // takes that cross through pair P, takes the panels of block 2P + 2 from it, applies that block to it and takes the
+    // panels of block 2P + 3.  The next main launch folds block 2P + 2 into that cross a second time, with the same
+    // operands, which moves nothing.  An odd last block gets its panels the same way and one 64-pivot launch.
+    const int nfull = (k_end - k_a) / Bq, pairs = nfull / 2;
+    auto k_of = [&](int q) { return k_a + q * Bq; };
+    bool chain_open = false;                       // launches are queued on side.s that `s` does not wait for yet
+    auto join = [&]() -> hipError_t {
+        chain_open = false;
+        hipError_t e = hipEventRecord(side.chain_done, side.s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, side.chain_done, 0);
+        return e;
+    };
+    auto run = [&]() -> int {
+        if (k_begin < k_a) {
+            use_set(-1);
+            if (const int rc = block(k_begin, Bq, false)) return rc;
+        }
+        // chain(0), on the caller's stream: the first pair's panels need block 0 applied to its own tile row and column
+        use_set(0);
+        if (const int rc = panels(k_of(0), Bq, s)) return rc;
+        if (const int rc = tiles(k_of(0), Bq, s, fwx::TILES_CROSS, k_a / (2 * Bq))) return rc;
+        use_set(1);
+        if (const int rc = panels(k_of(1), Bq, s)) return rc;
+        for (int P = 0; P < pairs; ++P) {
+            const int q = 2 * P, ahead = std::min(2, nfull - (q + 2));   // full blocks behind this pair, two at most
+            const int xn = k_of(q + 2) / (2 * Bq);                       // their tile row / column
+            if (ahead > 0) {
+                FWX_HIP(hipEventRecord(side.main_done, s));              // the last main launch and chain precede
+                FWX_HIP(hipStreamWaitEvent(side.s, side.main_done, 0));
+                chain_open = true;
+                use_set(q);
+                if (const int rc = tiles(k_of(q), 2 * Bq, side.s, fwx::TILES_CROSS, xn)) return rc;
+                use_set(q + 2);
+                if (const int rc = panels(k_of(q + 2), Bq, side.s)) return rc;
+                if (ahead == 2) {
+                    if (const int rc = tiles(k_of(q + 2), Bq, side.s, fwx::TILES_CROSS, xn)) return rc;
+                    use_set(q + 3);
+                    if (const int rc = panels(k_of(q + 3), Bq, side.s)) return rc;
+                }
+            }
+            use_set(q);
+            if (const int rc = tiles(k_of(q), 2 * Bq, s, ahead > 0 ? fwx::TILES_EXCEPT : fwx::TILES_ALL, xn)) return rc;
+            if (chain_open) FWX_HIP(join());
+        }
+        if (nfull & 1) {                           // the odd last block: its panels are ready
+            use_set(nfull - 1);
+            if (const int rc = block(k_of(nfull - 1), Bq, true)) return rc;
+        }
+        if (k_of(nfull) < k_end) {                 // a ragged tail takes the ladder
+            use_set(nfull);
+            if (const int rc = block(k_of(nfull), k_end - k_of(nfull), false)) return rc;
+        }
+        return FWX_OK;
+    };
+    const int rc = run();
+    if (chain_open) (void)join();                  // an error return: the caller's stream still waits for the chain
+    return rc;
 }
 
 // One launch per pivot over a slab; pivot rows from `prow0 + (k-k_begin)*stride`.  A rates-only call on

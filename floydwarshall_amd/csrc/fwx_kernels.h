@@ -138,11 +138,14 @@ template <typename T> struct RelaxKtArgs {
     unsigned long long *updates = nullptr;   // FWX_UPDATE_SHARDS_K counters or nullptr
 };
 template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s);
-// relax_tile (round 26, fwx_fused.hip): pivots [k, k+64) in ONE pass on 128 x 128 register tiles, operands from LDS;
-// np == 64, f32, updates == nullptr, n >= 64.  The fold is chosen per tile and stage (max form where the tile's
-// entries and operands allow it; fold_compare forces the compare form).  flip, temporal_bytes, store_bytes and walk
-// are not read: no result bit depends on them.
-hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s);
+// relax_tile (round 26, fwx_fused.hip): pivots [k, k+np) in ONE pass on 128 x 128 register tiles, operands from LDS;
+// np == 64 or 128 (round 29: w and ct then hold 128 rows / lines), f32, updates == nullptr, n >= 64.  The fold is
+// chosen per tile and stage (max form where the tile's entries and operands allow it; fold_compare forces the compare
+// form).  flip, temporal_bytes, store_bytes and walk are not read: no result bit depends on them.
+// The tiles of a launch: all, all but tile row tx and tile column tx (the main launch beside a look-ahead chain), or
+// only those two (the cross: one launch of 2 * tiles - 1 workgroups at a raised wave priority).
+enum TileSel { TILES_ALL = 0, TILES_EXCEPT = 1, TILES_CROSS = 2 };
+hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s, TileSel sel = TILES_ALL, int tx = 0);
 
 // Whole solve (pivots [k_begin,k_end)) of an n <= FWX_SMALL_N matrix in one single-workgroup launch.
 #define FWX_SMALL_N 128

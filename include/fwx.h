@@ -162,6 +162,14 @@ int fwx_test_perk_deep(uint64_t *deep_launches, int reset);
  * by fwx_test_perk_wide and as 2 by fwx_test_perk_deep -- which is cleared if reset.  Needs no device.  Not for
  * production use.                                                                                        */
 int fwx_test_perk_tile(uint64_t *launches, int reset);
+/* TEST HOOK for the pair schedule (FWX_PERK_PAIR_MIN_N): returns what the variable parses to right now: 0 = never,
+ * otherwise the smallest order n at which a call that takes the tile sweep applies its full blocks two at a time, one
+ * 128-pivot launch per pair with the next pair's panels made beside it on a look-ahead stream (digits only; any other
+ * text, or unset: the default).  *launches (if not NULL) receives the number of 128-pivot main launches in this
+ * process -- each of them also counted as 16 by fwx_test_perk_pivots, as 8 by fwx_test_perk_wide, as 4 by
+ * fwx_test_perk_deep and as 2 by fwx_test_perk_tile -- which is cleared if reset.  Needs no device.  Not for
+ * production use.                                                                                        */
+int fwx_test_perk_pair(uint64_t *launches, int reset);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).
