@@ -1040,6 +1040,29 @@ int fwx_test_perk_pair(uint64_t *launches, int reset)
     return perk_pair_min_n();
 }
 
+int fwx_test_perk_group(uint64_t *launches, int reset)
+{
+    for (int i = 0; i < FWX_PERK_GROUP_CAP / 2; ++i) {
+        const uint64_t v = reset ? g_perk_group_launches[i].exchange(0, std::memory_order_relaxed)
+                                 : g_perk_group_launches[i].load(std::memory_order_relaxed);
+        if (launches) launches[i] = v;
+    }
+    return perk_group_max_env();
+}
+
+int fwx_test_perk_group_plan(int n, int nfull, int gmax, int *size, int *set, int cap)
+{
+    if (gmax == 0) gmax = perk_group_max(n);
+    if (nfull < 0 || gmax < 2 || gmax > FWX_PERK_GROUP_CAP || (gmax & 1) || cap < 0) return -1;
+    int g = 0;
+    for (int q = 0, sz = perk_group_size(nfull, 0, gmax); sz > 0; q += sz, sz = perk_group_size(nfull - q, sz, gmax), ++g)
+        if (g < cap) {
+            if (size) size[g] = sz;
+            if (set) set[g] = (g & 1) * gmax;
+        }
+    return g;
+}
+
 int fwx_test_perk_wide(uint64_t *wide_launches, int reset)
 {
     const uint64_t v = reset ? g_perk_wide_launches.exchange(0, std::memory_order_relaxed)

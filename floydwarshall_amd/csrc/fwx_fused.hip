@@ -107,8 +107,16 @@ struct ClockProbe {
     }
 };
 #define FWX_PROBE ClockProbe probe_
+// relax_tile's phases (round 30), s_memtime cycles of every workgroup summed by thread 0: [0] entry to the first barrier
+// (tile load, class test, first commit), [1] the stage loop, [2] of that the commits and barriers at the stage ends,
+// [3] the store to the exit, [4] entry to exit, [5] the same in s_memrealtime ticks (100 MHz), [6] workgroups,
+// [7] stages.  fwx_debug_tile_clock reads them (tools/measure_tile_phases.py).
+__device__ unsigned long long g_tile_clk[8];
+#define FWX_TILE_NOW() __builtin_amdgcn_s_memtime()
+#define FWX_TILE_PROBE(...) __VA_ARGS__
 #else
 #define FWX_PROBE do { } while (0)
+#define FWX_TILE_PROBE(...)
 #endif
 
 // Column controls of a main-kernel launch (symmetric look-ahead, fused_range in fwx_api.hip):
@@ -1199,6 +1207,11 @@ __global__ __launch_bounds__(256, MINW) void fused_main_max(float *rate, int row
 // patch's column index advances with every commit -- and (sel, tx) names the tiles of the launch (TileSel,
 // fwx_kernels.h): all, all but tile row and tile column tx, or only those two.  The pair schedule of relax_range_kt
 // (fwx_internal.h) runs the second beside a chain of the third on another stream; the two never touch the same tile.
+//
+// Round 30: ns is any multiple of 4 up to 32 (a group of up to eight blocks, 512 contiguous panel rows and lines), and
+// the choice names a band of tw tile rows and columns from tx, the cross without the te indices in front of it.  The
+// interior test's pivot-column bound k0 + 16 * ns and the NaN patch's kcol, which advances by 16 with every commit, hold
+// for any ns: kcol starts at k0 + 2 * sp - sj and matches e in 0 .. 3 at exactly one stage per pivot pair.
 // ------------------------------------------------------------------------------------------------
 
 // One pivot pair of the compare-form fold on the register tile: pivot u = 0 on every entry, then u = 1
@@ -1246,8 +1259,10 @@ __device__ __forceinline__ int sign_bits(F32x4 v)
 template <int MINW, int RI, int NH>
 __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int k0, const float *w,
                                                         const float *ct, int ct_ld, int force_cmp, int ns, int sel,
-                                                        int tx)
+                                                        int tx, int tw, int te)
 {
+    FWX_TILE_PROBE(const unsigned long long pt0 = FWX_TILE_NOW(), pr0 = __builtin_amdgcn_s_memrealtime();
+                   unsigned long long pt_ends = 0;)
     typedef float V4 __attribute__((ext_vector_type(4)));
     constexpr int TI = 16 * RI, TJ = 64 * NH, HJ = 64, BS = 16, HP = BS / 2;
     static_assert(TI == 128 && TJ == 128, "every thread stages both operands: 8 pivot pairs x 32 vectors");
@@ -1256,23 +1271,30 @@ __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int 
     __shared__ __attribute__((aligned(16))) float sC[2][HP][2][TI];
     __shared__ __attribute__((aligned(16))) int sVote[2][4];   // [stage parity][wave]: the wave staged a sign bit
 
-    // Which tile (workgroup-uniform).  TILES_ALL: the grid is the tile grid.  TILES_EXCEPT: a grid one tile shorter each
-    // way that steps over tile row tx and tile column tx.  TILES_CROSS: a one-dimensional grid of 2 * tiles - 1, tile
-    // row tx first, then the rest of tile column tx; a launch of the look-ahead chain beside a main launch.
+    // Which tile (workgroup-uniform, scalar work on the workgroup ids).  TILES_ALL: the grid is the tile grid.
+    // TILES_EXCEPT: a grid tw tiles shorter each way that steps over the tile rows and tile columns [tx, tx + tw).
+    // TILES_CROSS: a launch of the look-ahead chain beside a main launch, those tile rows and columns alone, among the
+    // m tile indices that are left without [tx - te, tx): a one-dimensional grid of tw * (2 * m - tw), the band's tw
+    // tile rows first, m tiles each, then what is left of its tw tile columns, m - tw tiles each.  (tw is at most 4:
+    // the row or column is counted off, not divided out.)
     int bx = blockIdx.x, by = blockIdx.y;
     if (sel == TILES_EXCEPT) {
-        bx += bx >= tx ? 1 : 0;
-        by += by >= tx ? 1 : 0;
+        bx += bx >= tx ? tw : 0;
+        by += by >= tx ? tw : 0;
     } else if (sel == TILES_CROSS) {
         __builtin_amdgcn_s_setprio(2);
-        const int tiles = ((int)gridDim.x + 1) >> 1;
-        if (bx < tiles) {
-            by = tx;
-        } else {
-            by = bx - tiles;
-            by += by >= tx ? 1 : 0;
-            bx = tx;
+        const int m = ((n + TI - 1) / TI) - te, rows = tw * m;
+        const bool col = bx >= rows;
+        const int len = col ? m - tw : m;
+        int at = col ? bx - rows : bx, line = tx;
+        while (at >= len) {
+            at -= len;
+            ++line;
         }
+        at += at >= tx - te ? te : 0;            // step over the indices in front of the band
+        at += col && at >= tx ? tw : 0;          // a tile column: and over the band's own rows
+        bx = col ? line : at;
+        by = col ? at : line;
     }
     const int tid = threadIdx.x;
     const int i_base = by * TI;
@@ -1367,6 +1389,7 @@ __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int 
     __builtin_amdgcn_s_waitcnt(FWX_WAIT_VMCNT0);   // the tile is complete here, once (see fused_main_max)
     commit(0, x_bits(x));                          // clamped duplicates vote too: on the safe side
     __syncthreads();
+    FWX_TILE_PROBE(const unsigned long long pt1 = FWX_TILE_NOW();)
 
     bool cmp = force_cmp != 0;                     // the compare form has begun (it persists)
     int buf = 0;
@@ -1383,10 +1406,26 @@ __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int 
 #pragma unroll 1
         for (int tp = nmax; tp < HP; ++tp) cmp_fold_pair<RI, NH>(sW[buf][tp], sC[buf][tp], ti, tj, x);
         if (more) {
+            FWX_TILE_PROBE(const unsigned long long pe0 = FWX_TILE_NOW();)
             commit(buf ^ 1, 0);                    // the other buffer: nobody reads it now
             __syncthreads();
+            FWX_TILE_PROBE(pt_ends += FWX_TILE_NOW() - pe0;)
         }
     }
+    FWX_TILE_PROBE(const unsigned long long pt2 = FWX_TILE_NOW();
+                   auto probe_out = [&]() {
+                       __builtin_amdgcn_s_waitcnt(FWX_WAIT_VMCNT0);      // the stores have left
+                       if (threadIdx.x != 0) return;
+                       const unsigned long long pt3 = FWX_TILE_NOW();
+                       atomicAdd(&g_tile_clk[0], pt1 - pt0);
+                       atomicAdd(&g_tile_clk[1], pt2 - pt1);
+                       atomicAdd(&g_tile_clk[2], pt_ends);
+                       atomicAdd(&g_tile_clk[3], pt3 - pt2);
+                       atomicAdd(&g_tile_clk[4], pt3 - pt0);
+                       atomicAdd(&g_tile_clk[5], __builtin_amdgcn_s_memrealtime() - pr0);
+                       atomicAdd(&g_tile_clk[6], 1ull);
+                       atomicAdd(&g_tile_clk[7], (unsigned long long)ns);
+                   };)
 
     if (interior) {
         float *xp = rate + (size_t)i0 * n + j_base + tj * 4;
@@ -1394,6 +1433,7 @@ __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int 
         for (int r = 0; r < RI; ++r)
 #pragma unroll
             for (int h = 0; h < NH; ++h) *reinterpret_cast<V4 *>(xp + (size_t)r * n + h * HJ) = x[r][h];
+        FWX_TILE_PROBE(probe_out();)
         return;
     }
     if (i_base < j_base + TJ && j_base < i_base + TI) {   // the diagonal entries keep their value: restored once
@@ -1419,6 +1459,7 @@ __global__ __launch_bounds__(256, MINW) void relax_tile(float *rate, int n, int 
             if (j < n) *reinterpret_cast<V4 *>(rate + (size_t)i * n + j) = x[r][h];
         }
     }
+    FWX_TILE_PROBE(probe_out();)
 }
 
 typedef double F64x2 __attribute__((ext_vector_type(2)));
@@ -2924,25 +2965,27 @@ hipError_t launch_fused_panels(const FusedArgs<T> &a, T *w_out, int32_t *wh_out,
 template hipError_t launch_fused_panels<float>(const FusedArgs<float> &, float *, int32_t *, hipStream_t);
 template hipError_t launch_fused_panels<double>(const FusedArgs<double> &, double *, int32_t *, hipStream_t);
 
-// The per-k engine's tile sweep (relax_tile): pivots [a.k, a.k + a.np), a.np 64 or 128, in place and in one launch, on
-// the tiles that (sel, tx) names: all of them, all but tile row and tile column tx, or those two alone (an empty
-// choice launches nothing).  a.flip, a.temporal_bytes, a.store_bytes and a.walk are not read: a tile is loaded once and
-// stored once whatever the order of the tiles, and no result bit depends on them.
-hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s, TileSel sel, int tx)
+// The per-k engine's tile sweep (relax_tile): pivots [a.k, a.k + a.np), a.np a multiple of 64 up to 512, in place and in
+// one launch, on the tiles that (sel, tx, tw, te) names: all of them, all but the tile rows and tile columns
+// [tx, tx + tw), or those alone without what they share with the te indices in front of them (an empty choice launches
+// nothing).  a.flip, a.temporal_bytes, a.store_bytes and a.walk are not read: a tile is loaded once and stored once
+// whatever the order of the tiles, and no result bit depends on them.
+hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s, TileSel sel, int tx, int tw, int te)
 {
     if (a.n <= 0) return hipSuccess;
-    if ((a.np != B && a.np != 2 * B) || a.n < B || a.n % 4 || a.ct_ld % 4 || a.ct_ld < a.n || (uintptr_t)a.rate % 16 ||
-        (uintptr_t)a.w % 16 || (uintptr_t)a.ct % 16 || a.k < 0 || a.k + a.np > a.n || a.updates)
+    if (a.np < B || a.np > 8 * B || a.np % B || a.n < B || a.n % 4 || a.ct_ld % 4 || a.ct_ld < a.n ||
+        (uintptr_t)a.rate % 16 || (uintptr_t)a.w % 16 || (uintptr_t)a.ct % 16 || a.k < 0 || a.k + a.np > a.n || a.updates)
         return hipErrorInvalidValue;
     const int tiles = (a.n + 127) / 128;
-    if (sel != TILES_ALL && (tx < 0 || tx >= tiles)) return hipErrorInvalidValue;
+    if (sel != TILES_ALL && (tx < 0 || tw < 1 || tx + tw > tiles)) return hipErrorInvalidValue;
+    if (sel == TILES_CROSS ? te < 0 || te > tx : te != 0) return hipErrorInvalidValue;
     const dim3 grid = sel == TILES_ALL      ? dim3((unsigned)tiles, (unsigned)tiles)
-                      : sel == TILES_EXCEPT ? dim3((unsigned)(tiles - 1), (unsigned)(tiles - 1))
-                                            : dim3((unsigned)(2 * tiles - 1));
+                      : sel == TILES_EXCEPT ? dim3((unsigned)(tiles - tw), (unsigned)(tiles - tw))
+                                            : dim3((unsigned)(tw * (2 * (tiles - te) - tw)));
     if (grid.x == 0) return hipSuccess;
     note_form(KF_RELAX_K);
     hipLaunchKernelGGL((relax_tile<3, 8, 2>), grid, dim3(256), 0, s, a.rate, a.n, a.k, a.w, a.ct, a.ct_ld,
-                       a.fold_compare ? 1 : 0, a.np / 16, (int)sel, tx);
+                       a.fold_compare ? 1 : 0, a.np / 16, (int)sel, tx, tw, te);
     return hipGetLastError();
 }
 
@@ -2968,6 +3011,15 @@ extern "C" __attribute__((visibility("default"))) int fwx_debug_clock(unsigned l
     if (reset) {
         const unsigned long long z[3] = {0, 0, 0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(fwx::g_clk), z, 24) != hipSuccess) return -1;
+    }
+    return 0;
+}
+extern "C" __attribute__((visibility("default"))) int fwx_debug_tile_clock(unsigned long long *out, int reset)
+{
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(fwx::g_tile_clk), 64) != hipSuccess) return -1;
+    if (reset) {
+        const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(fwx::g_tile_clk), z, 64) != hipSuccess) return -1;
     }
     return 0;
 }

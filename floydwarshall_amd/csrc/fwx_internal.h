@@ -551,13 +551,54 @@ inline int perk_tile_min_n() { return (int)env_digits("FWX_PERK_TILE_MIN_N", 0, 
 // (relax_range_kt).  Digits only, read on every call: 0 = never, otherwise the smallest order that takes it; any other
 // text means the default.  Every older hook's counters read the same either way (a 128-pivot launch is sixteen 8-pivot
 // groups, eight wide, four deep and two tile launches); the 128-pivot launches themselves are g_perk_pair_launches.
-// No result bit depends on it.
+// No result bit depends on it.  Since round 30 it is the threshold of the group
+// schedule as well: how many blocks a main launch applies is FWX_PERK_GROUP_MAX's matter (below), whether the call takes
+// a look-ahead schedule at all is this variable's, and 0 still gives the serial schedule whatever the other says.
 // The default: serial / pair, ms per whole solve (profiles/r29_pair_crossover.txt): 2048 1.27 / 1.76, 3072 2.58 / 2.75,
 // 4096 4.23 / 4.58, 5120 6.90 / 6.09, 6144 10.12 / 9.19, 8192 20.7 / 18.9, 12288 69.5 / 62.1, 16384 158.5 / 142.9 -- up
 // to 4096 the look-ahead chain (four launches per 128 pivots) is the critical path, as it is for the fused engine's
 // double pass below its own crossover.
 #define FWX_PERK_PAIR_MIN_N_DEFAULT 5120
 inline int perk_pair_min_n() { return (int)env_digits("FWX_PERK_PAIR_MIN_N", 0, INT_MAX, FWX_PERK_PAIR_MIN_N_DEFAULT); }
+
+// The group schedule (round 30): a call that takes the pair schedule applies its full blocks in groups of up to
+// FWX_PERK_GROUP_MAX blocks per main launch, the groups growing inside the call (perk_group_size).  Digits only, read on
+// every call: 2 ... FWX_PERK_GROUP_CAP, an odd value rounded down to the even one below it; 2 is the pair schedule of
+// round 29, launch for launch.  Any other text, or unset, means the default, which goes by the order of the matrix
+// (perk_group_max(n)); a value that is set holds at every order.  FWX_PERK_PAIR_MIN_N=0 still gives the serial
+// schedule.  Every older hook's counters read the same for every value (a 512-pivot launch is four 128-pivot ones, and
+// so on down); the main launches by group size are g_perk_group_launches.  No result bit depends on it (DESIGN.md
+// section 4.1, round 30).
+// The default: serial / 2 / 4 / 8, ms per whole solve in one call (profiles/r30_group_crossover.txt): 5120 6.92 / 6.15 /
+// 6.41 / 6.73, 6144 10.18 / 9.15 / 9.18 / 9.00, 8192 20.8 / 19.1 / 18.0 / 17.8, 12288 70.2 / 62.1 / 57.5 / 56.8, 16384
+// 158.9 / 143.5 / 133.9 / 131.0 -- at 5120 the chains of the larger groups no longer end before the main launches
+// beside them, from 6144 eight blocks are the fastest at every order measured.
+#define FWX_PERK_GROUP_CAP 8
+#define FWX_PERK_GROUP_MIN_N_DEFAULT 6144
+inline int perk_group_max_env() { return (int)env_digits("FWX_PERK_GROUP_MAX", 2, FWX_PERK_GROUP_CAP, 0) & ~1; }
+inline int perk_group_max(int n)
+{
+    if (const int g = perk_group_max_env()) return g;
+    return n >= FWX_PERK_GROUP_MIN_N_DEFAULT ? FWX_PERK_GROUP_CAP : 2;
+}
+// The size of the next group: `left` full blocks are still to be applied, the group before had `prev` blocks (0: this
+// is the call's first group), at most `gmax` blocks per group.  The rule: the chain beside a main launch must end
+// before that launch does.  The chain that prepares a group of G blocks runs beside the main launch of the group
+// before, P blocks: per block of G one panel launch and one 64-pivot cross launch on the band, behind one cross launch
+// through the P blocks.  At n = 16384 a main launch spends about 570 us per block of P and the chain beside it 180 to
+// 380 us per block of G (profiles/r30_group_chain.txt: the panel launch alone takes 26 us by itself and 100 to 270 us
+// beside a main launch), so G <= 2 * P: the chain of a 4-block group ends 300 us before the pair's launch does, the
+// chain of a 2-block tail 2.7 ms before the 8-block launch, but the chain of an 8-block group ends about 180 us BEHIND
+// the 4-block launch beside it (its last three blocks run alone, 80 us each): the one place where the rule is not met.
+// It ships all the same: groups of at most 4 in its place are slower at every order from 6144
+// (profiles/r30_group_crossover.txt).
+// Nothing runs beside the work in front of the first main launch, so the first group is a pair, as in round 29.  A
+// single block that is left is the odd last block.
+inline int perk_group_size(int left, int prev, int gmax)
+{
+    if (left < 2) return left > 0 ? 1 : 0;
+    return std::min(std::min(prev > 0 ? 2 * prev : 2, gmax), left & ~1);
+}
 
 // The fold of relax_kt's non-counting f32 sweeps: FWX_PERK_FOLD=compare forces the compare form in every tile, read on
 // every call; anything else, or unset: automatic (each wave takes the max form where the operands it has loaded
@@ -630,6 +671,10 @@ inline std::atomic<uint64_t> g_perk_tile_launches;
 // above, and 1 to g_perk_pair_launches (fwx_test_perk_pair).  The cross launches of its look-ahead chain add nothing:
 // each entry still sees every pivot once in these counts.
 inline std::atomic<uint64_t> g_perk_pair_launches;
+// A main launch of the group schedule (round 30) that applies G blocks, G = 2, 4, 6 or 8, adds G / 2 to
+// g_perk_pair_launches and in proportion to everything above, and 1 to g_perk_group_launches[G / 2 - 1]
+// (fwx_test_perk_group).  The cross launches of its chain add nothing, as before.
+inline std::atomic<uint64_t> g_perk_group_launches[FWX_PERK_GROUP_CAP / 2];
 
 // Snapshot panels (W and Ct of one 64-pivot block) of the multi-pivot schedule: perk_kt_ws_bytes.  A blocking
 // entry point that holds a per-call context passes that context's workspace.  fwx_dev_relax* has no workspace
@@ -747,7 +792,7 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
     const bool tile = g_top == 32 && tile_min_n > 0 && n >= tile_min_n && n >= Bq;
     // The pair schedule (round 29; the comment above perk_pair_min_n): the stream's own scratch entry only, since a
     // caller's workspace holds one panel set and no look-ahead stream.
-    const int k_a = (k_begin + 2 * Bq - 1) / (2 * Bq) * (2 * Bq);     // the first pair starts on a tile boundary
+    const int k_a = (k_begin + 2 * Bq - 1) / (2 * Bq) * (2 * Bq);     // the first group starts on a tile boundary
     const int pair_min_n = perk_pair_min_n();
     bool pair = tile && !ws && pair_min_n > 0 && n >= pair_min_n && k_begin % Bq == 0 && k_end - k_a >= 4 * Bq;
     if (pair) {
@@ -759,19 +804,23 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
             pair = false;                                             // a captured graph gets no parallel branches
         }
     }
-    const int sets = pair ? 4 : 1;
+    // The group schedule (round 30): at most gmax blocks per main launch; 2 is the pair schedule itself.
+    const int gmax = pair ? perk_group_max(n) : 1;
+    const int sets = pair ? 2 * gmax : 1;
     PerkSide side;
     if (!ws) {
         const int rc0 = PerkScratch::get(s, (size_t)sets * perk_kt_ws_bytes<T>(n), &ws, pair ? &side : nullptr);
         if (rc0) return rc0;
     }
-    // `sets` panel sets: the W rows of all sets, then the Ct lines of all sets, so that with four sets -- block q of the
-    // pair schedule in set q & 3 -- the panels of a pair (2P, 2P + 1) are 128 contiguous rows of W and lines of Ct
+    // `sets` panel sets: the W rows of all sets, then the Ct lines of all sets.  The group schedule keeps two halves of
+    // gmax sets each, block i of group g in set (g & 1) * gmax + i, so that the panels of a group are contiguous rows of
+    // W and lines of Ct whatever its size and no group wraps; with gmax 2 that is round 29's "block q in set q & 3".
     T *const w_all = (T *)ws, *const ct_all = w_all + (size_t)sets * Bq * n;
     T *w = w_all, *ct = ct_all;                    // the set in use
-    auto use_set = [&](int q) {
-        w = w_all + (size_t)(q & (sets - 1)) * Bq * n;
-        ct = ct_all + (size_t)(q & (sets - 1)) * Bq * ld;
+    auto use_set = [&](int g, int i) {
+        const int at = (g & 1) * gmax + i;
+        w = w_all + (size_t)at * Bq * n;
+        ct = ct_all + (size_t)at * Bq * ld;
     };
 
     fwx::FusedArgs<T> pa;
@@ -797,7 +846,7 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
             if (groups >= 2) g_perk_wide_launches.fetch_add((uint64_t)groups / 2, std::memory_order_relaxed);
             if (groups >= 4) g_perk_deep_launches.fetch_add((uint64_t)groups / 4, std::memory_order_relaxed);
             if (groups >= 8) g_perk_tile_launches.fetch_add((uint64_t)groups / 8, std::memory_order_relaxed);
-            if (groups == 16) g_perk_pair_launches.fetch_add(1, std::memory_order_relaxed);
+            if (groups >= 16) g_perk_pair_launches.fetch_add((uint64_t)groups / 16, std::memory_order_relaxed);
         }
         return thr.tick(s);
     };
@@ -806,12 +855,15 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
         pa.k0 = k0; pa.bt = bt; pa.ct = ct; pa.side = st != s;
         return after(fwx::launch_fused_panels<T>(pa, w, nullptr, st), 4);
     };
-    // pivots [k0, k0 + bt) in one relax_tile launch, the panels from the set in use (bt 128: from it and the next one)
-    auto tiles = [&](int k0, int bt, hipStream_t st, fwx::TileSel sel, int tx) -> int {
+    // pivots [k0, k0 + bt) in one relax_tile launch, the panels from the set in use and the bt / 64 - 1 sets behind it
+    auto tiles = [&](int k0, int bt, hipStream_t st, fwx::TileSel sel, int tx, int tw, int te) -> int {
         if constexpr (std::is_same<T, float>::value) {
             a.k = k0; a.np = bt; a.w = w; a.ct = ct;
             a.flip = 0;                            // not read: a tile is loaded and stored once, in any order
-            return after(fwx::launch_relax_tile(a, st, sel, tx), sel == fwx::TILES_CROSS ? -1 : 3, bt / 8);
+            const hipError_t e = fwx::launch_relax_tile(a, st, sel, tx, tw, te);
+            if (e == hipSuccess && sel != fwx::TILES_CROSS && bt >= 2 * Bq)
+                g_perk_group_launches[bt / (2 * Bq) - 1].fetch_add(1, std::memory_order_relaxed);
+            return after(e, sel == fwx::TILES_CROSS ? -1 : 3, bt / 8);
         } else {
             return FWX_ERR_INVALID;                // (tile is false for f64)
         }
@@ -823,7 +875,7 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
             if (!panels_ready)
                 if (const int rc = panels(k0, bt, s)) return rc;
             if (tile && bt == Bq) {
-                if (const int rc = tiles(k0, bt, s, fwx::TILES_ALL, 0)) return rc;
+                if (const int rc = tiles(k0, bt, s, fwx::TILES_ALL, 0, 1, 0)) return rc;
                 t = bt;
             }
             for (int g = g_top; g >= 2; g >>= 1)
@@ -847,14 +899,21 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
         return FWX_OK;
     }
 
-    // ---- the pair schedule (the model is the double pass of fused_range) ------------
-    // Blocks are numbered from k_a; a leading block at k_begin = k_a - 64 is q = -1 and runs as above.  Pair P = blocks
-    // (2P, 2P + 1) = the 128 pivots of tile row / column X = k_a / 128 + P.  While the main launch applies pair P to
-    // every tile but the cross X + 1 (tile row and tile column of the next pair), the chain on the look-ahead stream
-    // takes that cross through pair P, takes the panels of block 2P + 2 from it, applies that block to it and takes the
-    // panels of block 2P + 3.  The next main launch folds block 2P + 2 into that cross a second time, with the same
-    // operands, which moves nothing.  An odd last block gets its panels the same way and one 64-pivot launch.
-    const int nfull = (k_end - k_a) / Bq, pairs = nfull / 2;
+    // ---- the group schedule (rounds 29 and 30; the model is the double pass of fused_range) ---
+    // Blocks are numbered from k_a; a leading block at k_begin = k_a - 64 runs as above.  Group g = `sz` blocks from block
+    // q (perk_group_size: 2, then 4, then 8 ... up to gmax, whatever even number is left at the end, a single odd block
+    // last) = the pivots of the tile rows / columns [x, x + sz / 2): its band.  While the main launch applies group g,
+    // the chain on the look-ahead stream prepares group g + 1: it takes the cross of band(g + 1) through group g in one
+    // launch, then block after block of group g + 1 takes the block's panels from that cross and applies the block to
+    // it.  With gmax > 2 it applies the group's last block as well: the band is then DONE -- through its own group --
+    // and neither the next main launch nor the next chain's first launch touches it again with those pivots.  The main
+    // launch of group g therefore steps over band(g) if that is done and over band(g + 1) if a chain runs beside it:
+    // one contiguous range of tile indices.
+    // Not done are the first group's band -- the work in front of the first main launch is round 29's chain(0), so the
+    // first main launch folds block 0 into it a second time, with the same operands, which moves nothing -- the band
+    // of an odd last block, which gets its panels the same way and one 64-pivot launch, and every band at gmax == 2,
+    // which is round 29's schedule launch for launch.
+    const int nfull = (k_end - k_a) / Bq;
     auto k_of = [&](int q) { return k_a + q * Bq; };
     bool chain_open = false;                       // launches are queued on side.s that `s` does not wait for yet
     auto join = [&]() -> hipError_t {
@@ -865,43 +924,50 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
     };
     auto run = [&]() -> int {
         if (k_begin < k_a) {
-            use_set(-1);
+            use_set(1, gmax - 1);
             if (const int rc = block(k_begin, Bq, false)) return rc;
         }
         // chain(0), on the caller's stream: the first pair's panels need block 0 applied to its own tile row and column
-        use_set(0);
+        use_set(0, 0);
         if (const int rc = panels(k_of(0), Bq, s)) return rc;
-        if (const int rc = tiles(k_of(0), Bq, s, fwx::TILES_CROSS, k_a / (2 * Bq))) return rc;
-        use_set(1);
+        if (const int rc = tiles(k_of(0), Bq, s, fwx::TILES_CROSS, k_a / (2 * Bq), 1, 0)) return rc;
+        use_set(0, 1);
         if (const int rc = panels(k_of(1), Bq, s)) return rc;
-        for (int P = 0; P < pairs; ++P) {
-            const int q = 2 * P, ahead = std::min(2, nfull - (q + 2));   // full blocks behind this pair, two at most
-            const int xn = k_of(q + 2) / (2 * Bq);                       // their tile row / column
-            if (ahead > 0) {
+        int g = 0, q = 0, sz = perk_group_size(nfull, 0, gmax);
+        bool done = false;                         // the chain has taken band(g) through group g
+        for (; sz >= 2; ++g) {
+            const int x = k_of(q) / (2 * Bq), xw = sz / 2;               // band(g)
+            const int qn = q + sz, szn = perk_group_size(nfull - qn, sz, gmax);
+            const int xn = x + xw, xnw = (szn + 1) / 2;                  // band(g + 1): adjacent
+            const bool done_n = szn >= 2 && gmax > 2;
+            if (szn > 0) {
                 FWX_HIP(hipEventRecord(side.main_done, s));              // the last main launch and chain precede
                 FWX_HIP(hipStreamWaitEvent(side.s, side.main_done, 0));
                 chain_open = true;
-                use_set(q);
-                if (const int rc = tiles(k_of(q), 2 * Bq, side.s, fwx::TILES_CROSS, xn)) return rc;
-                use_set(q + 2);
-                if (const int rc = panels(k_of(q + 2), Bq, side.s)) return rc;
-                if (ahead == 2) {
-                    if (const int rc = tiles(k_of(q + 2), Bq, side.s, fwx::TILES_CROSS, xn)) return rc;
-                    use_set(q + 3);
-                    if (const int rc = panels(k_of(q + 3), Bq, side.s)) return rc;
+                use_set(g, 0);                                           // what band(g) shares with it has seen group g
+                if (const int rc = tiles(k_of(q), sz * Bq, side.s, fwx::TILES_CROSS, xn, xnw, done ? xw : 0)) return rc;
+                for (int i = 0; i < szn; ++i) {
+                    use_set(g + 1, i);
+                    if (const int rc = panels(k_of(qn + i), Bq, side.s)) return rc;
+                    if (i + 1 < szn || done_n)
+                        if (const int rc = tiles(k_of(qn + i), Bq, side.s, fwx::TILES_CROSS, xn, xnw, 0)) return rc;
                 }
             }
-            use_set(q);
-            if (const int rc = tiles(k_of(q), 2 * Bq, s, ahead > 0 ? fwx::TILES_EXCEPT : fwx::TILES_ALL, xn)) return rc;
+            use_set(g, 0);
+            const int lo = done ? x : xn, hi = szn > 0 ? xn + xnw : xn;
+            if (const int rc = tiles(k_of(q), sz * Bq, s, lo < hi ? fwx::TILES_EXCEPT : fwx::TILES_ALL, lo, hi - lo, 0))
+                return rc;
             if (chain_open) FWX_HIP(join());
+            q = qn; sz = szn; done = done_n;
         }
-        if (nfull & 1) {                           // the odd last block: its panels are ready
-            use_set(nfull - 1);
-            if (const int rc = block(k_of(nfull - 1), Bq, true)) return rc;
+        if (sz == 1) {                             // the odd last block: its panels are ready
+            use_set(g, 0);
+            if (const int rc = block(k_of(q), Bq, true)) return rc;
+            ++q; ++g;
         }
-        if (k_of(nfull) < k_end) {                 // a ragged tail takes the ladder
-            use_set(nfull);
-            if (const int rc = block(k_of(nfull), k_end - k_of(nfull), false)) return rc;
+        if (k_of(q) < k_end) {                     // a ragged tail takes the ladder
+            use_set(g, 0);
+            if (const int rc = block(k_of(q), k_end - k_of(q), false)) return rc;
         }
         return FWX_OK;
     };

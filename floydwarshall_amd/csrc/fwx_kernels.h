@@ -139,13 +139,16 @@ template <typename T> struct RelaxKtArgs {
 };
 template <typename T> hipError_t launch_relax_kt(const RelaxKtArgs<T> &a, hipStream_t s);
 // relax_tile (round 26, fwx_fused.hip): pivots [k, k+np) in ONE pass on 128 x 128 register tiles, operands from LDS;
-// np == 64 or 128 (round 29: w and ct then hold 128 rows / lines), f32, updates == nullptr, n >= 64.  The fold is
-// chosen per tile and stage (max form where the tile's entries and operands allow it; fold_compare forces the compare
-// form).  flip, temporal_bytes, store_bytes and walk are not read: no result bit depends on them.
-// The tiles of a launch: all, all but tile row tx and tile column tx (the main launch beside a look-ahead chain), or
-// only those two (the cross: one launch of 2 * tiles - 1 workgroups at a raised wave priority).
+// np a multiple of 64 up to 512 (round 30; w and ct then hold np contiguous rows / lines), f32, updates == nullptr,
+// n >= 64.  The fold is chosen per tile and stage (max form where the tile's entries and operands allow it;
+// fold_compare forces the compare form).  flip, temporal_bytes, store_bytes and walk are not read: no result bit
+// depends on them.
+// The tiles of a launch: all; all but the tile rows and tile columns [tx, tx + tw) (the main launch beside a look-ahead
+// chain); or only those (the cross: one launch at a raised wave priority), and of those only the tiles whose other
+// index is not in [tx - te, tx): what the cross of the band in front has already taken through these pivots.
 enum TileSel { TILES_ALL = 0, TILES_EXCEPT = 1, TILES_CROSS = 2 };
-hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s, TileSel sel = TILES_ALL, int tx = 0);
+hipError_t launch_relax_tile(const RelaxKtArgs<float> &a, hipStream_t s, TileSel sel = TILES_ALL, int tx = 0,
+                             int tw = 1, int te = 0);
 
 // Whole solve (pivots [k_begin,k_end)) of an n <= FWX_SMALL_N matrix in one single-workgroup launch.
 #define FWX_SMALL_N 128

@@ -170,6 +170,21 @@ int fwx_test_perk_tile(uint64_t *launches, int reset);
  * fwx_test_perk_deep and as 2 by fwx_test_perk_tile -- which is cleared if reset.  Needs no device.  Not for
  * production use.                                                                                        */
 int fwx_test_perk_pair(uint64_t *launches, int reset);
+/* TEST HOOK for the group schedule (FWX_PERK_GROUP_MAX): returns what the variable parses to right now: 2, 4, 6 or 8,
+ * the most blocks a main launch of a call that takes the pair schedule applies (digits only, 2 to 8, an odd value
+ * counting as the even one below it), or 0 for any other text or unset: the default, which goes by the order of the
+ * matrix.  launches (if not NULL) receives four counters: the main launches of 2, 4, 6 and 8 blocks in this process
+ * (the pair schedule's own 128-pivot launches are the first) -- a launch of G blocks also counted as G / 2 by
+ * fwx_test_perk_pair and in proportion by the four hooks above it -- which are cleared if reset.  Needs no device.
+ * Not for production use.                                                                                */
+int fwx_test_perk_group(uint64_t *launches, int reset);
+/* TEST HOOK: the group sizes of a call of that schedule with nfull full blocks from its first tile boundary, at most
+ * gmax blocks per group (0: what a call on a matrix of order n would take: the variable, or the default for n).
+ * Writes up to cap sizes, in order, to size[] and the index of the first panel set of each group to set[] (either
+ * may be NULL; a group's panels take `size` sets from there and the call keeps 2 * gmax sets); an odd last block is a
+ * group of 1.  Returns the number of groups, or -1 for arguments out of range.  Needs no device.  Not for production
+ * use.                                                                                                   */
+int fwx_test_perk_group_plan(int n, int nfull, int gmax, int *size, int *set, int cap);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).

@@ -62,19 +62,23 @@ def main():
                 chains.append((c, v[i], v[i + 1]))
         if chains:
             lens = [len(c) for c, _, _ in chains]
-            steps = max(set(lens), key=lens.count)       # the usual chain; those at a call's edge differ
-            full = [x for x in chains if len(x[0]) == steps]
-            span = [max(e for _, e, _, _ in c) - c[0][0] for c, _, _ in full]
-            late = [max(e for _, e, _, _ in c) - (m[1] + t0) for c, m, _ in full]
-            print("side chain: %d chains of %d launches; span avg %.1f us, max %.1f us; its end against the end of the main "
-                  "launch beside it: avg %+.1f us, max %+.1f us" % (len(full), steps, sum(span) / len(span) / 1e3,
-                                                                   max(span) / 1e3, sum(late) / len(late) / 1e3, max(late) / 1e3))
-            for j in range(steps):
-                d = [c[j][1] - c[j][0] for c, _, _ in full]
-                w = [c[j][0] - (c[j - 1][1] if j else m[0] + t0) for c, m, _ in full]
-                print("  step %d  %-16s grid %8d  avg %7.1f us  max %7.1f us   starts %7.1f us after %s" %
-                      (j, full[0][0][j][2], full[0][0][j][3], sum(d) / len(d) / 1e3, max(d) / 1e3, sum(w) / len(w) / 1e3,
-                       "the step before ends" if j else "the main launch starts"))
+            # every kind of chain by its number of launches, the usual one first (the per-k engine's group schedule has
+            # one kind per group size; those at a call's edge differ as well)
+            for steps in sorted(set(lens), key=lambda n: -lens.count(n)):
+                full = [x for x in chains if len(x[0]) == steps]
+                span = [max(e for _, e, _, _ in c) - c[0][0] for c, _, _ in full]
+                late = [max(e for _, e, _, _ in c) - (m[1] + t0) for c, m, _ in full]
+                mdur = [m[1] - m[0] for _, m, _ in full]
+                print("side chain: %d chains of %d launches beside main launches of avg %.1f us; span avg %.1f us, max %.1f "
+                      "us; its end against the end of the main launch beside it: avg %+.1f us, max %+.1f us" %
+                      (len(full), steps, sum(mdur) / len(mdur) / 1e3, sum(span) / len(span) / 1e3, max(span) / 1e3,
+                       sum(late) / len(late) / 1e3, max(late) / 1e3))
+                for j in range(steps):
+                    d = [c[j][1] - c[j][0] for c, _, _ in full]
+                    w = [c[j][0] - (c[j - 1][1] if j else m[0] + t0) for c, m, _ in full]
+                    print("  step %d  %-16s grid %8d  avg %7.1f us  max %7.1f us   starts %7.1f us after %s" %
+                          (j, full[0][0][j][2], full[0][0][j][3], sum(d) / len(d) / 1e3, max(d) / 1e3,
+                           sum(w) / len(w) / 1e3, "the step before ends" if j else "the main launch starts"))
         if "--dump" in sys.argv:
             for s, e, name, gx, gy in rows[:60]:
                 print("    %9.1f %9.1f  %-24s %d" % ((s - t0) / 1e3, (e - t0) / 1e3, family(name), gx * gy))
