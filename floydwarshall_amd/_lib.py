@@ -180,7 +180,7 @@ _ARRAYS = [c_vp, c_vp, c_vp]                                # rate, next, hops
 _ITEMS = [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32]       # items, mat, src, dst, len_out, path_out, cap
 _SCRATCH = [c_vp, ctypes.c_size_t]                          # the large tier's scratch panels
 for _stem, _batch in (("batch", _UNIFORM), ("batch_mid", _UNIFORM), ("batch_large", _UNIFORM), ("ragged", _RAGGED),
-                      ("ragged_mid", _RAGGED)):
+                      ("ragged_mid", _RAGGED), ("ragged_large", _RAGGED)):
     for _t in ("f64", "f32"):                               # ..., updates_each, [the items,] opts
         SIGNATURES["fwx_solve_%s_%s" % (_stem, _t)] = (ctypes.c_int, _batch + _ARRAYS + [c_vp, _OPTS])
         SIGNATURES["fwx_solve_%s_lists_%s" % (_stem, _t)] = (ctypes.c_int, _batch + _ARRAYS + [c_vp] + _ITEMS + [_OPTS])
@@ -193,11 +193,13 @@ for _stem, _extra in (("batch", []), ("batch_mid", []), ("batch_large", _SCRATCH
     # count, n, stride, next0, trace, the items, scratch, stream
     SIGNATURES["fwx_dev_exact_paths_" + _stem] = (
         ctypes.c_int, _UNIFORM + [ctypes.c_int64, c_vp, _TRACE] + _ITEMS + [c_vp, c_vp])
-for _mid in ("", "_mid"):
-    SIGNATURES["fwx_ragged%s_plan" % _mid] = (ctypes.c_int, _RAGGED + [c_vp, c_vp, c_vp])
-    # count, dtype, the arrays, d_n_each, d_offset, d_order, tier_count, trace, d_updates_each, stream
+for _mid, _work, _extra in (("", [], []), ("_mid", [], []), ("_large", [c_vp], _SCRATCH)):
+    # count, n_each, offset_out, order_out, tier_count_out, [work_out]
+    SIGNATURES["fwx_ragged%s_plan" % _mid] = (ctypes.c_int, _RAGGED + [c_vp, c_vp, c_vp] + _work)
+    # count, dtype, the arrays, d_n_each, d_offset, d_order, tier_count, [work, d_work,] trace, d_updates_each,
+    # [scratch,] stream
     SIGNATURES["fwx_dev_solve_ragged" + _mid] = (
-        ctypes.c_int, [c_i32, c_i32] + _ARRAYS + [c_vp, c_vp, c_vp, c_vp, _TRACE, c_vp, c_vp])
+        ctypes.c_int, [c_i32, c_i32] + _ARRAYS + [c_vp, c_vp, c_vp, c_vp] + 2 * _work + [_TRACE, c_vp] + _extra + [c_vp])
     # count, d_n_each, d_offset, n_max, next0, trace, the items, scratch, stream
     SIGNATURES["fwx_dev_exact_paths_ragged" + _mid] = (
         ctypes.c_int, _RAGGED + [c_vp, c_i32, c_vp, _TRACE] + _ITEMS + [c_vp, c_vp])
@@ -208,6 +210,8 @@ SIGNATURES.update({
     "fwx_test_batch_large_min_n": (ctypes.c_int, []),
     "fwx_test_batch_large_geometry": (ctypes.c_int, [ctypes.POINTER(c_i32)]),
     "fwx_test_batch_lists_chunk": (ctypes.c_int64, [c_i32, c_i32]),
+    # count, large_count, work, scratch_bytes, group_first, cap, totals
+    "fwx_test_ragged_large_schedule": (ctypes.c_int, [c_i32, c_i32, c_vp, ctypes.c_size_t, c_vp, c_i32, c_vp]),
 })
 
 _LIB = None

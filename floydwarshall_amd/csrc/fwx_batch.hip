@@ -6,9 +6,9 @@
 //
 // A family of entry points is one BatchFamily value; every contract has one body that takes it:
 //   dev_solve_uniform      fwx_dev_solve_batch{,_mid,_large}{,_traced}
-//   dev_solve_ragged       fwx_dev_solve_ragged{,_mid}
+//   dev_solve_ragged       fwx_dev_solve_ragged{,_mid,_large}
 //   dev_exact_paths_batch  fwx_dev_exact_paths_batch{,_mid,_large}
-//   dev_exact_paths_ragged fwx_dev_exact_paths_ragged{,_mid}
+//   dev_exact_paths_ragged fwx_dev_exact_paths_ragged{,_mid,_large}
 //   solve_batch_host       every host form
 // and the tier of an order is decided in one place, BatchFamily::tier, which run_uniform acts on.
 #include <hip/hip_runtime.h>
@@ -29,6 +29,7 @@ using namespace fwxi;
 
 static_assert(FWX_BATCH_MID_MAX_N == FWX_MID_N, "fwx.h states the largest order of the mid tier");
 static_assert(FWX_BATCH_LARGE_MAX_N <= FWX_LARGE_N, "fwx.h states no order the large tier cannot take");
+static_assert(FWX_RAGGED_LARGE_WORK_ENTRIES(7) == 3 * 8, "three rows of count + 1 entries");
 static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1000) == FWX_LARGE_SCRATCH_BYTES(1000) &&
                   FWX_BATCH_LARGE_SCRATCH_BYTES(1) == FWX_LARGE_SCRATCH_BYTES(1),
               "fwx.h states the scratch the large tier lays out");
@@ -58,7 +59,7 @@ struct BatchFamily {
 };
 constexpr BatchFamily kPlain = {FWX_BATCH_MAX_N, false, false, 3};
 constexpr BatchFamily kMid = {FWX_BATCH_MID_MAX_N, true, false, 4};
-constexpr BatchFamily kLarge = {FWX_BATCH_LARGE_MAX_N, true, true, 0};
+constexpr BatchFamily kLarge = {FWX_BATCH_LARGE_MAX_N, true, true, 5};
 
 // body(rate as double * or float *), by the dtype code of a device form (checked by the caller).
 template <typename F> int with_dtype(int32_t dtype, void *rate, F &&body)
@@ -123,21 +124,35 @@ int run_uniform(const BatchFamily &f, int32_t count, int32_t n, T *rate, int32_t
     }
 }
 
-// A planned ragged batch, queued on s.  With four tiers the mid tier first -- its workgroups run longest -- then the
-// three small tiers.
+// What the fifth tier of a ragged batch runs on (fwx_dev_solve_ragged_large): the plan's work table on the host and on
+// the device, 3 * (count + 1) entries each, and the scratch panels.  Unused with fewer tiers.
+struct RaggedLarge {
+    const int64_t *work = nullptr, *d_work = nullptr;
+    void *scratch = nullptr;
+    size_t scratch_bytes = 0;
+};
+
+// A planned ragged batch, queued on s.  From four tiers up the mid tier first -- its workgroups run longest -- then the
+// three small tiers; with five the large tier's chain of launches (launch_ragged_large) behind them.
 template <typename T>
 int run_ragged(int tiers, int32_t count, T *rate, int32_t *next, int32_t *hops, const int32_t *d_n_each,
                const int64_t *d_offset, const int32_t *d_order, const int32_t *tier_count,
-               unsigned long long *d_updates_each, hipStream_t s, const fwx::PathLog &plog)
+               unsigned long long *d_updates_each, const RaggedLarge &lg, hipStream_t s, const fwx::PathLog &plog)
 {
-    if (tiers == 4) {
-        const long long small = (long long)tier_count[0] + tier_count[1] + tier_count[2];
-        const int rc = launch_status(fwx::launch_ragged_mid<T>(rate, next, hops, count, d_n_each, d_offset,
-                                                               d_order + small, tier_count[3], d_updates_each, s, plog));
-        if (rc || small == 0) return rc;
-    }
-    return launch_status(fwx::launch_ragged_solve<T>(rate, next, hops, count, d_n_each, d_offset, d_order, tier_count,
-                                                     d_updates_each, s, plog));
+    const long long small = (long long)tier_count[0] + tier_count[1] + tier_count[2];
+    int rc = FWX_OK;
+    if (tiers >= 4)
+        rc = launch_status(fwx::launch_ragged_mid<T>(rate, next, hops, count, d_n_each, d_offset, d_order + small,
+                                                     tier_count[3], d_updates_each, s, plog));
+    if (!rc && (tiers < 4 || small > 0))
+        rc = launch_status(fwx::launch_ragged_solve<T>(rate, next, hops, count, d_n_each, d_offset, d_order, tier_count,
+                                                       d_updates_each, s, plog));
+    if (!rc && tiers >= 5 && tier_count[4] > 0)
+        rc = launch_status(fwx::launch_ragged_large<T>(rate, next, hops, count, d_n_each, d_offset,
+                                                       d_order + small + tier_count[3], tier_count[4], lg.work,
+                                                       lg.d_work, (long long)count + 1, d_updates_each, lg.scratch,
+                                                       lg.scratch_bytes, s, plog));
+    return rc;
 }
 
 // Ragged batches: what the orders alone decide.  FWX_ERR_INVALID for a negative order; n_max is the largest
@@ -152,19 +167,25 @@ int ragged_orders(int32_t count, const int32_t *n_each, int32_t &n_max)
     return FWX_OK;
 }
 
-// The plan of a family's ragged form (fwx_ragged_plan: three tiers, fwx_ragged_mid_plan: four) for orders that
+// The plan of a family's ragged form (fwx_ragged_plan: three tiers, fwx_ragged_mid_plan: four, fwx_ragged_large_plan:
+// five -- large, n >= FWX_BATCH_LARGE_MIN_N, which wins over the mid tier as that does over the wave tier) for orders that
 // ragged_orders accepted and the family's limit admits: the packed offsets (count + 1 entries), the matrices with
 // n >= 1 grouped by tier -- wave (n <= FWX_BATCH_WAVE_MAX_N), 64-wide, 128-wide and, with four tiers, mid (n >=
 // FWX_BATCH_MID_MIN_N, which wins where the wave tier claims the order too) -- and within a tier by descending order,
 // ties by ascending index (a counting sort over the orders: the tier is monotone in the order), the rest of `order`
-// -1.  tier_count has f.ragged_tiers entries.  Any output may be null.
+// -1.  tier_count has f.ragged_tiers entries.  work (five tiers only): the large tier's work table, three rows of
+// count + 1 entries -- before slot m of its list the orders (row 0), the panel strips (row 1) and the sweep tiles
+// (row 2), the entries past the list repeating the totals.  Any output may be null.
 void ragged_plan(const BatchFamily &f, int32_t count, const int32_t *n_each, int64_t *offset, int32_t *order,
-                 int32_t *tier_count)
+                 int32_t *tier_count, int64_t *work = nullptr)
 {
     const int ntiers = f.ragged_tiers, wave_max_n = batch_wave_max_n(), mid_min_n = batch_mid_min_n();
-    auto tier_of = [&](int n) { return ntiers == 4 && n >= mid_min_n ? 3 : n <= wave_max_n ? 0 : n <= 64 ? 1 : 2; };
-    int64_t at[FWX_BATCH_MID_MAX_N + 2] = {0};  // at[n]: matrices of order n, then where the next one of order n goes
-    int32_t tiers[4] = {0, 0, 0, 0};
+    const int large_min_n = batch_large_min_n();
+    auto tier_of = [&](int n) {
+        return ntiers >= 5 && n >= large_min_n ? 4 : ntiers >= 4 && n >= mid_min_n ? 3 : n <= wave_max_n ? 0 : n <= 64 ? 1 : 2;
+    };
+    int64_t at[FWX_BATCH_LARGE_MAX_N + 2] = {0};  // at[n]: matrices of order n, then where the next one of order n goes
+    int32_t tiers[5] = {0, 0, 0, 0, 0};
     int64_t cells = 0;
     for (int32_t b = 0; b < count; ++b) {
         const int n = n_each[b];
@@ -174,6 +195,18 @@ void ragged_plan(const BatchFamily &f, int32_t count, const int32_t *n_each, int
     }
     if (offset) offset[count] = cells;
     if (tier_count) std::copy(tiers, tiers + ntiers, tier_count);
+    if (work && ntiers >= 5) {                  // the large list is the orders from the limit down, at[n] of each
+        int64_t *panel = work, *strip = work + count + 1, *tile = strip + count + 1;
+        int64_t m = 0;
+        panel[0] = strip[0] = tile[0] = 0;
+        for (int64_t n = f.max_n; n >= large_min_n; --n)
+            for (int64_t c = 0; c < at[n]; ++c, ++m) {
+                panel[m + 1] = panel[m] + n;
+                strip[m + 1] = strip[m] + (n + FWX_LARGE_S - 1) / FWX_LARGE_S;
+                tile[m + 1] = tile[m] + ((n + FWX_LARGE_TC - 1) / FWX_LARGE_TC) * ((n + FWX_LARGE_TR - 1) / FWX_LARGE_TR);
+            }
+        for (; m < count; ++m) { panel[m + 1] = panel[m]; strip[m + 1] = strip[m]; tile[m + 1] = tile[m]; }
+    }
     if (!order) return;
     int64_t pos = 0;
     for (int tier = 0; tier < ntiers; ++tier)
@@ -184,15 +217,15 @@ void ragged_plan(const BatchFamily &f, int32_t count, const int32_t *n_each, int
     for (int64_t i = pos; i < count; ++i) order[i] = -1;
 }
 
-// fwx_ragged_plan and fwx_ragged_mid_plan.
+// fwx_ragged_plan, fwx_ragged_mid_plan and fwx_ragged_large_plan.
 int ragged_plan_checked(const BatchFamily &f, int32_t count, const int32_t *n_each, int64_t *offset_out,
-                        int32_t *order_out, int32_t *tier_count_out)
+                        int32_t *order_out, int32_t *tier_count_out, int64_t *work_out = nullptr)
 {
     return guarded([&]() -> int {
         int32_t n_max = 0;
         if (count < 0 || (count > 0 && !n_each) || ragged_orders(count, n_each, n_max)) return FWX_ERR_INVALID;
         if (n_max > f.max_n) return FWX_ERR_UNSUPPORTED;
-        ragged_plan(f, count, n_each, offset_out, order_out, tier_count_out);
+        ragged_plan(f, count, n_each, offset_out, order_out, tier_count_out, work_out);
         return FWX_OK;
     });
 }
@@ -222,13 +255,22 @@ int dev_solve_uniform(const BatchFamily &f, int32_t count, int32_t n, int32_t dt
     });
 }
 
-// fwx_dev_solve_ragged and fwx_dev_solve_ragged_mid: one contract, the number of tiers apart.  The device forms cannot
-// read the orders: what they can decide is decided from the host arguments, and the kernels leave a matrix alone
-// whose order does not fit the tier it is listed in.
+// A host work table and scratch the large tier can run `listed` slots of a batch of `count` on (fwx.h).
+bool ragged_large_ok(int32_t count, int32_t listed, const RaggedLarge &lg)
+{
+    if (!lg.work || !lg.d_work) return false;
+    const fwx::RaggedLargeWork w(lg.work, (long long)count + 1);
+    return fwx::ragged_large_work_ok(w, listed) && large_scratch_ok(w.order_of(0), lg.scratch, lg.scratch_bytes);
+}
+
+// fwx_dev_solve_ragged, fwx_dev_solve_ragged_mid and fwx_dev_solve_ragged_large: one contract, the number of tiers
+// apart (lg: what the fifth runs on, judged only when it lists a matrix).  The device forms cannot read the orders:
+// what they can decide is decided from the host arguments, and the kernels leave a matrix alone whose order does not
+// fit the tier it is listed in.
 int dev_solve_ragged(const BatchFamily &f, int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
                      const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
                      const int32_t *tier_count, const fwx_trace *trace, unsigned long long *d_updates_each,
-                     void *stream)
+                     void *stream, const RaggedLarge &lg = RaggedLarge())
 {
     return guarded([&]() -> int {
         if (count < 0 || !tier_count || (dtype != FWX_F32 && dtype != FWX_F64)) return FWX_ERR_INVALID;
@@ -241,10 +283,11 @@ int dev_solve_ragged(const BatchFamily &f, int32_t count, int32_t dtype, void *r
         if (listed == 0) return FWX_OK;
         if (!rate || !d_n_each || !d_offset || !d_order || (hops && !next)) return FWX_ERR_INVALID;
         if (trace && (!next || !trace_complete(trace))) return FWX_ERR_INVALID;
+        if (f.ragged_tiers >= 5 && tier_count[4] > 0 && !ragged_large_ok(count, tier_count[4], lg)) return FWX_ERR_INVALID;
         if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
         return with_dtype(dtype, rate, [&](auto *r) {
             return run_ragged(f.ragged_tiers, count, r, next, hops, d_n_each, d_offset, d_order, tier_count,
-                              d_updates_each, (hipStream_t)stream, plog_of(trace));
+                              d_updates_each, lg, (hipStream_t)stream, plog_of(trace));
         });
     });
 }
@@ -268,7 +311,7 @@ int dev_exact_paths_batch(const BatchFamily &f, int32_t count, int32_t n, int64_
     });
 }
 
-// fwx_dev_exact_paths_ragged{,_mid}: the same over a ragged batch, n_max against the limit.
+// fwx_dev_exact_paths_ragged{,_mid,_large}: the same over a ragged batch, n_max against the limit.
 int dev_exact_paths_ragged(const BatchFamily &f, int32_t count, const int32_t *d_n_each, const int64_t *d_offset,
                            int32_t n_max, const int32_t *next0, const fwx_trace *trace, int32_t items,
                            const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
@@ -328,10 +371,13 @@ template <typename T> struct HostCall {
     // whole batch fits the pinned staging (see solve_host), in there
     struct Field { void *host; size_t bytes; void *dev; char *stage; } fld[3] = {};
     bool staged = false;
-    // ragged: the plan, packed for one copy -- count offsets, then count orders and the tier list (count) as int32 --
-    // and where it lies in the context's workspace, behind the counters
+    // ragged: the plan, packed for one copy -- count offsets, then count orders and the tier list (count) as int32,
+    // then, with five tiers, the large tier's work table -- and where it lies in the context's workspace, behind the
+    // counters
     std::vector<int64_t> plan{};
-    int32_t tiers[4] = {0, 0, 0, 0};
+    int32_t tiers[5] = {0, 0, 0, 0, 0};
+    size_t work_at = 0;                // of the work table in `plan`, in entries
+    const int64_t *d_work = nullptr;
     const int64_t *d_offset = nullptr;
     const int32_t *d_n_each = nullptr, *d_order = nullptr;
     bool counting = false;
@@ -375,9 +421,11 @@ template <typename T> struct HostCall {
         cells = (size_t)count * (size_t)n * (size_t)n;
         if (!form.ragged) return;
         std::vector<int64_t> offs((size_t)count + 1);
-        plan.resize(2 * (size_t)count);
+        const bool five = form.family.ragged_tiers >= 5;
+        work_at = 2 * (size_t)count;
+        plan.resize(work_at + (five ? FWX_RAGGED_LARGE_WORK_ENTRIES(count) : 0));
         int32_t *h_n = (int32_t *)(plan.data() + count), *h_order = h_n + count;
-        ragged_plan(form.family, count, form.n_each, offs.data(), h_order, tiers);
+        ragged_plan(form.family, count, form.n_each, offs.data(), h_order, tiers, five ? plan.data() + work_at : nullptr);
         std::copy(offs.begin(), offs.end() - 1, plan.begin());
         std::copy(form.n_each, form.n_each + count, h_n);
         cells = (size_t)offs[(size_t)count];
@@ -415,6 +463,7 @@ template <typename T> struct HostCall {
                 d_offset = (const int64_t *)((char *)ws + b_upd);
                 d_n_each = (const int32_t *)(d_offset + count);
                 d_order = d_n_each + count;
+                d_work = d_offset + work_at;
                 FWX_HIP(hipMemcpyAsync((void *)d_offset, plan.data(), plan.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
             }
         }
@@ -434,9 +483,13 @@ template <typename T> struct HostCall {
         // kBatchLargeScratchCap, larger batches run in groups; the buffer's own alignment, and every matrix's part a
         // multiple of 16 bytes -- then, with lists, the unsolved next-hops, the three trace arrays and the walk's
         // memory for one chunk of items (triples and lengths, lists, stacks)
+        // (ragged: the panels of every slot of the large tier -- there is one iff the largest order is routed there)
         const size_t per_large = FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)n);
         if (form.family.needs_scratch(n, op.k_begin, op.k_end))
-            b_scratch = per_large * std::min<size_t>((size_t)count, std::max<size_t>(1, kBatchLargeScratchCap / per_large));
+            b_scratch = form.ragged
+                ? std::min(FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)plan[work_at + (size_t)tiers[4]]),
+                           std::max(per_large, kBatchLargeScratchCap))
+                : per_large * std::min<size_t>((size_t)count, std::max<size_t>(1, kBatchLargeScratchCap / per_large));
         if (ls) {
             void *p = nullptr;
             chunk = std::min<long long>(batch_lists_chunk(n, ls->cap), ls->items);
@@ -462,8 +515,12 @@ template <typename T> struct HostCall {
     {
         T *r = (T *)fld[0].dev;
         int32_t *x = (int32_t *)fld[1].dev, *h = (int32_t *)fld[2].dev;
-        if (form.ragged)
-            return run_ragged(form.family.ragged_tiers, count, r, x, h, d_n_each, d_offset, d_order, tiers, d_upd, s, plog);
+        if (form.ragged) {
+            RaggedLarge lg;
+            if (tiers[4] > 0) lg = {plan.data() + work_at, d_work, d_scratch, b_scratch};
+            return run_ragged(form.family.ragged_tiers, count, r, x, h, d_n_each, d_offset, d_order, tiers, d_upd, lg, s,
+                              plog);
+        }
         return run_uniform(form.family, count, n, r, x, h, (int64_t)n * n, op.k_begin, op.k_end, d_upd, d_scratch,
                            b_scratch, s, plog);
     }
@@ -815,7 +872,100 @@ int fwx_dev_exact_paths_ragged_mid(int32_t count, const int32_t *d_n_each, const
                                   path_out, cap, scratch, stream);
 }
 
+// ---- ragged batches up to FWX_BATCH_LARGE_MAX_N: the fifth tier -----------------------------------------------------
+
+int fwx_ragged_large_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
+                          int32_t tier_count_out[5], int64_t *work_out)
+{
+    return ragged_plan_checked(kLarge, count, n_each, offset_out, order_out, tier_count_out, work_out);
+}
+
+int fwx_solve_ragged_large_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<double>({kLarge, true, n_each, nullptr}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_large_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_batch_host<float>({kLarge, true, n_each, nullptr}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_large_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                                     uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                     const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                     const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<double>({kLarge, true, n_each, &ls}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_solve_ragged_large_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                                     uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
+                                     const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
+                                     const fwx_opts *opts)
+{
+    const BatchLists ls = {items, mat, src, dst, len_out, path_out, cap};
+    return solve_batch_host<float>({kLarge, true, n_each, &ls}, count, 0, rate, next, hops, updates_each, opts);
+}
+
+int fwx_dev_solve_ragged_large(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                               const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                               const int32_t tier_count[5], const int64_t *work, const int64_t *d_work,
+                               const fwx_trace *trace, unsigned long long *d_updates_each, void *scratch,
+                               size_t scratch_bytes, void *stream)
+{
+    RaggedLarge lg;
+    lg.work = work;
+    lg.d_work = d_work;
+    lg.scratch = scratch;
+    lg.scratch_bytes = scratch_bytes;
+    return dev_solve_ragged(kLarge, count, dtype, rate, next, hops, d_n_each, d_offset, d_order, tier_count, trace,
+                            d_updates_each, stream, lg);
+}
+
+int fwx_dev_exact_paths_ragged_large(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                                     const int32_t *next0, const fwx_trace *trace, int32_t items, const int32_t *mat,
+                                     const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                                     int32_t cap, int32_t *scratch, void *stream)
+{
+    return dev_exact_paths_ragged(kLarge, count, d_n_each, d_offset, n_max, next0, trace, items, mat, src, dst, len_out,
+                                  path_out, cap, scratch, stream);
+}
+
 // ---- test hooks ---------------------------------------------------------------------------------------------------
+
+// The groups and grids launch_ragged_large makes of a host work table, counted with its own helpers.
+int fwx_test_ragged_large_schedule(int32_t count, int32_t large_count, const int64_t *work, size_t scratch_bytes,
+                                   int32_t *group_first, int32_t cap, int64_t totals[3])
+{
+    return guarded([&]() -> int {
+        if (count < 0 || large_count < 0 || large_count > count || cap < 0 || (cap > 0 && !group_first))
+            return FWX_ERR_INVALID;
+        int64_t sum[3] = {0, 0, 0};
+        int groups = 0;
+        if (large_count > 0) {
+            if (!work) return FWX_ERR_INVALID;
+            const fwx::RaggedLargeWork w(work, (long long)count + 1);
+            if (!fwx::ragged_large_work_ok(w, large_count) ||
+                scratch_bytes < FWX_BATCH_LARGE_SCRATCH_BYTES((size_t)w.order_of(0)))
+                return FWX_ERR_INVALID;
+            for (int m0 = 0; m0 < large_count; ++groups) {
+                const int m1 = fwx::ragged_large_group_end(w, m0, large_count, scratch_bytes);
+                if (groups < cap) group_first[groups] = m0;
+                fwx::ragged_large_blocks(w, m0, m1, [&](int, int active) {
+                    sum[0] += 2;
+                    sum[1] += w.strip[m0 + active] - w.strip[m0];
+                    sum[2] += w.tile[m0 + active] - w.tile[m0];
+                });
+                m0 = m1;
+            }
+        }
+        if (totals) std::copy(sum, sum + 3, totals);
+        return groups;
+    });
+}
 
 int fwx_test_batch_wave_max_n(void) { return batch_wave_max_n(); }
 

@@ -235,6 +235,63 @@ hipError_t launch_ragged_mid(T *rate, int32_t *next, int32_t *hops, int count, c
                              const int64_t *offset, const int32_t *order, long long listed,
                              unsigned long long *updates_each, hipStream_t s, PathLog plog = PathLog());
 
+// The fifth tier of a ragged batch (fwx_large.hip): the `listed` matrices whose ids stand in `order` (device; the large
+// tier's part of what fwx_ragged_large_plan gives, sorted by descending order), each of an order 1 ... FWX_LARGE_N,
+// several workgroups per matrix on launch_batch_large's bodies.  `work` is the plan's work table on the HOST, three
+// rows `row` entries apart (RaggedLargeWork), d_work the same contents on the device.  Slot m of the list has the order
+// panel[m + 1] - panel[m]; a GROUP is a maximal run of consecutive slots whose panels, 512 bytes per order and slot m
+// at 512 * (panel[m] - panel[first slot of the group]), fit scratch_bytes and whose tiles number less than 2^31; the
+// groups run one after the other on s.  Per pivot block q of a group, q < ceil(n_first / B), one panel and one sweep
+// launch over the ACTIVE PREFIX, the group's slots with n > q * B, each a linear grid of strip[m0 + active] -
+// strip[m0] resp. tile[...] workgroups that find their slot by binary search in the device row: 2 * ceil(n_first / B)
+// launches per group, and a matrix that is done costs nothing afterwards.  With plog, one launch over the tiles of all
+// slots writes -1 to the n x n cells of `last` before the first group.  Index arrays, layout, counters (by matrix id)
+// and plog as launch_ragged_mid.  A workgroup whose id lies outside [0, count), whose order lies outside 1 ...
+// FWX_LARGE_N or whose panels would end past scratch_bytes stays idle, and none touches anything outside the n x n
+// cells of its matrix or the scratch, whatever the device tables hold.  hipErrorInvalidValue for a host table that
+// ragged_large_work_ok refuses and for scratch that is null, misaligned or smaller than the first slot's.
+struct RaggedLargeWork {
+    const int64_t *panel, *strip, *tile;
+    RaggedLargeWork(const int64_t *work, long long row) : panel(work), strip(work + row), tile(work + 2 * row) {}
+    int order_of(int m) const { return (int)(panel[m + 1] - panel[m]); }
+};
+// A host table is usable: orders 1 ... FWX_LARGE_N, descending, and the strip and tile rows those of the geometry.
+inline bool ragged_large_work_ok(const RaggedLargeWork &w, int listed)
+{
+    for (int m = 0; m < listed; ++m) {
+        const int64_t n = w.panel[m + 1] - w.panel[m];
+        if (n < 1 || n > FWX_LARGE_N || (m > 0 && n > w.panel[m] - w.panel[m - 1])) return false;
+        const int64_t tiles = ((n + FWX_LARGE_TC - 1) / FWX_LARGE_TC) * ((n + FWX_LARGE_TR - 1) / FWX_LARGE_TR);
+        if (w.strip[m + 1] - w.strip[m] != (n + FWX_LARGE_S - 1) / FWX_LARGE_S || w.tile[m + 1] - w.tile[m] != tiles)
+            return false;
+    }
+    return true;
+}
+// One past the last slot of the group that starts at slot m0 (m0 itself: not even that slot fits).
+inline int ragged_large_group_end(const RaggedLargeWork &w, int m0, int listed, size_t scratch_bytes)
+{
+    int m1 = m0;
+    while (m1 < listed && (uint64_t)(w.panel[m1 + 1] - w.panel[m0]) <= scratch_bytes / FWX_LARGE_SCRATCH_BYTES(1) &&
+           w.tile[m1 + 1] - w.tile[m0] < ((int64_t)1 << 31))
+        ++m1;
+    return m1;
+}
+// f(q, active) for every pivot block q of the group [m0, m1): active = its slots with n > q * B, a prefix.
+template <typename F> void ragged_large_blocks(const RaggedLargeWork &w, int m0, int m1, F &&f)
+{
+    int active = m1 - m0;
+    const int blocks = (w.order_of(m0) + FWX_LARGE_B - 1) / FWX_LARGE_B;
+    for (int q = 0; q < blocks; ++q) {
+        while (active > 0 && w.order_of(m0 + active - 1) <= q * FWX_LARGE_B) --active;
+        f(q, active);
+    }
+}
+template <typename T>
+hipError_t launch_ragged_large(T *rate, int32_t *next, int32_t *hops, int count, const int32_t *n_each,
+                               const int64_t *offset, const int32_t *order, int listed, const int64_t *work,
+                               const int64_t *d_work, long long row, unsigned long long *updates_each, void *scratch,
+                               size_t scratch_bytes, hipStream_t s, PathLog plog = PathLog());
+
 template <typename T>
 hipError_t launch_snapshot_row(T *dst, const T *src, int32_t *hdst, const int32_t *hsrc, int n,
                                hipStream_t s);

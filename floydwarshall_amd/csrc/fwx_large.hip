@@ -54,6 +54,15 @@
 // Scratch: FWX_LARGE_SCRATCH_BYTES(n) per matrix of the group, laid out for the dtype and field set of the call
 // (W, Ct as T, then the int32 panels), an upper bound: 2 panels x B rows x n columns x 16 bytes.  launch_batch_large
 // solves the batch in groups of as many matrices as the scratch holds, one group after the other on the stream.
+//
+// The ragged form (launch_ragged_large; fwx_kernels.h has the contract): matrices of DIFFERENT orders, the fifth tier of
+// a ragged batch.  The bodies of the three kernels are __device__ functions that take what a kernel decides -- n, the
+// element offset, the scratch panels, k0, bt, the strip or tile, the counter slot -- by value; the uniform kernels call
+// them with what their grid says, large_panel_ragged / large_sweep_ragged / large_fill_last_ragged with what the
+// workgroup finds in the plan's tables.  Their grid is LINEAR over the active prefix of one group of the list, which is
+// sorted by descending order: at the block that starts at k0 the matrices with n > k0 are a prefix, and a matrix that
+// is done gets no workgroup.  Everything such a workgroup decides on is workgroup-uniform and decided before its
+// first barrier; the trip counts of the bodies stay functions of (n, k0, geometry) alone.
 #include "fwx_kernels.h"
 
 #include <algorithm>
@@ -85,12 +94,11 @@ template <typename T> struct LargePanels {
     T *W, *Ct;
     int32_t *WN, *CNt, *WH, *CHt;
 };
-template <typename T>
-__device__ __forceinline__ LargePanels<T> large_panels(char *scratch, size_t per_matrix, unsigned b, int n)
+template <typename T> __device__ __forceinline__ LargePanels<T> large_panels(char *base, int n)
 {
     const size_t bn = (size_t)kLargeB * (size_t)n;
     LargePanels<T> p;
-    p.W = (T *)(scratch + (size_t)b * per_matrix);
+    p.W = (T *)base;
     p.Ct = p.W + bn;
     p.WN = (int32_t *)(p.Ct + bn);
     p.CNt = p.WN + bn;
@@ -113,22 +121,119 @@ __global__ __launch_bounds__(kFillThreads) void large_fill_last(int32_t *last, i
     }
 }
 
-// The trace arguments stand last: an instantiation without HAS_LAST reads none of them.
+// ---- the ragged form: where a workgroup of a linear grid works -------------------------------------------------------
+// A ragged launch covers the ACTIVE PREFIX of one group of the large tier's list: the slots [m0, m0 + active), sorted
+// by descending order, so that the matrices with n > k0 are a prefix.  `base` is a row of the work table
+// (fwx_ragged_large_plan: strip_base for the panel launch, tile_base for the sweep and the fill), base[m] the units of
+// the slots before m; the grid has base[m0 + active] - base[m0] workgroups.  Workgroup w belongs to the last slot
+// of the prefix whose base, counted from the group's, is <= w: a binary search over that prefix only, every load
+// through a workgroup-uniform address (scalar loads), ceil(log2(active)) of them whatever the row holds.  `local`
+// receives w counted from the slot's own base -- a row that does not belong to the call makes it anything, which the
+// callers test against the order of the matrix they find.
+__device__ __forceinline__ int large_slot(const int64_t *base, int m0, int active, long long w, long long &local)
+{
+    const long long b0 = base[m0];
+    int lo = 0, hi = active;                                  // the slot is one of [lo, hi)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (base[m0 + mid] - b0 <= w) lo = mid; else hi = mid;
+    }
+    local = w - (base[m0 + lo] - b0);
+    return m0 + lo;
+}
+
+// A workgroup-uniform value in scalar registers, whatever the compiler could prove about it: the bodies keep n, the
+// offsets and the tile coordinates there in the uniform kernels, and the ragged ones must not spend vector registers
+// on them (the sweep sits at 94 of the 96 that five waves per SIMD allow).
+__device__ __forceinline__ int large_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ size_t large_uniform(size_t v)
+{
+    return (size_t)(unsigned)large_uniform((int)(unsigned)v) | (size_t)(unsigned)large_uniform((int)(unsigned)(v >> 32)) << 32;
+}
+
+// What a ragged workgroup finds at its slot: the matrix (id, order, element offset) and its scratch panels.  ok is
+// false -- the workgroup leaves, before its first barrier and without touching memory -- for an id outside
+// [0, count), an order outside 1 ... FWX_LARGE_N, or (with_scratch) panels that would not end within scratch_bytes.
+// Everything here is workgroup-uniform.
+struct LargeSlot {
+    bool ok;
+    int id, n;
+    size_t off;
+    char *panels;
+};
+__device__ __forceinline__ LargeSlot large_slot_matrix(int m, int m0, int count, const int32_t *n_each,
+                                                       const int64_t *offset, const int32_t *order,
+                                                       const int64_t *panel_base, char *scratch, size_t scratch_bytes,
+                                                       bool with_scratch)
+{
+    LargeSlot r{false, 0, 0, 0, nullptr};
+    r.id = order[m];
+    if ((unsigned)r.id >= (unsigned)count) return r;
+    r.n = n_each[r.id];
+    if (r.n <= 0 || r.n > FWX_LARGE_N) return r;
+    r.id = large_uniform(r.id);
+    r.n = large_uniform(r.n);
+    r.off = large_uniform((size_t)offset[r.id]);
+    if (with_scratch) {
+        const long long at = panel_base[m] - panel_base[m0];  // orders before the slot, within its group
+        const size_t bytes = FWX_LARGE_SCRATCH_BYTES(r.n);
+        if (at < 0 || scratch_bytes < bytes || (unsigned long long)at > (scratch_bytes - bytes) / FWX_LARGE_SCRATCH_BYTES(1))
+            return r;
+        r.panels = scratch + large_uniform((size_t)at * FWX_LARGE_SCRATCH_BYTES(1));
+    }
+    r.ok = true;
+    return r;
+}
+
+// Tile `local` of an order-n matrix, its tiles numbered row by row, ceil(n / TC) to a row: false where there is none.
+__device__ __forceinline__ bool large_tile_of(int n, long long local, int &tx, int &ty)
+{
+    const int tcols = (n + kLargeTC - 1) / kLargeTC, trows = (n + kLargeTR - 1) / kLargeTR;
+    if (local < 0 || local >= (long long)(tcols * trows)) return false;
+    ty = large_uniform((int)local / tcols);
+    tx = large_uniform((int)local - ty * tcols);
+    return true;
+}
+
+// -1 to the cells of `last` of one sweep tile (tx, ty) of the order-n matrix at `last`: the ragged fill, one workgroup
+// of kSweepThreads per tile, a row of the tile per pass.
+__device__ __forceinline__ void large_fill_tile(int32_t *last, int n, int tx, int ty)
+{
+    const int j = tx * kLargeTC + (int)threadIdx.x, i0 = ty * kLargeTR;
+    if (j >= n) return;
+    for (int r = 0; r < kLargeTR && i0 + r < n; ++r) last[(size_t)(i0 + r) * n + j] = -1;
+}
+
+// All L slots of the large tier, one workgroup per sweep tile: exactly the n_b x n_b cells of every listed matrix.
+__global__ __launch_bounds__(kSweepThreads) void large_fill_last_ragged(int32_t *last, int count,
+                                                                        const int32_t *n_each, const int64_t *offset,
+                                                                        const int32_t *order,
+                                                                        const int64_t *tile_base, int m0, int active)
+{
+    long long local;
+    const int m = large_slot(tile_base, m0, active, (long long)blockIdx.x, local);
+    const LargeSlot sl = large_slot_matrix(m, m0, count, n_each, offset, order, nullptr, nullptr, 0, false);
+    int tx, ty;
+    if (!sl.ok || !large_tile_of(sl.n, local, tx, ty)) return;
+    large_fill_tile(last + sl.off, sl.n, tx, ty);
+}
+
+// The panel phase of pivot block [k0, k0 + bt) on strip s0 of the order-n matrix at element `off` of the arrays, its
+// scratch panels at `panels`.  Shared by the uniform and the ragged kernel: everything a kernel decides comes in by
+// value, and every barrier is reached by the whole workgroup with a trip count that depends on bt alone.  The trace
+// arguments stand last: an instantiation without HAS_LAST reads none of them.
 template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
-__global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, const int32_t *next, const int32_t *hops,
-                                                             int n, long long stride, int k0, int bt, char *scratch,
-                                                             size_t per_matrix, PathLog plog)
+__device__ __forceinline__ void large_panel_body(const T *rate, const int32_t *next, const int32_t *hops, int n,
+                                                 size_t off, char *panels, int k0, int bt, int s0, const PathLog &plog)
 {
     static_assert(HAS_NEXT || !HAS_LAST, "the trace goes with next");
-    constexpr int B = kLargeB, S = kLargeS, Q = kLargePitch;
+    constexpr int B = kLargeB, Q = kLargePitch;
     __shared__ T W[B][Q], C[B][Q];
     __shared__ int32_t WN[HAS_NEXT ? B : 1][HAS_NEXT ? Q : 1], CN[HAS_NEXT ? B : 1][HAS_NEXT ? Q : 1];
     __shared__ int32_t WH[HAS_HOPS ? B : 1][HAS_HOPS ? Q : 1], CH[HAS_HOPS ? B : 1][HAS_HOPS ? Q : 1];
     __shared__ int32_t AR[HAS_LAST ? B : 1][HAS_LAST ? Q : 1], AC[HAS_LAST ? B : 1][HAS_LAST ? Q : 1];
 
     const int tid = threadIdx.x;
-    const int s0 = (int)blockIdx.x * S;
-    const size_t off = (size_t)blockIdx.y * (size_t)stride;
     rate += off;
     if constexpr (HAS_NEXT) next += off;
     if constexpr (HAS_HOPS) hops += off;
@@ -189,7 +294,7 @@ __global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, cons
     if (wave < bt && lane >= B) {
         const int x = s0 + lane - B;
         if (x < n) {
-            const LargePanels<T> pn = large_panels<T>(scratch, per_matrix, blockIdx.y, n);
+            const LargePanels<T> pn = large_panels<T>(panels, n);
             const size_t e = (size_t)wave * n + x;
             pn.W[e] = W[wave][lane];
             pn.Ct[e] = C[wave][lane];
@@ -207,10 +312,42 @@ __global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, cons
 }
 
 template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
-__global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *next, int32_t *hops, int n,
-                                                             long long stride, int bt, char *scratch,
-                                                             size_t per_matrix, unsigned long long *updates,
-                                                             int32_t *last, int k0)
+__global__ __launch_bounds__(kPanelThreads) void large_panel(const T *rate, const int32_t *next, const int32_t *hops,
+                                                             int n, long long stride, int k0, int bt, char *scratch,
+                                                             size_t per_matrix, PathLog plog)
+{
+    large_panel_body<T, HAS_NEXT, HAS_HOPS, HAS_LAST>(rate, next, hops, n, (size_t)blockIdx.y * (size_t)stride,
+                                                      scratch + (size_t)blockIdx.y * per_matrix, k0, bt,
+                                                      (int)blockIdx.x * kLargeS, plog);
+}
+
+// Ragged batch, large tier: workgroup w of the launch on one strip of the matrix large_slot finds for it, of the order
+// and at the offset the index arrays give, bt = min(B, n - k0).  Every test is workgroup-uniform and comes before the
+// body's first barrier and first memory access: all 1024 threads leave or none does.
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
+__global__ __launch_bounds__(kPanelThreads) void large_panel_ragged(const T *rate, const int32_t *next,
+                                                                    const int32_t *hops, int count,
+                                                                    const int32_t *n_each, const int64_t *offset,
+                                                                    const int32_t *order, const int64_t *panel_base,
+                                                                    const int64_t *strip_base, int m0, int active,
+                                                                    int k0, char *scratch, size_t scratch_bytes,
+                                                                    PathLog plog)
+{
+    long long local;
+    const int m = large_slot(strip_base, m0, active, (long long)blockIdx.x, local);
+    const LargeSlot sl = large_slot_matrix(m, m0, count, n_each, offset, order, panel_base, scratch, scratch_bytes, true);
+    if (!sl.ok || k0 >= sl.n || local < 0 || local * kLargeS >= sl.n) return;
+    large_panel_body<T, HAS_NEXT, HAS_HOPS, HAS_LAST>(rate, next, hops, sl.n, sl.off, sl.panels, k0,
+                                                      min(kLargeB, sl.n - k0), large_uniform((int)local * kLargeS), plog);
+}
+
+// The sweep of pivot block [k0, k0 + bt) on tile (tx, ty) of the order-n matrix at element `off`, from the panels at
+// `panels`; the workgroup's count goes to updates[slot].  Shared by the uniform and the ragged kernel like the panel
+// body: i0 < n is the caller's to see to.
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
+__device__ __forceinline__ void large_sweep_body(T *rate, int32_t *next, int32_t *hops, int32_t *last, int n,
+                                                 size_t off, char *panels, int k0, int bt, int tx, int ty,
+                                                 unsigned long long *updates, unsigned int slot)
 {
     static_assert(HAS_NEXT || !HAS_LAST, "the trace goes with next");
     constexpr int B = kLargeB, TR = kLargeTR, TC = kLargeTC;
@@ -219,14 +356,13 @@ __global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *n
     __shared__ unsigned int s_cnt;
 
     const int tid = threadIdx.x;
-    const int j = (int)blockIdx.x * TC + tid, i0 = (int)blockIdx.y * TR;
+    const int j = tx * TC + tid, i0 = ty * TR;
     const int rows = min(TR, n - i0);                         // >= 1: the grid covers [0, n) and no more
-    const size_t off = (size_t)blockIdx.z * (size_t)stride;
     rate += off;
     if constexpr (HAS_NEXT) next += off;
     if constexpr (HAS_HOPS) hops += off;
     if constexpr (HAS_LAST) last += off;
-    const LargePanels<T> pn = large_panels<T>(scratch, per_matrix, blockIdx.z, n);
+    const LargePanels<T> pn = large_panels<T>(panels, n);
 
     if (tid == 0) s_cnt = 0;
     for (int e = tid; e < B * TR; e += kSweepThreads) {       // lane on (t, row), row fastest
@@ -244,7 +380,7 @@ __global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *n
 
     unsigned int mine = 0;                                    // a WAVE total (scalar)
     // a wave whose 64 columns all lie past the edge has nothing to fold (wave-uniform)
-    if ((int)blockIdx.x * TC + (tid & ~63) < n) {
+    if (tx * TC + (tid & ~63) < n) {
         for (int r0 = 0; r0 < rows; r0 += kLargeRows) {
             // kLargeRows rows together, t outermost: independent compare chains for a wave that is alone on its SIMD.
             // +inf where a lane has no entry (past an edge, or the diagonal's): no candidate compares greater, and the
@@ -288,8 +424,38 @@ __global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *n
     if (updates) {                                            // workgroup-uniform
         if (mine && (tid & 63) == 0) atomicAdd(&s_cnt, mine);
         __syncthreads();
-        if (tid == 0 && s_cnt) atomicAdd(&updates[blockIdx.z], (unsigned long long)s_cnt);
+        if (tid == 0 && s_cnt) atomicAdd(&updates[slot], (unsigned long long)s_cnt);
     }
+}
+
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
+__global__ __launch_bounds__(kSweepThreads) void large_sweep(T *rate, int32_t *next, int32_t *hops, int n,
+                                                             long long stride, int bt, char *scratch,
+                                                             size_t per_matrix, unsigned long long *updates,
+                                                             int32_t *last, int k0)
+{
+    large_sweep_body<T, HAS_NEXT, HAS_HOPS, HAS_LAST>(rate, next, hops, last, n, (size_t)blockIdx.z * (size_t)stride,
+                                                      scratch + (size_t)blockIdx.z * per_matrix, k0, bt,
+                                                      (int)blockIdx.x, (int)blockIdx.y, updates, blockIdx.z);
+}
+
+// Ragged batch, large tier: workgroup w of the launch on one tile of its matrix, the tiles of a matrix numbered row by
+// row, ceil(n / TC) of its OWN order to a row; U goes to updates[id].  Tests as in large_panel_ragged.
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool HAS_LAST>
+__global__ __launch_bounds__(kSweepThreads) void large_sweep_ragged(T *rate, int32_t *next, int32_t *hops, int count,
+                                                                    const int32_t *n_each, const int64_t *offset,
+                                                                    const int32_t *order, const int64_t *panel_base,
+                                                                    const int64_t *tile_base, int m0, int active,
+                                                                    int k0, char *scratch, size_t scratch_bytes,
+                                                                    unsigned long long *updates, int32_t *last)
+{
+    long long local;
+    const int m = large_slot(tile_base, m0, active, (long long)blockIdx.x, local);
+    const LargeSlot sl = large_slot_matrix(m, m0, count, n_each, offset, order, panel_base, scratch, scratch_bytes, true);
+    int tx, ty;
+    if (!sl.ok || k0 >= sl.n || !large_tile_of(sl.n, local, tx, ty)) return;
+    large_sweep_body<T, HAS_NEXT, HAS_HOPS, HAS_LAST>(rate, next, hops, last, sl.n, sl.off, sl.panels, k0,
+                                                      min(kLargeB, sl.n - k0), tx, ty, updates, (unsigned int)sl.id);
 }
 
 }  // namespace
@@ -347,6 +513,67 @@ hipError_t launch_batch_large(T *rate, int32_t *next, int32_t *hops, int count, 
     }
     return hipSuccess;
 }
+
+template <typename T>
+hipError_t launch_ragged_large(T *rate, int32_t *next, int32_t *hops, int count, const int32_t *n_each,
+                               const int64_t *offset, const int32_t *order, int listed, const int64_t *work,
+                               const int64_t *d_work, long long row, unsigned long long *updates_each, void *scratch,
+                               size_t scratch_bytes, hipStream_t s, PathLog plog)
+{
+    if (count < 0 || listed < 0 || listed > count || row <= listed || (hops && !next)) return hipErrorInvalidValue;
+    if (listed == 0) return hipSuccess;
+    const bool traced = plog.last != nullptr;
+    if (!rate || !n_each || !offset || !order || !work || !d_work || (traced && (!next || !plog.at_col || !plog.at_row)))
+        return hipErrorInvalidValue;
+    const RaggedLargeWork w(work, row);
+    if (!ragged_large_work_ok(w, listed)) return hipErrorInvalidValue;
+    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < FWX_LARGE_SCRATCH_BYTES(w.order_of(0)))
+        return hipErrorInvalidValue;
+    const int64_t *d_panel = d_work, *d_strip = d_work + row, *d_tile = d_work + 2 * row;
+    char *sc = (char *)scratch;
+    // the trace's step 0, over every group at once, in runs of less than 2^31 tiles
+    for (int m0 = 0; traced && m0 < listed;) {
+        const int m1 = ragged_large_group_end(w, m0, listed, ~(size_t)0);
+        hipLaunchKernelGGL(large_fill_last_ragged, dim3((unsigned)(w.tile[m1] - w.tile[m0])), dim3(kSweepThreads), 0, s,
+                           plog.last, count, n_each, offset, order, d_tile, m0, m1 - m0);
+        m0 = m1;
+    }
+    for (int m0 = 0; m0 < listed;) {
+        const int m1 = ragged_large_group_end(w, m0, listed, scratch_bytes);   // > m0: the orders descend
+        hipError_t e = hipSuccess;
+        ragged_large_blocks(w, m0, m1, [&](int q, int active) {
+            if (e != hipSuccess) return;
+            const int k0 = q * kLargeB;
+            const dim3 strips((unsigned)(w.strip[m0 + active] - w.strip[m0]));
+            const dim3 tiles((unsigned)(w.tile[m0 + active] - w.tile[m0]));
+#define FWX_RAGGED_LARGE(HN, HH, HL)                                                                                   \
+    do {                                                                                                               \
+        hipLaunchKernelGGL((large_panel_ragged<T, HN, HH, HL>), strips, dim3(kPanelThreads), 0, s, rate, next, hops,   \
+                           count, n_each, offset, order, d_panel, d_strip, m0, active, k0, sc, scratch_bytes, plog);   \
+        hipLaunchKernelGGL((large_sweep_ragged<T, HN, HH, HL>), tiles, dim3(kSweepThreads), 0, s, rate, next, hops,    \
+                           count, n_each, offset, order, d_panel, d_tile, m0, active, k0, sc, scratch_bytes,           \
+                           updates_each, plog.last);                                                                   \
+    } while (0)
+            if (traced && hops) FWX_RAGGED_LARGE(true, true, true);
+            else if (traced) FWX_RAGGED_LARGE(true, false, true);
+            else if (hops) FWX_RAGGED_LARGE(true, true, false);
+            else if (next) FWX_RAGGED_LARGE(true, false, false);
+            else FWX_RAGGED_LARGE(false, false, false);
+#undef FWX_RAGGED_LARGE
+            e = hipGetLastError();
+        });
+        if (e != hipSuccess) return e;
+        m0 = m1;
+    }
+    return hipSuccess;
+}
+
+template hipError_t launch_ragged_large<float>(float *, int32_t *, int32_t *, int, const int32_t *, const int64_t *,
+                                               const int32_t *, int, const int64_t *, const int64_t *, long long,
+                                               unsigned long long *, void *, size_t, hipStream_t, PathLog);
+template hipError_t launch_ragged_large<double>(double *, int32_t *, int32_t *, int, const int32_t *, const int64_t *,
+                                                const int32_t *, int, const int64_t *, const int64_t *, long long,
+                                                unsigned long long *, void *, size_t, hipStream_t, PathLog);
 
 template hipError_t launch_batch_large<float>(float *, int32_t *, int32_t *, int, int, long long, int, int,
                                               unsigned long long *, void *, size_t, hipStream_t, PathLog);

@@ -23,7 +23,8 @@ __all__ = ["solve", "solve_batch", "dev_solve_batch", "solve_batch_lists", "dev_
            "dev_exact_paths_batch_large",
            "dev_solve_batch_mid_traced", "dev_exact_paths_batch_mid", "ragged_plan", "solve_ragged", "solve_ragged_lists", "dev_solve_ragged",
            "dev_exact_paths_ragged", "ragged_mid_plan", "solve_ragged_mid", "solve_ragged_mid_lists",
-           "dev_solve_ragged_mid", "dev_exact_paths_ragged_mid", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
+           "dev_solve_ragged_mid", "dev_exact_paths_ragged_mid", "ragged_large_plan", "solve_ragged_large",
+           "solve_ragged_large_lists", "dev_solve_ragged_large", "dev_exact_paths_ragged_large", "follow_path", "dev_follow_paths", "dev_check_nonneg", "dev_domain_bits", "dev_solve_fused",
            "dev_solve", "DeviceMatrix", "dev_relax", "dev_panel", "dev_panel_snap",
            "dev_relax_fused", "FusedWorkspace", "Trace", "FWX_FUSED_BLOCK", "device_count",
            "FwxError", "FWX_ENGINE_AUTO", "FWX_ENGINE_PERK", "FWX_ENGINE_FUSED",
@@ -396,7 +397,17 @@ def ragged_mid_plan(n_each):
     return _ragged_plan("fwx_ragged_mid_plan", 4, n_each)
 
 
-def _ragged_plan(name, ntiers, n_each):
+def ragged_large_plan(n_each):
+    """fwx_ragged_large_plan: ragged_mid_plan for orders up to FWX_BATCH_LARGE_MAX_N, with FIVE tiers -- the fifth the
+    large tier, orders from FWX_BATCH_LARGE_MIN_N up -- and the large tier's work table: (offset, order, tier_count,
+    work), work an int64 array of shape (3, count + 1), the orders, panel strips and sweep tiles before each slot of
+    the large tier's list.  Needs no device."""
+    n_each = np.ascontiguousarray(n_each, dtype=np.int32)
+    work = np.zeros((3, max(n_each.size, 0) + 1), dtype=np.int64)
+    return _ragged_plan("fwx_ragged_large_plan", 5, n_each, work)
+
+
+def _ragged_plan(name, ntiers, n_each, work=None):
     n_each = np.ascontiguousarray(n_each, dtype=np.int32)
     if n_each.ndim != 1:
         raise ValueError("n_each must be a one-dimensional sequence of orders")
@@ -404,8 +415,9 @@ def _ragged_plan(name, ntiers, n_each):
     offset = np.zeros(count + 1, dtype=np.int64)
     order = np.full(count, -1, dtype=np.int32)
     tiers = np.zeros(ntiers, dtype=np.int32)
-    check(getattr(lib(), name)(count, _np_ptr(n_each), _np_ptr(offset), _np_ptr(order), _np_ptr(tiers)), name)
-    return offset, order, tiers
+    extra = () if work is None else (_np_ptr(work),)
+    check(getattr(lib(), name)(count, _np_ptr(n_each), _np_ptr(offset), _np_ptr(order), _np_ptr(tiers), *extra), name)
+    return (offset, order, tiers) if work is None else (offset, order, tiers, work)
 
 
 def _pack_ragged(rates, nexts, hops):
@@ -466,6 +478,12 @@ def solve_ragged_mid(rates, nexts=None, hops=None, *, device=-1, count_updates=F
     return _solve_ragged("fwx_solve_ragged_mid", rates, nexts, hops, device, count_updates)
 
 
+def solve_ragged_large(rates, nexts=None, hops=None, *, device=-1, count_updates=False):
+    """solve_ragged with the limit at FWX_BATCH_LARGE_MAX_N (fwx_solve_ragged_large_f64 / _f32): orders 0 ... 1024 in
+    one call, five tiers, routing by FWX_BATCH_MID_MIN_N and FWX_BATCH_LARGE_MIN_N.  Same arrays, same return value."""
+    return _solve_ragged("fwx_solve_ragged_large", rates, nexts, hops, device, count_updates)
+
+
 def _solve_ragged(stem, rates, nexts, hops, device, count_updates):
     rates = list(rates)
     nexts = None if nexts is None else list(nexts)
@@ -492,6 +510,12 @@ def solve_ragged_mid_lists(rates, nexts, hops=None, *, items=None, cap=None, dev
     """solve_ragged_lists with the limit at FWX_BATCH_MID_MAX_N (fwx_solve_ragged_mid_lists_f64 / _f32).  Same arrays,
     same lists, same return value."""
     return _solve_ragged_lists("fwx_solve_ragged_mid_lists", rates, nexts, hops, items, cap, device, count_updates)
+
+
+def solve_ragged_large_lists(rates, nexts, hops=None, *, items=None, cap=None, device=-1, count_updates=False):
+    """solve_ragged_lists with the limit at FWX_BATCH_LARGE_MAX_N (fwx_solve_ragged_large_lists_f64 / _f32).  Same
+    arrays, same lists, same return value."""
+    return _solve_ragged_lists("fwx_solve_ragged_large_lists", rates, nexts, hops, items, cap, device, count_updates)
 
 
 def _solve_ragged_lists(stem, rates, nexts, hops, items, cap, device, count_updates):
@@ -568,8 +592,37 @@ def dev_solve_ragged_mid(rate_t, n_each_t, offset_t, order_t, tier_count, *, nex
                       trace, updates_t, stream)
 
 
+def dev_solve_ragged_large(rate_t, n_each_t, offset_t, order_t, tier_count, work, work_t, *, next_t=None, hops_t=None,
+                           trace=None, updates_t=None, scratch_t=None, scratch_bytes=None, stream=None):
+    """fwx_dev_solve_ragged_large: dev_solve_ragged_mid for orders up to FWX_BATCH_LARGE_MAX_N; order_t / tier_count
+    (five entries) and work a plan as ragged_large_plan gives it, work_t a DEVICE int64 array of the same contents.
+    scratch_t: a device array for the large tier's panels, 16-byte aligned, of at least
+    _lib.batch_large_scratch_bytes(the largest order of the large tier) bytes -- the call solves as many matrices at
+    a time as it holds; allocated here, for all of them, when not given.  scratch_bytes: how much of scratch_t the call
+    may use (default: all of it).  work / work_t / scratch_t may be None when the large tier lists nothing.  Returns
+    the scratch array (or None): it must stay alive until the stream has run the call."""
+    tiers = np.ascontiguousarray(tier_count, dtype=np.int32)
+    assert tiers.shape == (5,)
+    count = n_each_t.numel()
+    if work is not None:
+        work = np.ascontiguousarray(work, dtype=np.int64)
+        assert work.shape == (3, count + 1)
+        assert work_t is None or (work_t.is_cuda and work_t.is_contiguous() and _dtype_name(work_t) == "int64"
+                                  and work_t.numel() >= work.size)
+        if scratch_t is None and tiers[4] > 0:
+            scratch_t = _empty_like_device(rate_t, (_lib.batch_large_scratch_bytes(int(work[0, tiers[4]])),), "uint8")
+    if scratch_t is not None and scratch_bytes is None:
+        scratch_bytes = scratch_t.numel() * scratch_t.element_size()
+    vp = ctypes.c_void_p
+    large = (_np_ptr(work), vp(work_t.data_ptr()) if work_t is not None else None,
+             vp(scratch_t.data_ptr()) if scratch_t is not None else None, int(scratch_bytes or 0))
+    _dev_solve_ragged("fwx_dev_solve_ragged_large", 5, rate_t, n_each_t, offset_t, order_t, tiers, next_t, hops_t,
+                      trace, updates_t, stream, large)
+    return scratch_t
+
+
 def _dev_solve_ragged(name, ntiers, rate_t, n_each_t, offset_t, order_t, tier_count, next_t, hops_t, trace, updates_t,
-                      stream):
+                      stream, large=None):
     count = n_each_t.numel()
     tiers = np.ascontiguousarray(tier_count, dtype=np.int32)
     assert tiers.shape == (ntiers,)
@@ -583,9 +636,10 @@ def _dev_solve_ragged(name, ntiers, rate_t, n_each_t, offset_t, order_t, tier_co
         vp(next_t.data_ptr()) if next_t is not None else None,
         vp(hops_t.data_ptr()) if hops_t is not None else None,
         _index_ptr(n_each_t, "int32", count), _index_ptr(offset_t, "int64", count),
-        _index_ptr(order_t, "int32", int(tiers.sum())), _np_ptr(tiers),
+        _index_ptr(order_t, "int32", int(tiers.sum())), _np_ptr(tiers), *(() if large is None else large[:2]),
         _trace_of(trace, 0) if trace is not None else None,
-        vp(updates_t.data_ptr()) if updates_t is not None else None, _stream_ptr(stream, rate_t)), name)
+        vp(updates_t.data_ptr()) if updates_t is not None else None, *(() if large is None else large[2:]),
+        _stream_ptr(stream, rate_t)), name)
 
 
 def dev_exact_paths_ragged(next0_t, n_each_t, offset_t, n_max, trace, mat_t, src_t, dst_t, cap, *, stream=None):
@@ -600,6 +654,13 @@ def dev_exact_paths_ragged_mid(next0_t, n_each_t, offset_t, n_max, trace, mat_t,
     """fwx_dev_exact_paths_ragged_mid: dev_exact_paths_ragged over a batch that dev_solve_ragged_mid solved, n_max <=
     FWX_BATCH_MID_MAX_N."""
     return _dev_exact_paths_ragged("fwx_dev_exact_paths_ragged_mid", next0_t, n_each_t, offset_t, n_max, trace, mat_t,
+                                   src_t, dst_t, cap, stream)
+
+
+def dev_exact_paths_ragged_large(next0_t, n_each_t, offset_t, n_max, trace, mat_t, src_t, dst_t, cap, *, stream=None):
+    """fwx_dev_exact_paths_ragged_large: dev_exact_paths_ragged over a batch that dev_solve_ragged_large solved, n_max
+    <= FWX_BATCH_LARGE_MAX_N."""
+    return _dev_exact_paths_ragged("fwx_dev_exact_paths_ragged_large", next0_t, n_each_t, offset_t, n_max, trace, mat_t,
                                    src_t, dst_t, cap, stream)
 
 

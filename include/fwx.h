@@ -282,8 +282,8 @@ int fwx_test_batch_mid_block(void);
  * panels in device scratch between them, column strips (panel) and tiles (sweep) of every matrix on workgroups of
  * their own.  Every matrix gets the full semantics above, the list rule included; there is no domain check and no
  * routing by content, and each matrix comes back bit-identical to the reference loop on that matrix alone -- rate,
- * next, hops (diagonals included) and U.  The exact `_path` lists: fwx_solve_batch_large_lists_* below.  No ragged
- * form above 256.
+ * next, hops (diagonals included) and U.  The exact `_path` lists: fwx_solve_batch_large_lists_* below.  Matrices
+ * of different orders up to 1024 in one call: "ragged batches up to order FWX_BATCH_LARGE_MAX_N" below.
  *
  * The contract is that of fwx_solve_batch_mid_* / fwx_dev_solve_batch_mid, with the limit at
  * FWX_BATCH_LARGE_MAX_N: count matrices of order n, matrix b at rate + b*n*n (next / hops alike, both optional, hops
@@ -592,6 +592,99 @@ int fwx_solve_ragged_mid_lists_f32(int32_t count, const int32_t *n_each, float *
                                    uint64_t *updates_each, int32_t items, const int32_t *mat, const int32_t *src,
                                    const int32_t *dst, int32_t *len_out, int32_t *path_out, int32_t cap,
                                    const fwx_opts *opts);
+
+/* ---- ragged batches up to order FWX_BATCH_LARGE_MAX_N: a fifth tier in the same call ----------------------
+ * A price history of the 30 x 20 market above (600 vertices) is ragged AND crosses 256.  These entry points are the
+ * ragged-mid family above, entry for entry and word for word, with the limit at FWX_BATCH_LARGE_MAX_N (1024) and a
+ * plan of FIVE tiers: the four above and the large tier (several workgroups per matrix over two launches per block of
+ * 16 pivots, as fwx_dev_solve_batch_large runs it).  Every matrix comes back bit-identical to the reference loop on
+ * that matrix alone -- rate, next, hops (diagonals included), U, the trace and the lists; the full list rule, no
+ * domain check, no routing by content, whole pivot range only -- and no matrix pays for the largest order of the
+ * batch: a matrix of order n_b takes part in ceil(n_b / 16) blocks of pivots and costs nothing afterwards.  The entry
+ * points above keep their limits and their outputs; fwx_ragged_plan and fwx_ragged_mid_plan are unchanged.
+ *
+ * fwx_ragged_large_plan: as fwx_ragged_mid_plan, needs no device; order_out groups the matrices with n_b >= 1 into
+ * the wave, 64-wide, 128-wide, mid and large tier, in this order, each sorted by descending order, ties by ascending
+ * index, the rest -1; tier_count_out has five entries.  Tier boundaries: FWX_BATCH_WAVE_MAX_N and FWX_BATCH_MID_MIN_N
+ * as above, and FWX_BATCH_LARGE_MIN_N (1 ... 257, default 257, as for fwx_solve_batch_large_*) sends every order from
+ * it upward to the large tier.  All three are read by the plan and only by the plan.  Where several settings claim an
+ * order the LARGE tier wins over the mid tier, and the mid tier over the wave tier.  At default settings with every
+ * order <= FWX_BATCH_MID_MAX_N the first four counts and the order list are fwx_ragged_mid_plan's.
+ * work_out (optional like the others; FWX_RAGGED_LARGE_WORK_ENTRIES(count) int64): the large tier's work table, three
+ * rows of count + 1 entries.  With L matrices in the large tier and slot m the m-th of its list, for every m <= L
+ *   row 0, panel_base[m] = sum of n_a over the slots a < m: the scratch panels of slot m start 512 * (panel_base[m] -
+ *          panel_base[first slot of its group]) bytes into the scratch;
+ *   row 1, strip_base[m] = sum of ceil(n_a / S): the panel workgroups before slot m;
+ *   row 2, tile_base[m]  = sum of ceil(n_a / TC) * ceil(n_a / TR): the sweep workgroups before slot m,
+ * (S, TR, TC) those of fwx_test_batch_large_geometry; the entries past L repeat entry L.  The sort is what the
+ * kernels rely on: at the block of pivots that starts at k0 the matrices still active, n_b > k0, are a prefix of the
+ * list.  FWX_ERR_INVALID as fwx_ragged_plan; FWX_ERR_UNSUPPORTED: an order above FWX_BATCH_LARGE_MAX_N.  No result
+ * bit of a solve depends on the split.
+ *
+ * fwx_solve_ragged_large_f64 / _f32 and fwx_solve_ragged_large_lists_f64 / _f32: HOST arrays, packed, whole pivot
+ * range only; the four small tiers' launches as in fwx_solve_ragged_mid_*, then the large tier's on the same stream.
+ * The plan, the work table and the scratch panels come from the pooled per-call context, the panels capped at
+ * 256 MiB as for fwx_solve_batch_large_*: larger batches run in groups.  updates_each, opts->updates_out, the lists
+ * arguments, the chunks and the capacity rule as in fwx_solve_ragged_mid_* / fwx_solve_ragged_mid_lists_*.
+ *
+ * fwx_dev_solve_ragged_large / fwx_dev_exact_paths_ragged_large: caller-owned DEVICE memory, asynchronous on
+ * `stream`, nothing allocated or synchronised; offsets, trace and counters (by matrix id) as in
+ * fwx_dev_solve_ragged_mid.  tier_count (HOST) has five entries.  work (HOST) and d_work (DEVICE, the same contents)
+ * are the plan's work table; scratch is device memory for the panels, 16-byte aligned, scratch_bytes at least
+ * FWX_BATCH_LARGE_SCRATCH_BYTES(the largest order of the large tier).  A GROUP is a maximal run of consecutive slots
+ * whose panels fit scratch_bytes (and whose tiles number less than 2^31); the groups run one after the other on
+ * `stream`, each 2 * ceil(n_first / 16) launches, n_first its largest order: per block of pivots one panel and one
+ * sweep launch over the group's active prefix, in which every workgroup finds its slot by binary search in d_work.
+ * With a trace one more launch, before the first group, writes -1 to exactly the n_b x n_b cells of `last`.  A
+ * workgroup whose matrix id lies outside [0, count), whose order lies outside 1 ... 1024 or whose panels would end
+ * past scratch_bytes stays idle; whatever the device tables hold, nothing outside the n_b x n_b cells of a matrix
+ * and the scratch_bytes given is read or written.  With tier_count[4] == 0 the table and the scratch are ignored and
+ * may be NULL.  The walk: n_max <= FWX_BATCH_LARGE_MAX_N, scratch holds items * FWX_EXACT_SCRATCH_INTS(n_max) int32.
+ *
+ * Statuses, all decided before any device call, as in the ragged-mid family with: FWX_ERR_UNSUPPORTED for an order
+ * (n_max in the walk) above FWX_BATCH_LARGE_MAX_N; FWX_ERR_INVALID for a sum of the FIVE tier counts above count
+ * and, with tier_count[4] > 0, for a NULL work or d_work, a host table whose rows are not non-decreasing, whose
+ * orders (the differences of row 0) lie outside 1 ... 1024 or do not descend, or whose strip and tile rows are not
+ * those of these orders, and for scratch that is NULL, misaligned or too small.  Then FWX_ERR_NO_DEVICE without a
+ * device, the arrays untouched.
+ * When it pays (MI355X, f64 + next + hops, profiles/r31_ragged_large.txt): 512 matrices whose orders ramp from 4 to
+ * 1024 take 56.1 ms in one fwx_dev_solve_ragged_large call (one group, 128 launches), 144.3 ms NaN-padded to 1024 in
+ * one fwx_dev_solve_batch_large call and 113.6 ms split by hand into fwx_dev_solve_ragged_mid plus one padded large
+ * call; the host form takes 158.1 ms against 451.4 ms padded.  With all orders equal the call is SLOWER than
+ * fwx_dev_solve_batch_large by more than twice that call's spread in every cell measured -- 6.7 / 7.4 % at n = 257
+ * (16 / 256 matrices), 6.0 / 4.9 % at 512, 3.5 / 3.8 % at 1024, the cost of the slot search: use that one for a
+ * uniform batch.                                                                                               */
+#define FWX_RAGGED_LARGE_WORK_ENTRIES(count) (3 * ((size_t)(count) + 1))
+int fwx_ragged_large_plan(int32_t count, const int32_t *n_each, int64_t *offset_out, int32_t *order_out,
+                          int32_t tier_count_out[5], int64_t *work_out);
+int fwx_solve_ragged_large_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, const fwx_opts *opts);
+int fwx_solve_ragged_large_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next, int32_t *hops,
+                               uint64_t *updates_each, const fwx_opts *opts);
+int fwx_dev_solve_ragged_large(int32_t count, int32_t dtype, void *rate, int32_t *next, int32_t *hops,
+                               const int32_t *d_n_each, const int64_t *d_offset, const int32_t *d_order,
+                               const int32_t tier_count[5], const int64_t *work, const int64_t *d_work,
+                               const struct fwx_trace *trace, unsigned long long *d_updates_each, void *scratch,
+                               size_t scratch_bytes, void *stream);
+int fwx_dev_exact_paths_ragged_large(int32_t count, const int32_t *d_n_each, const int64_t *d_offset, int32_t n_max,
+                                     const int32_t *next0, const struct fwx_trace *trace, int32_t items,
+                                     const int32_t *mat, const int32_t *src, const int32_t *dst, int32_t *len_out,
+                                     int32_t *path_out, int32_t cap, int32_t *scratch, void *stream);
+int fwx_solve_ragged_large_lists_f64(int32_t count, const int32_t *n_each, double *rate, int32_t *next,
+                                     int32_t *hops, uint64_t *updates_each, int32_t items, const int32_t *mat,
+                                     const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                                     int32_t cap, const fwx_opts *opts);
+int fwx_solve_ragged_large_lists_f32(int32_t count, const int32_t *n_each, float *rate, int32_t *next,
+                                     int32_t *hops, uint64_t *updates_each, int32_t items, const int32_t *mat,
+                                     const int32_t *src, const int32_t *dst, int32_t *len_out, int32_t *path_out,
+                                     int32_t cap, const fwx_opts *opts);
+/* TEST HOOK: the schedule fwx_dev_solve_ragged_large makes of a host work table (count + 1 entries to a row) whose
+ * first large_count slots are listed, with scratch_bytes of scratch: returns the number of groups and writes the first
+ * slot of each, up to cap, to group_first; totals[0] = launches, totals[1] = panel workgroups, totals[2] = sweep
+ * workgroups over the whole call (no trace).  FWX_ERR_INVALID as the device form.  Needs no device.  Not for
+ * production use. */
+int fwx_test_ragged_large_schedule(int32_t count, int32_t large_count, const int64_t *work, size_t scratch_bytes,
+                                   int32_t *group_first, int32_t cap, int64_t totals[3]);
 
 /* Index form of the `_path` list that optimum returns (Algorithms.hs:74-75): follow next-hops
  * from src until dst.  Returns the number of vertices written to out (dst included, src not), 0 if
