@@ -112,6 +112,9 @@ SIGNATURES = {
     "fwx_test_perk_group": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "fwx_test_perk_group_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                                 ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
+    "fwx_test_pools": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "fwx_test_perk_scratch_victim": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int),
+                                                    ctypes.c_int, ctypes.c_int]),
     "fwx_test_perk_wide": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "fwx_solve_f64": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),
     "fwx_solve_f32": (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(FwxOpts)]),

@@ -1063,6 +1063,31 @@ int fwx_test_perk_group_plan(int n, int nfull, int gmax, int *size, int *set, in
     return g;
 }
 
+int fwx_test_perk_scratch_victim(const uint64_t *used, const int *busy, int count, int cap)
+{
+    if (count < 0 || cap < 0 || (count > 0 && (!used || !busy))) return -2;
+    return perk_scratch_victim(used, busy, count, cap);
+}
+
+int fwx_test_pools(uint64_t *out, int reset)
+{
+    static const uint64_t cap[POOL_COUNT] = {kCtxPoolMaxFree, kPerkScratchMax, kMultiPoolMaxIdle};
+    for (int i = 0; i < POOL_COUNT; ++i) {
+        PoolStats &st = g_pool_stats[i];
+        const uint64_t leased = st.leased.load(std::memory_order_relaxed);
+        const uint64_t v[4] = {cap[i],
+                               reset ? st.created.exchange(0, std::memory_order_relaxed)
+                                     : st.created.load(std::memory_order_relaxed),
+                               reset ? st.destroyed.exchange(0, std::memory_order_relaxed)
+                                     : st.destroyed.load(std::memory_order_relaxed),
+                               reset ? st.peak.exchange(leased, std::memory_order_relaxed)
+                                     : st.peak.load(std::memory_order_relaxed)};
+        if (out)
+            for (int j = 0; j < 4; ++j) out[4 * i + j] = v[j];
+    }
+    return POOL_COUNT;
+}
+
 int fwx_test_perk_wide(uint64_t *wide_launches, int reset)
 {
     const uint64_t v = reset ? g_perk_wide_launches.exchange(0, std::memory_order_relaxed)

@@ -257,6 +257,24 @@ struct SideStream {
 };
 
 
+// What the three process-wide pools have done in this process (test hook fwx_test_pools, fwx.h): entries created,
+// entries destroyed or evicted, and the most that were leased -- in a call -- at one time.  Relaxed host atomics.
+struct PoolStats {
+    std::atomic<uint64_t> created{0}, destroyed{0}, leased{0}, peak{0};
+    void lease()
+    {
+        const uint64_t now = leased.fetch_add(1, std::memory_order_relaxed) + 1;
+        uint64_t p = peak.load(std::memory_order_relaxed);
+        while (p < now && !peak.compare_exchange_weak(p, now, std::memory_order_relaxed)) {}
+    }
+    void unlease() { leased.fetch_sub(1, std::memory_order_relaxed); }
+};
+enum { POOL_CTX, POOL_PERK, POOL_MULTI, POOL_COUNT };
+inline PoolStats g_pool_stats[POOL_COUNT];
+constexpr size_t kCtxPoolMaxFree = 8;          // CtxPool keeps this many idle contexts
+constexpr size_t kPerkScratchMax = 16;         // PerkScratch keeps this many streams' buffers
+constexpr size_t kMultiPoolMaxIdle = 2;        // MultiPool (fwx_multi.hip) parks this many handles
+
 // ------------------------------------------------------------------------------------------------
 // Per-call context.  fwx_solve_f64 / _f32 / fwx_dev_solve are stateless for the caller, but what a
 // call needs on the device -- a stream, the look-ahead stream and its events, device buffers for the
@@ -362,6 +380,7 @@ public:
                 if (p.free_[i]->device == dev) {
                     *out = p.free_[i];
                     p.free_.erase(p.free_.begin() + (long)i);
+                    g_pool_stats[POOL_CTX].lease();
                     return FWX_OK;
                 }
         }
@@ -373,12 +392,15 @@ public:
             delete c;
             return FWX_ERR_HIP;
         }
+        g_pool_stats[POOL_CTX].created.fetch_add(1, std::memory_order_relaxed);
+        g_pool_stats[POOL_CTX].lease();
         *out = c;
         return FWX_OK;
     }
     static void release(CallCtx *c)
     {
         if (!c) return;
+        g_pool_stats[POOL_CTX].unlease();
         c->trim();
         Pool &p = pool();
         {
@@ -387,10 +409,11 @@ public:
         }
         c->destroy();          // more concurrent callers than the pool keeps: this one goes
         delete c;
+        g_pool_stats[POOL_CTX].destroyed.fetch_add(1, std::memory_order_relaxed);
     }
 
 private:
-    static constexpr size_t kMaxFree = 8;
+    static constexpr size_t kMaxFree = kCtxPoolMaxFree;
     struct Pool { std::mutex mu; std::vector<CallCtx *> free_; };
     static Pool &pool() { static Pool *p = new Pool(); return *p; }   // leaked on purpose
 };
@@ -697,13 +720,41 @@ template <typename T> inline size_t perk_kt_ws_bytes(int n)
 // null stream included) through the events alone; the events without timing -- and destroyed with the entry.  Every call
 // makes the caller's stream wait for the look-ahead stream before it returns, so "this stream's launches are the
 // buffer's only readers" holds as before.
+//
+// An entry is IN USE from the `get` of a call to that call's return (PerkLease, held by relax_range_kt for its scope,
+// error returns included): the call goes on queueing launches that read the buffer, on the look-ahead stream too, long
+// after `get` has dropped the mutex, and hipFree waits only for what is queued already.  An entry in use is never
+// evicted, whatever its stamp; the victim is the least recently used IDLE entry (perk_scratch_victim).  With every
+// entry in use -- more callers inside the library at once than the pool keeps -- the pool exceeds kMax for the
+// moment; a later `get` that adds an entry evicts idle ones until kMax are kept again.
 struct PerkSide {
     hipStream_t s = nullptr;
     hipEvent_t main_done = nullptr, chain_done = nullptr;
 };
+// The victim rule over the entries' stamps and in-use marks: the index of the least recently used idle entry of a
+// pool that holds `cap` entries or more, -1 if the pool is below `cap` or every entry is in use (fwx_test_perk_scratch_victim).
+inline int perk_scratch_victim(const uint64_t *used, const int *busy, int count, int cap)
+{
+    if (count < cap) return -1;
+    int v = -1;
+    for (int i = 0; i < count; ++i)
+        if (!busy[i] && (v < 0 || used[i] < used[v])) v = i;
+    return v;
+}
+struct PerkLease {                                 // an entry of PerkScratch in use by one call
+    hipStream_t s = nullptr;
+    int dev = -1;
+    bool held = false;
+    PerkLease() = default;
+    PerkLease(const PerkLease &) = delete;
+    PerkLease &operator=(const PerkLease &) = delete;
+    inline ~PerkLease();
+};
 class PerkScratch {
 public:
-    static int get(hipStream_t s, size_t bytes, void **out, PerkSide *side = nullptr)
+    static constexpr size_t kMax = kPerkScratchMax;
+    // lease: marks the entry in use until the lease is destroyed
+    static int get(hipStream_t s, size_t bytes, void **out, PerkSide *side, PerkLease &lease)
     {
         int dev = 0, cur = 0;
         FWX_HIP(hipGetDevice(&cur));
@@ -715,18 +766,25 @@ public:
         for (Entry &x : p.all)
             if (x.s == s && x.dev == dev) { e = &x; break; }
         if (!e) {
-            if (p.all.size() >= kMax) {            // evict the least recently used
-                size_t lru = 0;
-                for (size_t i = 1; i < p.all.size(); ++i)
-                    if (p.all[i].used < p.all[lru].used) lru = i;
-                if (p.all[lru].p) (void)hipFree(p.all[lru].p);
-                release(p.all[lru].side);          // behind the hipFree, which has waited for the device
-                p.all.erase(p.all.begin() + (long)lru);
+            while (p.all.size() >= kMax) {         // evict the least recently used idle entries, down to kMax - 1
+                std::vector<uint64_t> used;
+                std::vector<int> busy;
+                for (const Entry &x : p.all) { used.push_back(x.used); busy.push_back(x.busy); }
+                const int v = perk_scratch_victim(used.data(), busy.data(), (int)p.all.size(), (int)kMax);
+                if (v < 0) break;                  // every entry is in a call: the pool grows for the moment
+                if (p.all[v].p) (void)hipFree(p.all[v].p);
+                release(p.all[v].side);            // behind the hipFree, which has waited for the device
+                p.all.erase(p.all.begin() + v);
+                g_pool_stats[POOL_PERK].destroyed.fetch_add(1, std::memory_order_relaxed);
             }
-            p.all.push_back(Entry{dev, s, nullptr, 0, 0, PerkSide()});
+            p.all.push_back(Entry{dev, s, nullptr, 0, 0, PerkSide(), 0});
             e = &p.all.back();
+            g_pool_stats[POOL_PERK].created.fetch_add(1, std::memory_order_relaxed);
         }
         e->used = ++p.clock;
+        ++e->busy;                                 // from here on every return path leaves the mark to the lease
+        lease.s = s; lease.dev = dev; lease.held = true;
+        g_pool_stats[POOL_PERK].lease();
         if (e->cap < bytes) {
             if (e->p) {
                 if (s) (void)hipStreamSynchronize(s);   // its readers are queued on this stream and nowhere else
@@ -752,10 +810,21 @@ public:
         *out = e->p;
         return FWX_OK;
     }
+    static void put(hipStream_t s, int dev)
+    {
+        Pool &p = pool();
+        std::lock_guard<std::mutex> lk(p.mu);
+        for (Entry &x : p.all)
+            if (x.s == s && x.dev == dev) {
+                if (x.busy > 0) --x.busy;
+                x.used = ++p.clock;                // idle from now: the stamp eviction goes by
+                break;
+            }
+        g_pool_stats[POOL_PERK].unlease();
+    }
 
 private:
-    static constexpr size_t kMax = 16;
-    struct Entry { int dev; hipStream_t s; void *p; size_t cap; uint64_t used; PerkSide side; };
+    struct Entry { int dev; hipStream_t s; void *p; size_t cap; uint64_t used; PerkSide side; int busy; };
     static void release(PerkSide &d)
     {
         if (d.main_done) (void)hipEventDestroy(d.main_done);
@@ -766,6 +835,7 @@ private:
     struct Pool { std::mutex mu; std::vector<Entry> all; uint64_t clock = 0; };
     static Pool &pool() { static Pool *p = new Pool(); return *p; }   // leaked on purpose
 };
+inline PerkLease::~PerkLease() { if (held) PerkScratch::put(s, dev); }
 
 // The multi-pivot schedule of relax_range (below) for a rates-only solve of the whole matrix in place.  Per
 // block of <= 64 pivots: ONE panel launch (fused_panels, compare form: W and Ct of the block from the
@@ -808,8 +878,9 @@ inline int relax_range_kt(T *rate, int n, int k_begin, int k_end, int serpentine
     const int gmax = pair ? perk_group_max(n) : 1;
     const int sets = pair ? 2 * gmax : 1;
     PerkSide side;
+    PerkLease lease;                               // the stream's entry stays in use until this call returns
     if (!ws) {
-        const int rc0 = PerkScratch::get(s, (size_t)sets * perk_kt_ws_bytes<T>(n), &ws, pair ? &side : nullptr);
+        const int rc0 = PerkScratch::get(s, (size_t)sets * perk_kt_ws_bytes<T>(n), &ws, pair ? &side : nullptr, lease);
         if (rc0) return rc0;
     }
     // `sets` panel sets: the W rows of all sets, then the Ct lines of all sets.  The group schedule keeps two halves of

@@ -1385,11 +1385,14 @@ public:
             }
             pl.idle.push_back({k, m});
         }
-        if (evict) fwx_matrix_destroy(evict);
+        if (evict) {
+            fwx_matrix_destroy(evict);
+            g_pool_stats[POOL_MULTI].destroyed.fetch_add(1, std::memory_order_relaxed);
+        }
     }
 
 private:
-    static constexpr size_t kKeepBytes = (size_t)256 << 20, kMaxIdle = 2;
+    static constexpr size_t kKeepBytes = (size_t)256 << 20, kMaxIdle = kMultiPoolMaxIdle;
     struct Entry { Key k; fwx_matrix *m; };
     struct Pool { std::mutex mu; std::vector<Entry> idle; };
     static Pool &pool() { static Pool *p = new Pool(); return *p; }   // leaked on purpose
@@ -1419,12 +1422,24 @@ static int solve_multi_host(int32_t n, int dtype, void *rate, int32_t *next, int
     // it in an unknown state)
     struct Holder {
         fwx_matrix *m = nullptr;
-        ~Holder() { if (m) fwx_matrix_destroy(m); }
+        bool leased = false;
+        ~Holder()
+        {
+            if (m) {
+                fwx_matrix_destroy(m);
+                g_pool_stats[POOL_MULTI].destroyed.fetch_add(1, std::memory_order_relaxed);
+            }
+            if (leased) g_pool_stats[POOL_MULTI].unlease();
+        }
     } h;
     h.m = MultiPool::take(key);
-    if (!h.m && (rc = fwx_matrix_create_multi(&h.m, n, dtype, next != nullptr, hops != nullptr, n_parts,
-                                              devices, exchange)))
-        return rc;
+    if (!h.m) {
+        if ((rc = fwx_matrix_create_multi(&h.m, n, dtype, next != nullptr, hops != nullptr, n_parts, devices, exchange)))
+            return rc;
+        g_pool_stats[POOL_MULTI].created.fetch_add(1, std::memory_order_relaxed);
+    }
+    h.leased = true;
+    g_pool_stats[POOL_MULTI].lease();
     rc = fwx_matrix_upload(h.m, rate, next, hops);
     if (!rc) rc = multi_solve(h.m, op);
     if (!rc) rc = fwx_matrix_download(h.m, rate, next, hops);

@@ -48,6 +48,13 @@
  * once the pool is warm), a handle on the handle's own non-blocking stream, so solves
  * on different host threads overlap on the device and nothing synchronises implicitly with the
  * streams of other libraries in the process (torch's included).
+ * What is NOT promised: one handle must not be used by two threads at once (calls on different handles
+ * are independent).  Two host threads must not have step-API calls (fwx_dev_relax*) in flight on the
+ * same stream at once, the null stream included: the snapshot panels are one buffer per stream.  If
+ * more callers come at once than a pool keeps -- contexts, per-stream panels, parked multi-partition
+ * handles -- the pool grows for the moment and shrinks again: what is in use by a call that has not
+ * returned is never freed under it, and the surplus is released (which synchronises the device) as the
+ * calls return or by a later call.
  */
 #ifndef FWX_H
 #define FWX_H
@@ -185,6 +192,19 @@ int fwx_test_perk_group(uint64_t *launches, int reset);
  * group of 1.  Returns the number of groups, or -1 for arguments out of range.  Needs no device.  Not for production
  * use.                                                                                                   */
 int fwx_test_perk_group_plan(int n, int nfull, int gmax, int *size, int *set, int cap);
+/* TEST HOOK for the three process-wide pools: the per-call contexts of the one-shot entry points, the per-stream
+ * snapshot panels of fwx_dev_relax* (below) and the parked handles of fwx_solve_multi_*.  out (if not NULL) receives
+ * twelve numbers, four per pool in that order: how many entries the pool keeps (its capacity), the entries created
+ * in this process, the entries destroyed or evicted, and the most that were leased -- in a call -- at one time.
+ * reset clears created and destroyed and sets the peak to what is leased right now.  Returns the number of pools, 3.
+ * Needs no device.  Not for production use.                                                               */
+int fwx_test_pools(uint64_t *out, int reset);
+/* TEST HOOK: the rule by which the pool of snapshot panels picks the entry it evicts, over `count` entries with the
+ * stamps used[] (larger = more recently used) and the marks busy[] (non-zero: a call that has not returned holds the
+ * entry) in a pool that keeps `cap`: the index of the least recently used idle entry; -1 below capacity
+ * (count < cap: nothing is evicted) and when every entry is busy (the pool grows for the moment); -2 for arguments
+ * out of range.  Needs no device.  Not for production use.                                                 */
+int fwx_test_perk_scratch_victim(const uint64_t *used, const int *busy, int count, int cap);
 
 /* ---- one-shot host-buffer entry points: what the reference-side FFI binds --------------------
  * Replace runAlgo (Algorithms.hs:42-61) for a matrix produced by buildMatrix (:26-40).
@@ -964,7 +984,8 @@ typedef struct fwx_pivots {
  * anything else, or unset, is automatic -- a wave whose loaded pivot operands are all NaN or sign-clear takes
  * the maximum of its candidates first and compares once, which gives the same bits for every entry.  For
  * tests and A/B runs; no result bit depends on it.  The snapshots live in library-owned device scratch on the stream's
- * device, one buffer of 128 * n elements per stream (at most 16 are kept, the least recently used goes):
+ * device, one buffer of 128 * n elements per stream (at most 16 are kept, the least recently used that no call still
+ * inside the library holds goes; with more than 16 callers inside at once the pool grows for the moment):
  * the FIRST such call on a stream calls hipMalloc, and a call with a larger n than the stream has seen
  * waits for the stream before it frees and allocates again -- so such a call cannot be captured into a
  * graph; set FWX_PERK_PIVOTS=1 for that.  Every later call allocates nothing, synchronises nothing and
