@@ -18,7 +18,7 @@ LIB = os.path.join(PKG, "libfwx.so")
 CLI = os.path.join(PKG, "fwx_cli")
 
 HIP_SOURCES = ["fwx_kernels.hip", "fwx_mid.hip", "fwx_large.hip", "fwx_fused.hip", "fwx_api.hip", "fwx_batch.hip",
-               "fwx_multi.hip"]
+               "fwx_multi.hip", "fwx_perk.hip"]
 CXX_SOURCES = []  # host mirror sources are appended below when present
 HOST_DIR = os.path.join(CSRC, "host")
 

@@ -18,6 +18,7 @@
 #include "fwx_handle.h"
 #include "fwx_internal.h"
 #include "fwx_kernels.h"
+#include "fwx_perk.h"
 #include "fwx_query.h"
 
 using namespace fwxi;
@@ -473,11 +474,9 @@ int solve_host(int32_t n, T *rate, int32_t *next, int32_t *hops, const fwx_opts 
         // per-k engine; pitch nd (a matrix padded for the fused engine but found outside its domain)
         void *ws = nullptr;      // snapshot panels of the multi-pivot schedule (rates only): the context's
         if (!dn && !dh && (rc = cx.reserve(CallCtx::WS, perk_kt_ws_bytes<T>(nd), &ws))) return rc;
-        rc = relax_range<T>(dr, dn, dh, nd, nd, 0, dr + (size_t)op.k_begin * nd,
-                            dh ? dh + (size_t)op.k_begin * nd : nullptr, nd, op.k_begin, op.k_end,
-                            op.serpentine, upd, s, fwx::PathLog(), 0, 0,
-                            dn ? dn + (size_t)op.k_begin * nd : nullptr, ws);
-        if (rc) return rc;
+        PerkRange<T> pr = PerkRange<T>::whole(dr, dn, dh, nd, op.k_begin, op.k_end);
+        pr.serpentine = op.serpentine; pr.d_updates = upd; pr.stream = s; pr.kt_ws = ws;
+        if ((rc = relax_range<T>(pr))) return rc;
     }
 
     if ((rc = copy2d(staged ? (void *)st_rate : (void *)rate, n, d_rate.p, nd, sizeof(T), hipMemcpyDeviceToHost))) return rc;
@@ -875,10 +874,9 @@ int matrix_solve_typed(fwx_matrix *m, const Opts &op, unsigned long long *upd, h
         return FWX_OK;
     }
     if (m->resume) { m->resume->valid_upto = 0; m->resume->state_at = -1; }   // nothing was recorded
-    return relax_range<T>(r, d.next, d.hops, nd, nd, 0, r + (size_t)op.k_begin * nd,
-                          d.hops ? d.hops + (size_t)op.k_begin * nd : nullptr, nd, op.k_begin,
-                          op.k_end, op.serpentine, upd, s, d.plog, 0, 0,
-                          d.next ? d.next + (size_t)op.k_begin * nd : nullptr);
+    PerkRange<T> pr = PerkRange<T>::whole(r, d.next, d.hops, nd, op.k_begin, op.k_end);
+    pr.serpentine = op.serpentine; pr.d_updates = upd; pr.stream = s; pr.plog = d.plog;
+    return relax_range<T>(pr);
 }
 
 // Solve with the path trace (PathLog): one pass.  `last` starts at -1 everywhere; the kernels set
@@ -1002,73 +1000,6 @@ int fwx_test_kernel_forms(uint64_t *seen, int reset)
     return fwx::KF_COUNT;
 }
 
-int fwx_test_perk_pivots(uint64_t *launches, int reset)
-{
-    for (int i = 0; i < 5; ++i) {
-        const uint64_t v = reset ? g_perk_launches[i].exchange(0, std::memory_order_relaxed)
-                                 : g_perk_launches[i].load(std::memory_order_relaxed);
-        if (launches) launches[i] = v;
-    }
-    return perk_pivots();
-}
-
-int fwx_test_perk_fold(void) { return perk_fold_compare() ? 1 : 0; }
-
-int fwx_test_perk_walk(void) { return perk_walk() ? 1 : 0; }
-
-int fwx_test_perk_deep(uint64_t *deep_launches, int reset)
-{
-    const uint64_t v = reset ? g_perk_deep_launches.exchange(0, std::memory_order_relaxed)
-                             : g_perk_deep_launches.load(std::memory_order_relaxed);
-    if (deep_launches) *deep_launches = v;
-    return perk_deep() ? 1 : 0;
-}
-
-int fwx_test_perk_tile(uint64_t *launches, int reset)
-{
-    const uint64_t v = reset ? g_perk_tile_launches.exchange(0, std::memory_order_relaxed)
-                             : g_perk_tile_launches.load(std::memory_order_relaxed);
-    if (launches) *launches = v;
-    return perk_tile_min_n();
-}
-
-int fwx_test_perk_pair(uint64_t *launches, int reset)
-{
-    const uint64_t v = reset ? g_perk_pair_launches.exchange(0, std::memory_order_relaxed)
-                             : g_perk_pair_launches.load(std::memory_order_relaxed);
-    if (launches) *launches = v;
-    return perk_pair_min_n();
-}
-
-int fwx_test_perk_group(uint64_t *launches, int reset)
-{
-    for (int i = 0; i < FWX_PERK_GROUP_CAP / 2; ++i) {
-        const uint64_t v = reset ? g_perk_group_launches[i].exchange(0, std::memory_order_relaxed)
-                                 : g_perk_group_launches[i].load(std::memory_order_relaxed);
-        if (launches) launches[i] = v;
-    }
-    return perk_group_max_env();
-}
-
-int fwx_test_perk_group_plan(int n, int nfull, int gmax, int *size, int *set, int cap)
-{
-    if (gmax == 0) gmax = perk_group_max(n);
-    if (nfull < 0 || gmax < 2 || gmax > FWX_PERK_GROUP_CAP || (gmax & 1) || cap < 0) return -1;
-    int g = 0;
-    for (int q = 0, sz = perk_group_size(nfull, 0, gmax); sz > 0; q += sz, sz = perk_group_size(nfull - q, sz, gmax), ++g)
-        if (g < cap) {
-            if (size) size[g] = sz;
-            if (set) set[g] = (g & 1) * gmax;
-        }
-    return g;
-}
-
-int fwx_test_perk_scratch_victim(const uint64_t *used, const int *busy, int count, int cap)
-{
-    if (count < 0 || cap < 0 || (count > 0 && (!used || !busy))) return -2;
-    return perk_scratch_victim(used, busy, count, cap);
-}
-
 int fwx_test_pools(uint64_t *out, int reset)
 {
     static const uint64_t cap[POOL_COUNT] = {kCtxPoolMaxFree, kPerkScratchMax, kMultiPoolMaxIdle};
@@ -1086,14 +1017,6 @@ int fwx_test_pools(uint64_t *out, int reset)
             for (int j = 0; j < 4; ++j) out[4 * i + j] = v[j];
     }
     return POOL_COUNT;
-}
-
-int fwx_test_perk_wide(uint64_t *wide_launches, int reset)
-{
-    const uint64_t v = reset ? g_perk_wide_launches.exchange(0, std::memory_order_relaxed)
-                             : g_perk_wide_launches.load(std::memory_order_relaxed);
-    if (wide_launches) *wide_launches = v;
-    return perk_wide() ? 1 : 0;
 }
 
 const char *fwx_test_kernel_form_name(int form)
@@ -1671,15 +1594,17 @@ int fwx_dev_relax_skip(const fwx_slab *slab, const fwx_pivots *piv, int32_t serp
         if (skip_lo < 0 || skip_hi < skip_lo || skip_hi > slab->rows ||
             (skip_hi > skip_lo && (skip_lo % 4 || skip_hi % 4)))
             return FWX_ERR_INVALID;
-        if (slab->dtype == FWX_F64)
-            return relax_range<double>((double *)slab->rate, slab->next, slab->hops, slab->rows,
-                                       slab->n, slab->row0, (const double *)piv->rate, piv->hops,
-                                       piv->stride, piv->k_begin, piv->k_end, serpentine, d_updates, s,
-                                       fwx::PathLog(), skip_lo, skip_hi, slab->next ? piv->next : nullptr);
-        return relax_range<float>((float *)slab->rate, slab->next, slab->hops, slab->rows, slab->n,
-                                  slab->row0, (const float *)piv->rate, piv->hops, piv->stride,
-                                  piv->k_begin, piv->k_end, serpentine, d_updates, s, fwx::PathLog(),
-                                  skip_lo, skip_hi, slab->next ? piv->next : nullptr);
+        auto run = [&](auto elem) -> int {
+            using T = decltype(elem);
+            PerkRange<T> pr;
+            pr.rate = (T *)slab->rate; pr.next = slab->next; pr.hops = slab->hops;
+            pr.rows = slab->rows; pr.n = slab->n; pr.row0 = slab->row0;
+            pr.prow0 = (const T *)piv->rate; pr.phops0 = piv->hops; pr.pnext0 = slab->next ? piv->next : nullptr;
+            pr.stride = piv->stride; pr.k_begin = piv->k_begin; pr.k_end = piv->k_end; pr.serpentine = serpentine;
+            pr.d_updates = d_updates; pr.stream = s; pr.skip_lo = skip_lo; pr.skip_hi = skip_hi;
+            return relax_range<T>(pr);
+        };
+        return slab->dtype == FWX_F64 ? run(double()) : run(float());
     });
 }
 

@@ -36,6 +36,51 @@ static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1000) == FWX_LARGE_SCRATCH_BYTES(100
 
 namespace {
 
+// Tier choice of the batched small solves (fwx_solve_batch_*, fwx_dev_solve_batch): matrices of order n <=
+// FWX_BATCH_WAVE_MAX_N take the wave tier (one wave per matrix, registers only), larger ones the workgroup
+// tier (small_solve's body, one workgroup per matrix).  An integer 0 ... FWX_BATCH_WAVE_N, read on every
+// call; 0 turns the wave tier off; any other value: the default.  No result bit depends on it.
+#define FWX_BATCH_WAVE_MAX_N_DEFAULT FWX_BATCH_WAVE_N
+int batch_wave_max_n()
+{
+    return (int)env_digits("FWX_BATCH_WAVE_MAX_N", 0, FWX_BATCH_WAVE_N, FWX_BATCH_WAVE_MAX_N_DEFAULT);
+}
+
+// Routing of the mid-size batch entry points (fwx_solve_batch_mid_*, fwx_dev_solve_batch_mid): orders below
+// FWX_BATCH_MID_MIN_N are forwarded to the tiers above, orders from it up to FWX_BATCH_MID_MAX_N run the mid
+// tier (fwx_mid.hip).  An integer 1 ... FWX_BATCH_MAX_N + 1, read on every call; any other value: the default,
+// FWX_BATCH_MAX_N + 1 (only what the small tiers cannot take).  No result bit depends on it.
+// fwx_ragged_mid_plan and the host forms fwx_solve_ragged_mid_* read it too, as the boundary of the plan's fourth tier
+// (the plan reads it and only the plan: the device form takes the tier counts it is given).
+#define FWX_BATCH_MID_MIN_N_DEFAULT (FWX_BATCH_MAX_N + 1)
+int batch_mid_min_n()
+{
+    return (int)env_digits("FWX_BATCH_MID_MIN_N", 1, FWX_BATCH_MID_MIN_N_DEFAULT, FWX_BATCH_MID_MIN_N_DEFAULT);
+}
+
+// Routing of the large batch entry points (fwx_solve_batch_large_*, fwx_dev_solve_batch_large): orders below
+// FWX_BATCH_LARGE_MIN_N are forwarded to the mid entry path (which forwards further by FWX_BATCH_MID_MIN_N), orders
+// from it up to FWX_BATCH_LARGE_MAX_N run the large tier (fwx_large.hip).  An integer 1 ... FWX_BATCH_MID_MAX_N + 1,
+// read on every call; any other value: the default, FWX_BATCH_MID_MAX_N + 1.  No result bit depends on it.
+#define FWX_BATCH_LARGE_MIN_N_DEFAULT (FWX_BATCH_MID_MAX_N + 1)
+int batch_large_min_n()
+{
+    return (int)env_digits("FWX_BATCH_LARGE_MIN_N", 1, FWX_BATCH_LARGE_MIN_N_DEFAULT, FWX_BATCH_LARGE_MIN_N_DEFAULT);
+}
+
+// fwx_solve_batch_lists_*: items walked per launch.  The lists (cap int32 per item), the walk stacks
+// (FWX_EXACT_SCRATCH_INTS(n)) and the item triples + lengths (4) of one launch stay within
+// FWX_BATCH_LISTS_BUDGET_BYTES of device memory; FWX_BATCH_LISTS_CHUNK (environment, read per call: digits only,
+// >= 1, anything else means the default) asks for fewer.  At least one item per launch.  No result depends on it.
+#define FWX_BATCH_LISTS_BUDGET_BYTES ((long long)64 << 20)
+long long batch_lists_chunk(int n, int cap)
+{
+    const long long per_item = 4ll * ((long long)cap + 3ll * ((long long)n + 2) + 4);
+    long long fit = FWX_BATCH_LISTS_BUDGET_BYTES / per_item;
+    if (fit < 1) fit = 1;
+    return env_digits("FWX_BATCH_LISTS_CHUNK", 1, fit - 1, fit);
+}
+
 enum Tier { TIER_SMALL, TIER_MID, TIER_LARGE };
 
 // One family of entry points: the largest order it takes, the tiers it may route to beyond the small ones (the

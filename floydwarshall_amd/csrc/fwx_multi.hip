@@ -33,6 +33,7 @@
 #include "fwx_handle.h"
 #include "fwx_internal.h"
 #include "fwx_kernels.h"
+#include "fwx_perk.h"
 #include "fwx_query.h"
 
 namespace fwxi {
@@ -985,11 +986,13 @@ template <typename T> static int multi_solve_typed(DeviceGuard &g, fwx_matrix *m
                     auto sweep = [&](int lo, int hi, int skip_lo, int skip_hi) -> int {
                         if (hi <= lo) return FWX_OK;
                         const size_t off = (size_t)lo * nd;
-                        return relax_range<T>((T *)q.rate + off, q.next ? q.next + off : nullptr,
-                                              q.hops ? q.hops + off : nullptr, hi - lo, nd, q.row0 + lo,
-                                              (const T *)q.wp[slot], q.whp[slot], nd, blk.k0, blk.k0 + blk.bt,
-                                              op.serpentine, counting ? q.upd : nullptr, q.main, fwx::PathLog(),
-                                              skip_lo, skip_hi);
+                        PerkRange<T> pr;
+                        pr.rate = (T *)q.rate + off; pr.next = q.next ? q.next + off : nullptr;
+                        pr.hops = q.hops ? q.hops + off : nullptr; pr.rows = hi - lo; pr.n = nd; pr.row0 = q.row0 + lo;
+                        pr.prow0 = (const T *)q.wp[slot]; pr.phops0 = q.whp[slot]; pr.stride = nd;
+                        pr.k_begin = blk.k0; pr.k_end = blk.k0 + blk.bt; pr.serpentine = op.serpentine;
+                        pr.d_updates = counting ? q.upd : nullptr; pr.stream = q.main; pr.skip_lo = skip_lo; pr.skip_hi = skip_hi;
+                        return relax_range<T>(pr);
                     };
                     if (!owner) return sweep(0, q.rows, 0, 0);
                     if (la_lo % 4 == 0 && la_hi % 4 == 0) return sweep(0, q.rows, la_lo, la_hi);

@@ -295,7 +295,7 @@ def perk_launches(reset=True):
 
 
 def perk_expected_launches(kb, ke, np_):
-    """What relax_range_kt issues for pivots [kb, ke): per block of <= 64 pivots from kb one panel launch, the
+    """What relax_range_kt (csrc/fwx_perk.hip) issues for pivots [kb, ke): per block of <= 64 pivots from kb one panel launch, the
     block's pivots np_ at a time, a ragged end down the powers of two, a last single pivot on relax_k."""
     want = [0, 0, 0, 0, 0]
     if np_ == 1 or ke - kb < 2:

@@ -18,13 +18,13 @@ def test_default_is_a_supported_width(monkeypatch):
     assert _default(monkeypatch) in (1, 2, 4, 8)
 
 
-@pytest.mark.parametrize("value", ["1", "2", "4", "8"])
+@pytest.mark.parametrize("value", ["1", "2", "4", "8", " 8", "+4"])     # (as strtol reads it: a leading blank or sign)
 def test_supported_values_are_taken(value, monkeypatch):
     monkeypatch.setenv("FWX_PERK_PIVOTS", value)
     assert _parsed() == int(value)
 
 
-@pytest.mark.parametrize("value", ["", "0", "3", "5", "6", "7", "16", "64", "-2", "-4", "2.5", "4x", "x4", "0x8",
+@pytest.mark.parametrize("value", ["", "0", "8 ", "3", "5", "6", "7", "16", "64", "-2", "-4", "2.5", "4x", "x4", "0x8",
                                    "four", "8 8", "99999999999999999999", "nan"])
 def test_anything_else_is_the_default(value, monkeypatch):
     default = _default(monkeypatch)

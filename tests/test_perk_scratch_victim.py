@@ -1,4 +1,4 @@
-"""The eviction rule of the per-stream snapshot-panel pool (PerkScratch, csrc/fwx_internal.h), as a pure function over
+"""The eviction rule of the per-stream snapshot-panel pool (PerkScratch, csrc/fwx_perk.hip), as a pure function over
 the entries' stamps and in-use marks: fwx_test_perk_scratch_victim.  An entry that a call still inside the library holds
 is never the victim, whatever its stamp; the pool grows past its capacity for the moment instead.  CPU only; the pool
 itself is exercised with more concurrent callers than it keeps by tests/test_gpu_threads.py.  Also the shape of the

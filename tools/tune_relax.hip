@@ -197,7 +197,7 @@ static int stores_sweep(float *d, int n, int per, int rounds)
     return 0;
 }
 
-// `pivots` mode: the multi-pivot schedule of the per-k engine (relax_range_kt in fwx_internal.h).  For NP = 1
+// `pivots` mode: the multi-pivot schedule of the per-k engine (relax_range_kt in fwx_perk.hip).  For NP = 1
 // (relax_k, one launch per pivot) and NP = 2, 4, 8 (relax_kt, geometries RPB x UNROLL; `cmp`: the production
 // geometry with the compare form of the fold forced in every tile, RelaxKtArgs::fold_compare) a window of `per`
 // pivots -- from k = 0, 4096 and 12000, each started from a copy of the matrix state at its first pivot -- is
