@@ -32,6 +32,7 @@ FWX_FUSED_BLOCK = 64
 FWX_BATCH_MAX_N = 128
 FWX_BATCH_MID_MAX_N = 256
 FWX_BATCH_LARGE_MAX_N = 1024
+FWX_SWEEP_MAX_N = FWX_BATCH_MAX_N
 
 
 def batch_large_scratch_bytes(n):
@@ -69,6 +70,20 @@ class FwxPivots(ctypes.Structure):
 
 class FwxTrace(ctypes.Structure):
     _fields_ = [("last", c_vp), ("at_col", c_vp), ("at_row", c_vp)]
+
+
+class FwxSweepPatches(ctypes.Structure):
+    _fields_ = [("ptr", c_vp), ("total", ctypes.c_int64), ("index", c_vp), ("rate", c_vp), ("next", c_vp),
+                ("hops", c_vp)]
+
+
+class FwxSweepItems(ctypes.Structure):
+    _fields_ = [("ptr", c_vp), ("total", ctypes.c_int64), ("src", c_vp), ("dst", c_vp), ("rate_out", c_vp),
+                ("next_out", c_vp), ("hops_out", c_vp)]
+
+
+class FwxSweepFull(ctypes.Structure):
+    _fields_ = [("rate", c_vp), ("next", c_vp), ("hops", c_vp), ("stride", ctypes.c_int64)]
 
 
 class FwxFusedScratch(ctypes.Structure):
@@ -206,6 +221,12 @@ for _mid, _work, _extra in (("", [], []), ("_mid", [], []), ("_large", [c_vp], _
     # count, d_n_each, d_offset, n_max, next0, trace, the items, scratch, stream
     SIGNATURES["fwx_dev_exact_paths_ragged" + _mid] = (
         ctypes.c_int, _RAGGED + [c_vp, c_i32, c_vp, _TRACE] + _ITEMS + [c_vp, c_vp])
+# What-if sweeps: count, n, [dtype,] the base, patches, items, [full,] updates, stream | opts
+_SWEEP = [ctypes.POINTER(FwxSweepPatches), ctypes.POINTER(FwxSweepItems)]
+SIGNATURES["fwx_dev_solve_sweep"] = (
+    ctypes.c_int, _UNIFORM + [c_i32] + _ARRAYS + _SWEEP + [ctypes.POINTER(FwxSweepFull), c_vp, c_vp])
+for _t in ("f64", "f32"):
+    SIGNATURES["fwx_solve_sweep_" + _t] = (ctypes.c_int, _UNIFORM + _ARRAYS + _SWEEP + [c_vp, _OPTS])
 SIGNATURES.update({
     "fwx_test_batch_wave_max_n": (ctypes.c_int, []),
     "fwx_test_batch_mid_min_n": (ctypes.c_int, []),

@@ -634,9 +634,225 @@ int solve_batch_host(const HostForm &form, int32_t count, int32_t n, T *rate, in
     return guarded([&]() -> int { return HostCall<T>{form, count, n, rate, next, hops, updates_each}.run(o); });
 }
 
+// ---- what-if sweeps ---------------------------------------------------------------------------------------------------
+
+// What both sweep forms decide from their host arguments, in fwx.h's order (the dtype is the caller's); FWX_OK with
+// done set: nothing to do.
+int sweep_args(int32_t count, int32_t n, const void *base_rate, const int32_t *base_next, const int32_t *base_hops,
+               const fwx_sweep_patches *p, const fwx_sweep_items *it, const fwx_sweep_full *fu, bool &done)
+{
+    done = true;
+    if (count < 0 || n < 0) return FWX_ERR_INVALID;
+    if (count == 0 || n == 0) return FWX_OK;
+    if (!base_rate || (base_hops && !base_next)) return FWX_ERR_INVALID;
+    if (p) {
+        if ((p->next && !base_next) || (p->hops && !base_hops) || p->total < 0) return FWX_ERR_INVALID;
+        if (p->total > 0 && (!p->ptr || !p->index || !p->rate)) return FWX_ERR_INVALID;
+    }
+    if (it) {
+        if ((it->next_out && !base_next) || (it->hops_out && !base_hops) || it->total < 0) return FWX_ERR_INVALID;
+        if (it->total > 0 && (!it->ptr || !it->src || !it->dst || !it->rate_out)) return FWX_ERR_INVALID;
+    }
+    if (fu) {
+        if ((fu->next && !base_next) || (fu->hops && !base_hops)) return FWX_ERR_INVALID;
+        if ((fu->rate || fu->next || fu->hops) && fu->stride < (int64_t)n * n) return FWX_ERR_INVALID;
+    }
+    if (n > FWX_SWEEP_MAX_N) return FWX_ERR_UNSUPPORTED;
+    done = false;
+    return FWX_OK;
+}
+
+// The launcher's tables from the ABI's structs (any may be null), rates as T.
+template <typename T>
+fwx::SweepTables<T> sweep_tables(const fwx_sweep_patches *p, const fwx_sweep_items *it, const fwx_sweep_full *fu)
+{
+    fwx::SweepTables<T> t;
+    if (p && p->total > 0) {
+        t.patch_ptr = p->ptr;
+        t.patch_total = p->total;
+        t.patch_index = p->index;
+        t.patch_rate = (const T *)p->rate;
+        t.patch_next = p->next;
+        t.patch_hops = p->hops;
+    }
+    if (it && it->total > 0) {
+        t.item_ptr = it->ptr;
+        t.item_total = it->total;
+        t.item_src = it->src;
+        t.item_dst = it->dst;
+        t.item_rate = (T *)it->rate_out;
+        t.item_next = it->next_out;
+        t.item_hops = it->hops_out;
+    }
+    if (fu) {
+        t.full_rate = (T *)fu->rate;
+        t.full_next = fu->next;
+        t.full_hops = fu->hops;
+        t.full_stride = fu->stride;
+    }
+    return t;
+}
+
+// A host table the kernels would have to defend against: ptr[0] != 0, a descending ptr, ptr[count] != total.
+bool sweep_ptr_ok(const int64_t *ptr, int32_t count, int64_t total)
+{
+    if (ptr[0] != 0 || ptr[count] != total) return false;
+    for (int32_t b = 0; b < count; ++b)
+        if (ptr[b + 1] < ptr[b]) return false;
+    return true;
+}
+
+// fwx_solve_sweep_*: the base, the patch arrays and the item arrays go up once into ONE reservation of the pooled
+// context, the item outputs and the counters come down.  Nothing of the caller's is written before the reservation.
+template <typename T>
+int solve_sweep_host(int32_t count, int32_t n, const T *base_rate, const int32_t *base_next, const int32_t *base_hops,
+                     const fwx_sweep_patches *p, const fwx_sweep_items *it, uint64_t *updates_each, const fwx_opts *o)
+{
+    return guarded([&]() -> int {
+        bool done = false;
+        int rc = sweep_args(count, n, base_rate, base_next, base_hops, p, it, nullptr, done);
+        if (rc || done) return rc;
+        Opts op{};
+        if ((rc = read_opts(o, n, op))) return rc;
+        if (op.k_begin != 0 || op.k_end != n) return FWX_ERR_INVALID;
+        if (op.engine != FWX_ENGINE_AUTO) return FWX_ERR_UNSUPPORTED;
+        const int64_t np = p ? p->total : 0, ni = it ? it->total : 0, cells = (int64_t)n * n;
+        if (np > 0) {
+            if (!sweep_ptr_ok(p->ptr, count, np)) return FWX_ERR_INVALID;
+            for (int64_t q = 0; q < np; ++q)
+                if (p->index[q] < 0 || p->index[q] >= cells) return FWX_ERR_INVALID;
+        }
+        if (ni > 0) {
+            if (!sweep_ptr_ok(it->ptr, count, ni)) return FWX_ERR_INVALID;
+            for (int64_t q = 0; q < ni; ++q)
+                if (it->src[q] < 0 || it->src[q] >= n || it->dst[q] < 0 || it->dst[q] >= n) return FWX_ERR_INVALID;
+        }
+        DeviceGuard g{};
+        if ((rc = g.enter(op.device))) return rc;
+        CtxLease lease{};
+        if ((rc = lease.open())) return rc;
+        CallCtx &cx = *lease.c;
+        if (op.has_stream) cx.uses_stream(op.stream);
+        hipStream_t s = op.has_stream ? op.stream : cx.s;
+
+        // the pieces of the reservation, each 16-byte aligned: inputs (host != null: copied up), outputs, counters
+        struct Piece { const void *host; size_t bytes; char *dev; };
+        const size_t ptr_bytes = ((size_t)count + 1) * sizeof(int64_t);
+        const bool counting = updates_each || op.updates_out;
+        enum { BR, BN, BH, PP, PI, PR, PN, PH, IP, IS, ID, OR, ON, OH, UP, NPIECE };
+        Piece pc[NPIECE] = {};
+        pc[BR] = {base_rate, (size_t)cells * sizeof(T), nullptr};
+        pc[BN] = {base_next, base_next ? (size_t)cells * 4 : 0, nullptr};
+        pc[BH] = {base_hops, base_hops ? (size_t)cells * 4 : 0, nullptr};
+        if (np > 0) {
+            pc[PP] = {p->ptr, ptr_bytes, nullptr};
+            pc[PI] = {p->index, (size_t)np * sizeof(int64_t), nullptr};
+            pc[PR] = {p->rate, (size_t)np * sizeof(T), nullptr};
+            pc[PN] = {p->next, p->next ? (size_t)np * 4 : 0, nullptr};
+            pc[PH] = {p->hops, p->hops ? (size_t)np * 4 : 0, nullptr};
+        }
+        if (ni > 0) {
+            pc[IP] = {it->ptr, ptr_bytes, nullptr};
+            pc[IS] = {it->src, (size_t)ni * 4, nullptr};
+            pc[ID] = {it->dst, (size_t)ni * 4, nullptr};
+            pc[OR] = {nullptr, (size_t)ni * sizeof(T), nullptr};
+            pc[ON] = {nullptr, it->next_out ? (size_t)ni * 4 : 0, nullptr};
+            pc[OH] = {nullptr, it->hops_out ? (size_t)ni * 4 : 0, nullptr};
+        }
+        pc[UP] = {nullptr, counting ? (size_t)count * sizeof(unsigned long long) : 0, nullptr};
+        size_t total = 0;
+        for (Piece &a : pc) total += (a.bytes + 15) & ~(size_t)15;
+        void *buf = nullptr;
+        fail_point();
+        if ((rc = cx.reserve(CallCtx::RATE, total, &buf))) return rc;
+        char *at = (char *)buf;
+        for (Piece &a : pc) {
+            if (!a.bytes) continue;
+            a.dev = at;
+            at += (a.bytes + 15) & ~(size_t)15;
+            if (a.host) FWX_HIP(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, s));
+        }
+        if (counting) FWX_HIP(hipMemsetAsync(pc[UP].dev, 0, pc[UP].bytes, s));
+        // the tables passed the checks above, so every item's outputs are written by its variant
+
+        fwx::SweepTables<T> t;
+        if (np > 0) {
+            t.patch_ptr = (const int64_t *)pc[PP].dev;
+            t.patch_total = np;
+            t.patch_index = (const int64_t *)pc[PI].dev;
+            t.patch_rate = (const T *)pc[PR].dev;
+            t.patch_next = (const int32_t *)pc[PN].dev;
+            t.patch_hops = (const int32_t *)pc[PH].dev;
+        }
+        if (ni > 0) {
+            t.item_ptr = (const int64_t *)pc[IP].dev;
+            t.item_total = ni;
+            t.item_src = (const int32_t *)pc[IS].dev;
+            t.item_dst = (const int32_t *)pc[ID].dev;
+            t.item_rate = (T *)pc[OR].dev;
+            t.item_next = (int32_t *)pc[ON].dev;
+            t.item_hops = (int32_t *)pc[OH].dev;
+        }
+        if ((rc = launch_status(fwx::launch_sweep_solve<T>((const T *)pc[BR].dev, (const int32_t *)pc[BN].dev,
+                                                           (const int32_t *)pc[BH].dev, count, n, t,
+                                                           (unsigned long long *)pc[UP].dev, batch_wave_max_n(), s))))
+            return rc;
+        std::vector<unsigned long long> h_upd(counting ? (size_t)count : 0);
+        if (ni > 0) {
+            FWX_HIP(hipMemcpyAsync(it->rate_out, pc[OR].dev, pc[OR].bytes, hipMemcpyDeviceToHost, s));
+            if (it->next_out) FWX_HIP(hipMemcpyAsync(it->next_out, pc[ON].dev, pc[ON].bytes, hipMemcpyDeviceToHost, s));
+            if (it->hops_out) FWX_HIP(hipMemcpyAsync(it->hops_out, pc[OH].dev, pc[OH].bytes, hipMemcpyDeviceToHost, s));
+        }
+        if (counting) FWX_HIP(hipMemcpyAsync(h_upd.data(), pc[UP].dev, pc[UP].bytes, hipMemcpyDeviceToHost, s));
+        FWX_HIP(hipStreamSynchronize(s));
+        uint64_t sum = 0;
+        for (int32_t b = 0; counting && b < count; ++b) {
+            sum += h_upd[(size_t)b];
+            if (updates_each) updates_each[b] = h_upd[(size_t)b];
+        }
+        if (op.updates_out) *op.updates_out = sum;
+        return FWX_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- what-if sweeps ---------------------------------------------------------------------------------------------------
+
+int fwx_dev_solve_sweep(int32_t count, int32_t n, int32_t dtype, const void *base_rate, const int32_t *base_next,
+                        const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                        const fwx_sweep_full *full, unsigned long long *d_updates_each, void *stream)
+{
+    return guarded([&]() -> int {
+        if (dtype != FWX_F32 && dtype != FWX_F64) return FWX_ERR_INVALID;
+        bool done = false;
+        const int rc = sweep_args(count, n, base_rate, base_next, base_hops, patches, items, full, done);
+        if (rc || done) return rc;
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        return with_dtype(dtype, (void *)base_rate, [&](auto *r) {
+            using T = std::remove_pointer_t<decltype(r)>;
+            return launch_status(fwx::launch_sweep_solve<T>(r, base_next, base_hops, count, n,
+                                                            sweep_tables<T>(patches, items, full), d_updates_each,
+                                                            batch_wave_max_n(), (hipStream_t)stream));
+        });
+    });
+}
+
+int fwx_solve_sweep_f64(int32_t count, int32_t n, const double *base_rate, const int32_t *base_next,
+                        const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                        uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_sweep_host<double>(count, n, base_rate, base_next, base_hops, patches, items, updates_each, opts);
+}
+
+int fwx_solve_sweep_f32(int32_t count, int32_t n, const float *base_rate, const int32_t *base_next,
+                        const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                        uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_sweep_host<float>(count, n, base_rate, base_next, base_hops, patches, items, updates_each, opts);
+}
 
 // ---- uniform batches: host forms ----------------------------------------------------------------------------------
 

@@ -170,6 +170,33 @@ hipError_t launch_batch_solve(T *rate, int32_t *next, int32_t *hops, int count, 
                               int k_begin, int k_end, unsigned long long *updates_each, int wave_max_n,
                               hipStream_t s, PathLog plog = PathLog());
 
+// What-if sweeps: `count` variants of ONE base matrix of order n <= FWX_SMALL_N (pitch n, never written) in one
+// launch (one per 2^21 variants), tiers as launch_batch_solve.  Variant b is the base with the patches [patch_ptr[b],
+// patch_ptr[b+1]) applied in list order (patch_next / patch_hops optional: that field of the cell keeps the base's
+// value); it answers its items [item_ptr[b], item_ptr[b+1]) into item_rate / item_next / item_hops (the last two
+// optional) and, where a full output is given (each optional), stores its whole n x n part at + b*full_stride,
+// diagonal included, the gap never.  counter b of updates_each (or nullptr) is incremented by U of variant b.
+// Everything is device memory.  The kernels clamp each ptr range into [0, total] and pass over patch indices and
+// item vertices that do not belong to the order; what the host arguments decide is hipErrorInvalidValue.
+template <typename T> struct SweepTables {
+    const int64_t *patch_ptr = nullptr;
+    long long patch_total = 0;
+    const int64_t *patch_index = nullptr;
+    const T *patch_rate = nullptr;
+    const int32_t *patch_next = nullptr, *patch_hops = nullptr;
+    const int64_t *item_ptr = nullptr;
+    long long item_total = 0;
+    const int32_t *item_src = nullptr, *item_dst = nullptr;
+    T *item_rate = nullptr;
+    int32_t *item_next = nullptr, *item_hops = nullptr;
+    T *full_rate = nullptr;
+    int32_t *full_next = nullptr, *full_hops = nullptr;
+    long long full_stride = 0;
+};
+template <typename T>
+hipError_t launch_sweep_solve(const T *base_rate, const int32_t *base_next, const int32_t *base_hops, int count, int n,
+                              const SweepTables<T> &t, unsigned long long *updates_each, int wave_max_n, hipStream_t s);
+
 // Mid tier of the batched solves (fwx_mid.hip): `count` matrices of one order n <= FWX_MID_N, same layout and
 // counters as launch_batch_solve, one workgroup per matrix, the matrix resident in global memory and FWX_MID_B
 // pivots per pass from time-k snapshot panels in LDS.  Any n from 1 up, any stride >= n*n, scalar accesses only.

@@ -1031,6 +1031,113 @@ void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, 
 }
 
 // -------------------------------------------------------------------------------------------------
+// Where the matrix of a small solve comes from and where it goes: the load stage and the store stage of
+// small_solve_body and wave_solve_body, which hold the one pivot loop in between.
+//   InPlaceIO  the matrix is solved where it lies (small_solve, the batch and the ragged kernels).  The register of
+//              a diagonal entry holds +inf and its value in memory is left alone.
+//   SweepIO    variant b of a what-if sweep (small_solve_sweep, wave_solve_sweep): the entries are the BASE's (const,
+//              the same for every variant), then the variant's patches in list order; nothing goes back to the base.
+//              The items of the variant are answered from the registers, the whole matrix goes to the full outputs
+//              if there are any.  There is no memory left alone here, so the (patched) diagonal rate is kept aside
+//              by the thread that owns it -- `dg` in the bodies -- and is what an item on (i, i) and a full output
+//              receive.
+// in_base / out_base: element offsets the wave body adds (its loads and stores keep one scalar base each); the
+// workgroup body is handed pointers that include them and passes 0.
+// The bodies know their layout: they hand patches() a `put` and items() a `get`, both an unrolled select over the
+// thread's entries (no register array is indexed dynamically); the policy walks the tables, through wave-uniform
+// addresses, and holds the defence against tables that do not belong to the arrays.
+// -------------------------------------------------------------------------------------------------
+template <typename T> struct InPlaceIO {
+    static constexpr bool SWEEP = false;
+    T *in_rate;
+    int32_t *in_next, *in_hops;
+    T *out_rate;
+    int32_t *out_next, *out_hops;
+    size_t in_base, out_base;
+    __device__ __forceinline__ InPlaceIO(T *rate, int32_t *next, int32_t *hops, size_t base = 0)
+        : in_rate(rate), in_next(next), in_hops(hops), out_rate(rate), out_next(next), out_hops(hops), in_base(base),
+          out_base(base) {}
+    __device__ __forceinline__ void put_rate(size_t off, T v, bool diag, T) const { if (!diag) out_rate[off] = v; }
+    __device__ __forceinline__ void put_next(size_t off, int32_t v) const { out_next[off] = v; }
+    __device__ __forceinline__ void put_hops(size_t off, int32_t v) const { out_hops[off] = v; }
+};
+
+__device__ __forceinline__ long long uniform64(long long v)
+{
+    return (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)v));
+}
+
+template <typename T> struct SweepIO {
+    static constexpr bool SWEEP = true;
+    const T *in_rate;                          // the base, pitch n
+    const int32_t *in_next, *in_hops;
+    T *out_rate;                               // the full outputs of this variant, each optional
+    int32_t *out_next, *out_hops;
+    size_t in_base, out_base;
+    int n;
+    const int64_t *patch_index;                // this variant's patches: [p0, p1) of the patch arrays
+    const T *patch_rate;
+    const int32_t *patch_next, *patch_hops;    // optional
+    long long p0, p1;
+    const int32_t *item_src, *item_dst;        // this variant's items: [q0, q1) of the item arrays
+    T *item_rate;
+    int32_t *item_next, *item_hops;            // optional
+    long long q0, q1;
+
+    // [ptr[b], ptr[b + 1]) clamped into [0, total]; a descending pair and a null table are empty ranges
+    __device__ __forceinline__ static void range(const int64_t *ptr, long long b, long long total, long long &lo,
+                                                 long long &hi)
+    {
+        lo = hi = 0;
+        if (!ptr || total <= 0) return;
+        long long a = uniform64(ptr[b]), e = uniform64(ptr[b + 1]);
+        a = a < 0 ? 0 : a;
+        e = e > total ? total : e;
+        lo = a;
+        hi = e < a ? a : e;
+    }
+    // put(cell, rate, has_next, next, has_hops, hops) for every patch in list order; an index outside [0, n * n) is
+    // ignored
+    template <typename Put> __device__ __forceinline__ void patches(Put &&put) const
+    {
+        const long long cells = (long long)n * n;
+#pragma unroll 1
+        for (long long q = p0; q < p1; ++q) {
+            const long long idx = uniform64(patch_index[q]);
+            if (idx < 0 || idx >= cells) continue;
+            int32_t pn = -1, ph = 0;
+            if (patch_next) pn = patch_next[q];
+            if (patch_hops) ph = patch_hops[q];
+            put((int)idx, patch_rate[q], patch_next != nullptr, pn, patch_hops != nullptr, ph);
+        }
+    }
+    // get(src, dst, rate, next, hops) -> "this thread holds the entry"; it writes the item's outputs.  An item whose
+    // src or dst is outside [0, n) leaves them untouched.
+    template <typename Get> __device__ __forceinline__ void items(Get &&get) const
+    {
+#pragma unroll 1
+        for (long long q = q0; q < q1; ++q) {
+            const int s = __builtin_amdgcn_readfirstlane(item_src[q]), d = __builtin_amdgcn_readfirstlane(item_dst[q]);
+            if ((unsigned)s >= (unsigned)n || (unsigned)d >= (unsigned)n) continue;
+            T v;
+            int32_t nv = -1, hv = 0;
+            if (get(s, d, v, nv, hv)) {
+                item_rate[q] = v;
+                if (item_next) item_next[q] = nv;
+                if (item_hops) item_hops[q] = hv;
+            }
+        }
+    }
+    __device__ __forceinline__ void put_rate(size_t off, T v, bool diag, T dg) const
+    {
+        if (out_rate) out_rate[off] = diag ? dg : v;
+    }
+    __device__ __forceinline__ void put_next(size_t off, int32_t v) const { if (out_next) out_next[off] = v; }
+    __device__ __forceinline__ void put_hops(size_t off, int32_t v) const { if (out_hops) out_hops[off] = v; }
+};
+
+// -------------------------------------------------------------------------------------------------
 // small_solve: the whole of runAlgo for n <= 128 in ONE launch of one workgroup -- the reference's
 // own regime (its tests stop at 4 x 4, src/test/AlgorithmsTest.hs:66-77; the README session has 4
 // vertices; a market of 10 exchanges x 12 currencies has 120).  The matrix is padded with NaN to
@@ -1041,12 +1148,12 @@ void relax_walk(float *rate, const float *w, const float *ct, int ct_ld, int n, 
 // enough.  Row k and column k are fixed points of step k, so what step k reads are exactly the
 // step-start operands (Algorithms.hs:58-60).
 //
-// The body is shared by two kernels: small_solve (one matrix, one workgroup) and small_solve_batch (the
-// workgroup tier of the batched solve: workgroup b solves matrix b of a batch).
+// The body is shared by the kernels small_solve (one matrix, one workgroup), small_solve_batch (the workgroup tier
+// of the batched solve: workgroup b solves matrix b of a batch), small_solve_ragged and small_solve_sweep (workgroup
+// b solves variant b of one base matrix); `io` (InPlaceIO or SweepIO, above) is its load and its store stage.
 // -------------------------------------------------------------------------------------------------
-template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
-__device__ __forceinline__ void small_solve_body(T *rate, int32_t *next, int32_t *hops, int n,
-                                                 int k_begin, int k_end,
+template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS, bool LOG, typename IO>
+__device__ __forceinline__ void small_solve_body(const IO &io, int n, int k_begin, int k_end,
                                                  unsigned long long *updates, PathLog plog)
 {
     constexpr int E = M / RG;                 // entries per thread; rows r = r0 + RG*m
@@ -1076,6 +1183,7 @@ __device__ __forceinline__ void small_solve_body(T *rate, int32_t *next, int32_t
 
     T x[E];
     int32_t nx[HAS_NEXT && !IDXL ? E : 1], hp[HAS_HOPS && !IDXL ? E : 1], hd[LOG ? E : 1];
+    [[maybe_unused]] T dg = quiet_nan<T>();   // sweep: my diagonal entry's rate (a thread owns at most one)
     auto publish = [&](int k, int b) {        // my entries of row k / column k -> buffer b
 #pragma unroll
         for (int m = 0; m < E; ++m) {
@@ -1101,20 +1209,38 @@ __device__ __forceinline__ void small_solve_body(T *rate, int32_t *next, int32_t
     for (int m = 0; m < E; ++m) {
         const int r = r0 + RG * m;
         const bool in = r < n && c < n;
-        x[m] = in ? rate[off0 + m * off_step] : quiet_nan<T>();
+        x[m] = in ? io.in_rate[off0 + m * off_step] : quiet_nan<T>();
+        if constexpr (IO::SWEEP) { if (r == c) dg = x[m]; }
         // skip j == i: a diagonal entry is never an operand (it could only be one in the steps
         // that skip it) and never a target, so its register holds +inf -- no candidate compares
         // greater -- and the value in memory is left as it is
         if (r == c) x[m] = (T)__builtin_huge_val();
         if constexpr (HAS_NEXT) {
-            const int32_t v = in ? next[off0 + m * off_step] : -1;
+            const int32_t v = in ? io.in_next[off0 + m * off_step] : -1;
             if constexpr (IDXL) NX[r][c] = v; else nx[m] = v;
         }
         if constexpr (HAS_HOPS) {
-            const int32_t v = in ? hops[off0 + m * off_step] : 0;
+            const int32_t v = in ? io.in_hops[off0 + m * off_step] : 0;
             if constexpr (IDXL) HP[r][c] = v; else hp[m] = v;
         }
         if constexpr (LOG) hd[m] = -1;
+    }
+    if constexpr (IO::SWEEP) {
+        // the variant's patches: the thread that owns the cell takes the value (a diagonal rate goes aside, its
+        // register stays +inf); NX / HP are written by their owner before the first barrier
+        io.patches([&](int cell, T v, bool hn, int32_t pn, bool hh, int32_t ph) {
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                const int r = r0 + RG * m;
+                const bool hit = r < n && c < n && cell == off0 + m * off_step;
+                dg = hit && r == c ? v : dg;
+                x[m] = hit && r != c ? v : x[m];
+                if constexpr (NXL) { if (hit && hn) NX[r][c] = pn; }
+                else if constexpr (HAS_NEXT) nx[m] = hit && hn ? pn : nx[m];
+                if constexpr (HPL) { if (hit && hh) HP[r][c] = ph; }
+                else if constexpr (HAS_HOPS) hp[m] = hit && hh ? ph : hp[m];
+            }
+        });
     }
     publish(k_begin, k_begin & 1);
     __syncthreads();
@@ -1169,13 +1295,34 @@ __device__ __forceinline__ void small_solve_body(T *rate, int32_t *next, int32_t
     for (int m = 0; m < E; ++m) {
         const int r = r0 + RG * m;
         if (r < n && c < n) {
-            if (r != c) rate[off0 + m * off_step] = x[m];
-            if constexpr (NXL) next[off0 + m * off_step] = NX[r][c];
-            else if constexpr (HAS_NEXT) next[off0 + m * off_step] = nx[m];
-            if constexpr (HPL) hops[off0 + m * off_step] = HP[r][c];
-            else if constexpr (HAS_HOPS) hops[off0 + m * off_step] = hp[m];
+            io.put_rate(off0 + m * off_step, x[m], r == c, dg);
+            if constexpr (NXL) io.put_next(off0 + m * off_step, NX[r][c]);
+            else if constexpr (HAS_NEXT) io.put_next(off0 + m * off_step, nx[m]);
+            if constexpr (HPL) io.put_hops(off0 + m * off_step, HP[r][c]);
+            else if constexpr (HAS_HOPS) io.put_hops(off0 + m * off_step, hp[m]);
             if constexpr (LOG) plog.last[off0 + m * off_step] = hd[m];
         }
+    }
+    if constexpr (IO::SWEEP) {
+        // the variant's items: entry (s, d) is register s / RG of the thread (s % RG, d)
+        io.items([&](int s, int d, T &v, int32_t &nv, int32_t &hv) -> bool {
+            const int ms = s / RG;
+            const bool own = c == d && r0 == (s & (RG - 1));
+            T xv = dg;                        // s == d: the diagonal entry of the thread that holds it
+            // the index is a constant of each step from the start: a rolled `m == ms ? x[m] : xv` comes back
+            // from the optimiser as x[ms], and the array with it as LDS or scratch
+            for_slots<E>([&](auto mc) {
+                constexpr int m = decltype(mc)::value;
+                const bool at = m == ms;      // scalar
+                xv = at && s != d ? x[m] : xv;
+                if constexpr (HAS_NEXT && !IDXL) nv = at ? nx[m] : nv;
+                if constexpr (HAS_HOPS && !IDXL) hv = at ? hp[m] : hv;
+            });
+            v = xv;
+            if constexpr (NXL) { if (own) nv = NX[s][d]; }
+            if constexpr (HPL) { if (own) hv = HP[s][d]; }
+            return own;
+        });
     }
     if (updates) {
         if (mine && (tid & 63) == 0) atomicAdd(&s_cnt, mine);   // `mine` is a wave total
@@ -1189,7 +1336,7 @@ __global__ __launch_bounds__(M * RG) void small_solve(T *rate, int32_t *next, in
                                                       int k_begin, int k_end,
                                                       unsigned long long *updates, PathLog plog)
 {
-    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(rate, next, hops, n, k_begin, k_end, updates, plog);
+    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(InPlaceIO<T>(rate, next, hops), n, k_begin, k_end, updates, plog);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1207,9 +1354,10 @@ __global__ __launch_bounds__(M * RG) void small_solve_batch(T *rate, int32_t *ne
 {
     const size_t off = (size_t)blockIdx.x * (size_t)stride;
     if constexpr (LOG) { plog.last += off; plog.at_col += off; plog.at_row += off; }
-    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(rate + off, HAS_NEXT ? next + off : nullptr,
-                                                        HAS_HOPS ? hops + off : nullptr, n, k_begin, k_end,
-                                                        updates ? updates + blockIdx.x : nullptr, plog);
+    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(InPlaceIO<T>(rate + off, HAS_NEXT ? next + off : nullptr,
+                                                                     HAS_HOPS ? hops + off : nullptr),
+                                                        n, k_begin, k_end, updates ? updates + blockIdx.x : nullptr,
+                                                        plog);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1234,13 +1382,13 @@ __global__ __launch_bounds__(M * RG) void small_solve_batch(T *rate, int32_t *ne
 // change inside the step and "the start of step k" is anywhere in it: the stores are issued at the top,
 // before the cross-lane reads, and drain behind them.  `last` is stored with the results.
 //
-// The body is shared by two kernels: wave_solve_batch (wave b on matrix b, at b*stride) and wave_solve_ragged (the
-// wave tier of the ragged batch: its own order and offset per wave).  n is wave-uniform in both; the matrix is at
-// + base in all arrays, its U goes to updates[b].
+// The body is shared by three kernels: wave_solve_batch (wave b on matrix b, at b*stride), wave_solve_ragged (the
+// wave tier of the ragged batch: its own order and offset per wave) and wave_solve_sweep (wave b on variant b of one
+// base matrix).  n is wave-uniform in all; `io` (InPlaceIO or SweepIO) is the load and the store stage: the matrix
+// is read at + io.in_base and written at + io.out_base, the trace at + io.out_base; its U goes to updates[b].
 // -------------------------------------------------------------------------------------------------
-template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool LOG>
-__device__ __forceinline__ void wave_solve_body(T *rate, int32_t *next, int32_t *hops, int n, size_t base,
-                                                long long b, int k_begin, int k_end,
+template <typename T, bool HAS_NEXT, bool HAS_HOPS, bool LOG, typename IO>
+__device__ __forceinline__ void wave_solve_body(const IO &io, int n, long long b, int k_begin, int k_end,
                                                 unsigned long long *updates, PathLog plog)
 {
     constexpr int E = 4;                      // rows per lane: q, q + 4, q + 8, q + 12
@@ -1249,20 +1397,35 @@ __device__ __forceinline__ void wave_solve_body(T *rate, int32_t *next, int32_t 
 
     T x[E];
     int32_t nx[E], hp[E], hd[LOG ? E : 1];
-    if constexpr (LOG) { plog.last += base; plog.at_col += base; plog.at_row += base; }
+    [[maybe_unused]] T dg = quiet_nan<T>();   // sweep: my diagonal entry's rate (a lane owns at most one)
+    if constexpr (LOG) { plog.last += io.out_base; plog.at_col += io.out_base; plog.at_row += io.out_base; }
     const int qn = q * n;
 #pragma unroll
     for (int m = 0; m < E; ++m) {
         const int r = q + 4 * m;
         const bool in = r < n && c < n;
-        const size_t off = base + (size_t)(r * n + c);
+        const size_t off = io.in_base + (size_t)(r * n + c);
         if constexpr (LOG) hd[m] = -1;
-        x[m] = in ? rate[off] : quiet_nan<T>();
+        x[m] = in ? io.in_rate[off] : quiet_nan<T>();
+        if constexpr (IO::SWEEP) { if (r == c) dg = x[m]; }
         if (r == c) x[m] = (T)__builtin_huge_val();           // skip j == i (see small_solve)
         nx[m] = -1;
         hp[m] = 0;
-        if constexpr (HAS_NEXT) { if (in) nx[m] = next[off]; }
-        if constexpr (HAS_HOPS) { if (in) hp[m] = hops[off]; }
+        if constexpr (HAS_NEXT) { if (in) nx[m] = io.in_next[off]; }
+        if constexpr (HAS_HOPS) { if (in) hp[m] = io.in_hops[off]; }
+    }
+    if constexpr (IO::SWEEP) {                // the variant's patches (see small_solve_body)
+        io.patches([&](int cell, T v, bool hn, int32_t pn, bool hh, int32_t ph) {
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                const int r = q + 4 * m;
+                const bool hit = r < n && c < n && cell == r * n + c;
+                dg = hit && r == c ? v : dg;
+                x[m] = hit && r != c ? v : x[m];
+                if constexpr (HAS_NEXT) nx[m] = hit && hn ? pn : nx[m];
+                if constexpr (HAS_HOPS) hp[m] = hit && hh ? ph : hp[m];
+            }
+        });
     }
 
     unsigned int mine = 0;
@@ -1321,12 +1484,27 @@ __device__ __forceinline__ void wave_solve_body(T *rate, int32_t *next, int32_t 
     for (int m = 0; m < E; ++m) {
         const int r = q + 4 * m;
         if (r < n && c < n) {
-            const size_t off = base + (size_t)(r * n + c);
-            if (r != c) rate[off] = x[m];
-            if constexpr (HAS_NEXT) next[off] = nx[m];
-            if constexpr (HAS_HOPS) hops[off] = hp[m];
+            const size_t off = io.out_base + (size_t)(r * n + c);
+            io.put_rate(off, x[m], r == c, dg);
+            if constexpr (HAS_NEXT) io.put_next(off, nx[m]);
+            if constexpr (HAS_HOPS) io.put_hops(off, hp[m]);
             if constexpr (LOG) (plog.last + 4 * m * n)[qn + c] = hd[m];
         }
+    }
+    if constexpr (IO::SWEEP) {                // the variant's items: entry (s, d) is register s / 4 of lane (s % 4, d)
+        io.items([&](int s, int d, T &v, int32_t &nv, int32_t &hv) -> bool {
+            const int ms = s >> 2;
+            T xv = dg;
+            for_slots<E>([&](auto mc) {       // constant indices from the start, as in small_solve_body
+                constexpr int m = decltype(mc)::value;
+                const bool at = m == ms;      // scalar
+                xv = at && s != d ? x[m] : xv;
+                if constexpr (HAS_NEXT) nv = at ? nx[m] : nv;
+                if constexpr (HAS_HOPS) hv = at ? hp[m] : hv;
+            });
+            v = xv;
+            return lane == ((s & 3) << 4 | d);
+        });
     }
     if (updates && mine && lane == 0) atomicAdd(&updates[b], (unsigned long long)mine);
 }
@@ -1339,8 +1517,8 @@ __global__ __launch_bounds__(256) void wave_solve_batch(T *rate, int32_t *next, 
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const long long b = (long long)blockIdx.x * 4 + wave;
     if (b >= count) return;                   // wave-uniform
-    wave_solve_body<T, HAS_NEXT, HAS_HOPS, LOG>(rate, next, hops, n, (size_t)b * (size_t)stride, b, k_begin, k_end,
-                                                updates, plog);
+    wave_solve_body<T, HAS_NEXT, HAS_HOPS, LOG>(InPlaceIO<T>(rate, next, hops, (size_t)b * (size_t)stride), n, b, k_begin,
+                                                k_end, updates, plog);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1364,9 +1542,9 @@ __global__ __launch_bounds__(M * RG) void small_solve_ragged(T *rate, int32_t *n
     if (n <= 0 || n > M) return;
     const size_t off = (size_t)offset[id];
     if constexpr (LOG) { plog.last += off; plog.at_col += off; plog.at_row += off; }
-    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(rate + off, HAS_NEXT ? next + off : nullptr,
-                                                        HAS_HOPS ? hops + off : nullptr, n, 0, n,
-                                                        updates ? updates + id : nullptr, plog);
+    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, LOG>(InPlaceIO<T>(rate + off, HAS_NEXT ? next + off : nullptr,
+                                                                     HAS_HOPS ? hops + off : nullptr),
+                                                        n, 0, n, updates ? updates + id : nullptr, plog);
 }
 
 // Wave tier: wave w of the launch (four per workgroup) on matrix order[w]; a wave past tier_count leaves at once.
@@ -1386,7 +1564,7 @@ __global__ __launch_bounds__(256) void wave_solve_ragged(T *rate, int32_t *next,
     const int64_t off = offset[id];            // wave-uniform too: the base of every load and store of the body
     const size_t base =((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) |
                         (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)off);
-    wave_solve_body<T, HAS_NEXT, HAS_HOPS, LOG>(rate, next, hops, n, base, (long long)id, 0, n, updates, plog);
+    wave_solve_body<T, HAS_NEXT, HAS_HOPS, LOG>(InPlaceIO<T>(rate, next, hops, base), n, (long long)id, 0, n, updates, plog);
 }
 
 template <typename T>
@@ -1439,6 +1617,126 @@ template hipError_t launch_batch_solve<float>(float *, int32_t *, int32_t *, int
                                               unsigned long long *, int, hipStream_t, PathLog);
 template hipError_t launch_batch_solve<double>(double *, int32_t *, int32_t *, int, int, long long, int, int,
                                                unsigned long long *, int, hipStream_t, PathLog);
+
+// -------------------------------------------------------------------------------------------------
+// What-if sweeps: `count` variants of ONE base matrix of order n <= 128 in one launch.  Variant b is the base (pitch
+// n, const, the same for every variant) with the patches [patch_ptr[b], patch_ptr[b+1]) applied in list order: patch
+// q puts patch_rate[q] -- and patch_next[q] / patch_hops[q] where those arrays are given -- at cell patch_index[q] =
+// i*n + j; a later patch of a cell wins.  The solved variant answers its items [item_ptr[b], item_ptr[b+1]): entry
+// (item_src[q], item_dst[q]) goes to out.item_rate[q] (item_next, item_hops alike, optional), and, where a full
+// output is given, its whole n x n part goes there at + b*stride, diagonal included, the gap never.  U of variant b
+// is added to out.updates[b].  Whole pivot range, no trace.
+//
+// The kernels are the batch kernels with SweepIO in place of InPlaceIO: small_solve_sweep is workgroup b on variant b,
+// wave_solve_sweep wave b (four per workgroup; a wave past `count` leaves at once).  The tables are read through
+// wave-uniform addresses; their pointers are __restrict__ so that the item loads, which follow stores, stay scalar.
+// The device form cannot see the tables: each [ptr[b], ptr[b+1]) is clamped into [0, total] (a descending pair is
+// empty), a patch index outside [0, n*n) is ignored and an item whose src or dst is outside [0, n) leaves its
+// outputs alone, so nothing outside the arrays' stated extents is read or written whatever the tables hold.
+// -------------------------------------------------------------------------------------------------
+template <typename T> struct SweepOut {
+    T *item_rate;
+    int32_t *item_next, *item_hops;
+    T *full_rate;
+    int32_t *full_next, *full_hops;
+    long long stride;
+    unsigned long long *updates;
+};
+
+#define FWX_SWEEP_PARAMS                                                                                           \
+    const T *__restrict__ base_rate, const int32_t *__restrict__ base_next, const int32_t *__restrict__ base_hops, \
+        int n, int count, const int64_t *__restrict__ patch_ptr, long long patch_total,                            \
+        const int64_t *__restrict__ patch_index, const T *__restrict__ patch_rate,                                 \
+        const int32_t *__restrict__ patch_next, const int32_t *__restrict__ patch_hops,                            \
+        const int64_t *__restrict__ item_ptr, long long item_total, const int32_t *__restrict__ item_src,          \
+        const int32_t *__restrict__ item_dst, SweepOut<T> out
+
+// Variant b's policy; full_off: what the body does not add to the full outputs itself.
+#define FWX_SWEEP_IO(io, b, full_off, body_off)                                                                    \
+    SweepIO<T> io;                                                                                                 \
+    io.in_rate = base_rate; io.in_next = base_next; io.in_hops = base_hops;                                        \
+    io.out_rate = out.full_rate ? out.full_rate + (full_off) : nullptr;                                            \
+    io.out_next = out.full_next ? out.full_next + (full_off) : nullptr;                                            \
+    io.out_hops = out.full_hops ? out.full_hops + (full_off) : nullptr;                                            \
+    io.in_base = 0; io.out_base = (body_off); io.n = n;                                                            \
+    io.patch_index = patch_index; io.patch_rate = patch_rate; io.patch_next = patch_next; io.patch_hops = patch_hops; \
+    io.item_src = item_src; io.item_dst = item_dst;                                                                \
+    io.item_rate = out.item_rate; io.item_next = out.item_next; io.item_hops = out.item_hops;                      \
+    SweepIO<T>::range(patch_ptr, (b), patch_total, io.p0, io.p1);                                                  \
+    SweepIO<T>::range(item_ptr, (b), item_total, io.q0, io.q1)
+
+template <typename T, int M, int RG, bool HAS_NEXT, bool HAS_HOPS>
+__global__ __launch_bounds__(M * RG) void small_solve_sweep(FWX_SWEEP_PARAMS)
+{
+    const size_t off = (size_t)blockIdx.x * (size_t)out.stride;
+    FWX_SWEEP_IO(io, (long long)blockIdx.x, off, (size_t)0);
+    small_solve_body<T, M, RG, HAS_NEXT, HAS_HOPS, false>(io, n, 0, n, out.updates ? out.updates + blockIdx.x : nullptr,
+                                                          PathLog{});
+}
+
+template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+__global__ __launch_bounds__(256) void wave_solve_sweep(FWX_SWEEP_PARAMS)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const long long b = (long long)blockIdx.x * 4 + wave;
+    if (b >= count) return;                   // wave-uniform
+    FWX_SWEEP_IO(io, b, (size_t)0, (size_t)b * (size_t)out.stride);
+    wave_solve_body<T, HAS_NEXT, HAS_HOPS, false>(io, n, b, 0, n, out.updates, PathLog{});
+}
+#undef FWX_SWEEP_IO
+#undef FWX_SWEEP_PARAMS
+
+template <typename T>
+hipError_t launch_sweep_solve(const T *base_rate, const int32_t *base_next, const int32_t *base_hops, int count, int n,
+                              const SweepTables<T> &t, unsigned long long *updates_each, int wave_max_n, hipStream_t s)
+{
+    if (count <= 0 || n <= 0) return hipSuccess;
+    if (n > FWX_SMALL_N || !base_rate || (base_hops && !base_next) || t.patch_total < 0 || t.item_total < 0 ||
+        (t.patch_total > 0 && (!t.patch_ptr || !t.patch_index || !t.patch_rate)) ||
+        (t.item_total > 0 && (!t.item_ptr || !t.item_src || !t.item_dst || !t.item_rate)) ||
+        ((t.patch_next || t.item_next || t.full_next) && !base_next) ||
+        ((t.patch_hops || t.item_hops || t.full_hops) && !base_hops) ||
+        ((t.full_rate || t.full_next || t.full_hops) && t.full_stride < (long long)n * n))
+        return hipErrorInvalidValue;
+    const bool wave = n <= wave_max_n && n <= FWX_BATCH_WAVE_N;
+    constexpr int kChunk = 1 << 21;           // workgroups per launch, as launch_batch_solve
+    for (long long b0 = 0; b0 < count; b0 += kChunk) {
+        const int cnt = (int)std::min<long long>(kChunk, count - b0);
+        const size_t off = (size_t)b0 * (size_t)t.full_stride;
+        const SweepOut<T> out = {t.item_rate, t.item_next, t.item_hops, t.full_rate ? t.full_rate + off : nullptr,
+                                 t.full_next ? t.full_next + off : nullptr, t.full_hops ? t.full_hops + off : nullptr,
+                                 t.full_stride, updates_each ? updates_each + b0 : nullptr};
+        const int64_t *pp = t.patch_total > 0 ? t.patch_ptr + b0 : nullptr, *ip = t.item_total > 0 ? t.item_ptr + b0 : nullptr;
+#define FWX_SWEEP_ARGS                                                                                             \
+    base_rate, base_next, base_hops, n, cnt, pp, (long long)t.patch_total, t.patch_index, t.patch_rate,            \
+        t.patch_next, t.patch_hops, ip, (long long)t.item_total, t.item_src, t.item_dst, out
+#define FWX_SWEEP_WAVE(HN, HH)                                                                     \
+    hipLaunchKernelGGL((wave_solve_sweep<T, HN, HH>), dim3((cnt + 3) / 4), dim3(256), 0, s, FWX_SWEEP_ARGS)
+#define FWX_SWEEP_WG(M, RG, HN, HH)                                                                \
+    hipLaunchKernelGGL((small_solve_sweep<T, M, RG, HN, HH>), dim3(cnt), dim3(M * RG), 0, s, FWX_SWEEP_ARGS)
+#define FWX_SWEEP_FIELDS(LAUNCH, ...)                                                              \
+    do {                                                                                           \
+        if (base_hops) LAUNCH(__VA_ARGS__ true, true);                                             \
+        else if (base_next) LAUNCH(__VA_ARGS__ true, false);                                       \
+        else LAUNCH(__VA_ARGS__ false, false);                                                     \
+    } while (0)
+        if (wave) FWX_SWEEP_FIELDS(FWX_SWEEP_WAVE);
+        else if (n <= 64) FWX_SWEEP_FIELDS(FWX_SWEEP_WG, 64, 16,);
+        else FWX_SWEEP_FIELDS(FWX_SWEEP_WG, 128, 8,);
+#undef FWX_SWEEP_FIELDS
+#undef FWX_SWEEP_WG
+#undef FWX_SWEEP_WAVE
+#undef FWX_SWEEP_ARGS
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template hipError_t launch_sweep_solve<float>(const float *, const int32_t *, const int32_t *, int, int,
+                                              const SweepTables<float> &, unsigned long long *, int, hipStream_t);
+template hipError_t launch_sweep_solve<double>(const double *, const int32_t *, const int32_t *, int, int,
+                                               const SweepTables<double> &, unsigned long long *, int, hipStream_t);
 
 template <typename T>
 hipError_t launch_ragged_solve(T *rate, int32_t *next, int32_t *hops, int count, const int32_t *n_each,

@@ -200,6 +200,129 @@ def _dev_solve_batch(name, rate_t, count, n, next_t, hops_t, stride, k_begin, k_
         _stream_ptr(stream, rate_t)), name)
 
 
+def _sweep_csr(per_variant, count, what):
+    """(ptr int64[count + 1], the per-variant tuples with empty ones as ()) of a per-variant list."""
+    if per_variant is None:
+        per_variant = [()] * count
+    if len(per_variant) != count:
+        raise ValueError("%s must have one entry per variant" % what)
+    rows = [() if v is None else tuple(np.atleast_1d(np.asarray(a)) for a in v) for v in per_variant]
+    ptr = np.zeros(count + 1, dtype=np.int64)
+    for b, v in enumerate(rows):
+        if v and any(a.shape != v[0].shape or a.ndim != 1 for a in v):
+            raise ValueError("the arrays of %s[%d] must be 1-D and equally long" % (what, b))
+        ptr[b + 1] = ptr[b] + (len(v[0]) if v else 0)
+    return ptr, rows
+
+
+def solve_sweep(base_rate, base_next=None, base_hops=None, *, patches, items, device=-1, count_updates=False):
+    """A what-if sweep in ONE call (fwx_solve_sweep_f64 / _f32): variant b is base_rate (n x n, n <=
+    FWX_SWEEP_MAX_N; base_next / base_hops alike) with patches[b] applied in order, solved whole; only the entries
+    items[b] asks for come back.  The base is not written.
+
+    patches: per variant None / () or (index, rate[, next[, hops]]) -- index = i * n + j, a later patch of a cell wins;
+    next / hops must be given by every variant that has patches, or by none (then that field of a patched cell
+    keeps the base's value).  items: per variant None / () or (src, dst).  len(patches) == len(items) == count
+    (either may be None: no patches / no items at all).
+
+    Returns a list with, per variant, the tuple (rate[, next[, hops]]) of arrays over its items (next with base_next,
+    hops with base_hops); with count_updates (that list, the per-variant U as a uint64 array)."""
+    _check_arrays(base_rate, base_next, base_hops)
+    if patches is None and items is None:
+        raise ValueError("patches or items must say how many variants there are")
+    count = len(patches) if patches is not None else len(items)
+    n = base_rate.shape[0]
+    pptr, prow = _sweep_csr(patches, count, "patches")
+    iptr, irow = _sweep_csr(items, count, "items")
+    widths = {len(v) for v in prow if v}
+    if len(widths) > 1 or (widths and not 2 <= min(widths) <= 4):
+        raise ValueError("every patch list is (index, rate[, next[, hops]]), the same fields in all variants")
+    if any(len(v) != 2 for v in irow if v):
+        raise ValueError("every item list is (src, dst)")
+    width = widths.pop() if widths else 2
+
+    def cat(rows, k, dtype):
+        parts = [v[k] for v in rows if v]
+        return np.ascontiguousarray(np.concatenate(parts), dtype=dtype) if parts else np.zeros(0, dtype=dtype)
+
+    p = _lib.FwxSweepPatches()
+    p_arrays = [pptr, cat(prow, 0, np.int64), cat(prow, 1, base_rate.dtype),
+                cat(prow, 2, np.int32) if width >= 3 else None, cat(prow, 3, np.int32) if width >= 4 else None]
+    p.ptr, p.total = pptr.ctypes.data, int(pptr[-1])
+    p.index, p.rate = p_arrays[1].ctypes.data, p_arrays[2].ctypes.data
+    p.next = p_arrays[3].ctypes.data if p_arrays[3] is not None else None
+    p.hops = p_arrays[4].ctypes.data if p_arrays[4] is not None else None
+    it = _lib.FwxSweepItems()
+    total = int(iptr[-1])
+    src, dst = cat(irow, 0, np.int32), cat(irow, 1, np.int32)
+    out = [np.zeros(total, dtype=base_rate.dtype),
+           np.zeros(total, dtype=np.int32) if base_next is not None else None,
+           np.zeros(total, dtype=np.int32) if base_hops is not None else None]
+    it.ptr, it.total, it.src, it.dst, it.rate_out = iptr.ctypes.data, total, src.ctypes.data, dst.ctypes.data, \
+        out[0].ctypes.data
+    it.next_out = out[1].ctypes.data if out[1] is not None else None
+    it.hops_out = out[2].ctypes.data if out[2] is not None else None
+    o, _ = _opts(device, FWX_ENGINE_AUTO)
+    each = np.zeros(count, dtype=np.uint64) if count_updates else None
+    fn = lib().fwx_solve_sweep_f64 if base_rate.dtype == np.float64 else lib().fwx_solve_sweep_f32
+    check(fn(count, n, _np_ptr(base_rate), _np_ptr(base_next), _np_ptr(base_hops), ctypes.byref(p), ctypes.byref(it),
+             _np_ptr(each), ctypes.byref(o)), "fwx_solve_sweep")
+    res = [tuple(a[iptr[b]:iptr[b + 1]] for a in out if a is not None) for b in range(count)]
+    return (res, each) if count_updates else res
+
+
+def dev_solve_sweep(base_rate_t, count, n, *, base_next_t=None, base_hops_t=None, patches=None, items=None, full=None,
+                    updates_t=None, stream=None):
+    """fwx_dev_solve_sweep on device arrays (torch tensors or hip.DeviceArray), asynchronously on `stream` (default: as
+    dev_relax): `count` variants of the base (n x n, n <= FWX_SWEEP_MAX_N, never written).
+
+    patches: None or (ptr, index, rate[, next[, hops]]) -- ptr int64[count + 1], index int64, rate as the base, next /
+    hops int32 or None; the total is index's length.  items: None or (ptr, src, dst, rate_out[, next_out[,
+    hops_out]]) -- src / dst int32, the total is src's length; the outputs are written in place.  full: None or
+    (rate, next, hops, stride) with any of the three None; variant b's solved n x n part goes to + b * stride.
+    updates_t: device array of `count` 64-bit counters, counter b is incremented by U of variant b."""
+    def ptr_of(t):
+        return None if t is None else t.data_ptr()
+
+    def ints(t, name, least):
+        assert t is None or (t.is_cuda and t.is_contiguous() and _dtype_name(t) == name and t.numel() >= least), name
+        return t
+
+    assert base_rate_t.is_cuda and base_rate_t.is_contiguous() and base_rate_t.numel() >= n * n
+    rate_name = _dtype_name(base_rate_t)
+    ints(base_next_t, "int32", n * n), ints(base_hops_t, "int32", n * n)
+    p = it = fu = None
+    if patches is not None:
+        t = tuple(patches) + (None,) * (5 - len(patches))
+        total = int(t[1].numel())
+        ints(t[0], "int64", count + 1), ints(t[1], "int64", total), ints(t[2], rate_name, total)
+        ints(t[3], "int32", total), ints(t[4], "int32", total)
+        p = _lib.FwxSweepPatches()
+        p.ptr, p.total, p.index, p.rate, p.next, p.hops = ptr_of(t[0]), total, ptr_of(t[1]), ptr_of(t[2]), \
+            ptr_of(t[3]), ptr_of(t[4])
+    if items is not None:
+        t = tuple(items) + (None,) * (6 - len(items))
+        total = int(t[1].numel())
+        ints(t[0], "int64", count + 1), ints(t[1], "int32", total), ints(t[2], "int32", total)
+        ints(t[3], rate_name, total), ints(t[4], "int32", total), ints(t[5], "int32", total)
+        it = _lib.FwxSweepItems()
+        it.ptr, it.total, it.src, it.dst, it.rate_out, it.next_out, it.hops_out = ptr_of(t[0]), total, ptr_of(t[1]), \
+            ptr_of(t[2]), ptr_of(t[3]), ptr_of(t[4]), ptr_of(t[5])
+    if full is not None:
+        stride = int(full[3])
+        need = (count - 1) * stride + n * n if count > 0 else 0
+        ints(full[0], rate_name, need), ints(full[1], "int32", need), ints(full[2], "int32", need)
+        fu = _lib.FwxSweepFull()
+        fu.rate, fu.next, fu.hops, fu.stride = ptr_of(full[0]), ptr_of(full[1]), ptr_of(full[2]), stride
+    assert updates_t is None or (updates_t.element_size() == 8 and updates_t.numel() >= count)
+    vp = ctypes.c_void_p
+    check(lib().fwx_dev_solve_sweep(
+        count, n, _tensor_dtype_code(base_rate_t), vp(base_rate_t.data_ptr()), ptr_of(base_next_t), ptr_of(base_hops_t),
+        ctypes.byref(p) if p is not None else None, ctypes.byref(it) if it is not None else None,
+        ctypes.byref(fu) if fu is not None else None, vp(updates_t.data_ptr()) if updates_t is not None else None,
+        _stream_ptr(stream, base_rate_t)), "fwx_dev_solve_sweep")
+
+
 # solve_batch_lists with cap=None: the first capacity tried, and the last (the lists of an input with arbitrage
 # grow with every pivot; past this bound the caller states the cap).
 BATCH_LISTS_FIRST_CAP = 64

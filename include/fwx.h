@@ -706,6 +706,83 @@ int fwx_solve_ragged_large_lists_f32(int32_t count, const int32_t *n_each, float
 int fwx_test_ragged_large_schedule(int32_t count, int32_t large_count, const int64_t *work, size_t scratch_bytes,
                                    int32_t *group_first, int32_t cap, int64_t totals[3]);
 
+/* ---- batched what-if sweeps: variants of ONE base matrix of order n <= FWX_SWEEP_MAX_N solved in one call ----
+ * A what-if sweep is `count` variants of one matrix that differ from it in a handful of entries -- a candidate quote
+ * changes two entries of buildMatrix's output -- and the host wants a few entries of each solved variant, say the best
+ * rate A -> B under each quote.  fwx_solve_batch_* serves it only from `count` materialised copies, count * n * n
+ * entries per field each way; here the base goes up once, the device builds variant b in the registers of the batch
+ * tiers, and only the queried entries come back.  No count * n * n array exists unless the caller asks for one.
+ *
+ * Variant b is M_b = the base with the patches [patches->ptr[b], patches->ptr[b+1]) applied in list order: patch q
+ * puts rate[q] at cell index[q] = i*n + j, and next[q] / hops[q] there if those arrays are given (NULL: that field
+ * of the cell keeps the base's value, as fwx_matrix_patch_input); a later patch of the same cell wins; the diagonal
+ * may be patched.  Item q of [items->ptr[b], items->ptr[b+1]) receives entry (src[q], dst[q]) of the SOLVED M_b:
+ * rate_out[q], and next_out[q] (the first hop) / hops_out[q] (the length) if given.  Every output is bit for bit what
+ * fwx_solve_batch_* returns for M_b, and so what the reference loop returns for it: rate, next, hops (diagonals
+ * included) and U; the full list rule applies, there is no domain check and no routing by content.  Whole pivot range
+ * only, no path trace.  Tier choice by FWX_BATCH_WAVE_MAX_N as above; no result bit depends on it.  Inputs and
+ * outputs must not overlap.
+ *
+ * Device form: every pointer, those inside the structs included, is DEVICE memory; asynchronous on `stream`, nothing
+ * allocated or synchronised; the base is never written.  patches NULL: every variant is the base.  items NULL: no
+ * items.  full NULL, or any of its three pointers NULL: that output is not wanted; otherwise the whole n x n part of
+ * the solved M_b goes to full->rate + b*stride (next, hops alike), diagonal included, the gap never written.
+ * d_updates_each: optional, count uint64, INCREMENTED by each variant's U.  The device form cannot read the tables:
+ * each [ptr[b], ptr[b+1]) is clamped into [0, total] (a descending pair is empty), a patch whose index is outside
+ * [0, n*n) is ignored and an item whose src or dst is outside [0, n) leaves its outputs untouched -- whatever the
+ * tables hold, nothing outside the arrays' stated extents is read or written.
+ *
+ * Host form: HOST arrays throughout.  The base, the patch arrays and the item arrays go up once, the item outputs
+ * and updates_each (optional, count entries) come down; there are no full outputs -- a host that wants every solved
+ * matrix calls fwx_solve_batch_*.  Device memory comes from the pooled per-call context.  opts: device, stream /
+ * use_stream and updates_out (the SUM of U) are honoured; a pivot range other than the whole one is FWX_ERR_INVALID,
+ * an engine other than FWX_ENGINE_AUTO FWX_ERR_UNSUPPORTED.
+ *
+ * Statuses, all decided before any device call.  FWX_ERR_INVALID: count < 0 or n < 0; a bad dtype; base_rate NULL;
+ * base_hops without base_next; patches->next, items->next_out or full->next without base_next; patches->hops,
+ * items->hops_out or full->hops without base_hops; a negative total; a NULL ptr, index, rate, src, dst or rate_out
+ * with total > 0; full->stride < n*n with a non-NULL full pointer; a bad struct_size.  Host form only, which can read
+ * the tables: ptr[0] != 0, a descending ptr, ptr[count] != total, a patch index outside [0, n*n), an item src or dst
+ * outside [0, n).  FWX_ERR_UNSUPPORTED: n > FWX_SWEEP_MAX_N.  count == 0 or n == 0: FWX_OK, nothing is touched.  Then
+ * FWX_ERR_NO_DEVICE without a device, every output untouched.
+ *
+ * When it pays (MI355X, f64 + next + hops, two patches and four items a variant; profiles/r34_sweep.txt).  Host form
+ * against numpy building the copies, fwx_solve_batch_f64 and indexing the answers: 15.2x at n = 128, count = 4096 (6.3
+ * against 96.0 ms; 0.9 MB moved instead of 2 x 1.07 GB), 17.6x at n = 64, count = 4096, 11.7x / 7.6x at count = 256,
+ * 10.6x at n = 16, count = 4096; at n = 4 and at n = 16, count = 256 1.2 ... 2.3x -- use whichever is at hand.  Device
+ * form against fwx_dev_solve_batch on variants already materialised on the device: equal at n = 128 and at n = 64,
+ * count = 256, 1.39x SLOWER at n = 64, count = 4096 and 1.7 ... 2x slower at n = 4 (3 us): a caller whose variants
+ * already lie on the device gains nothing from it; it pays where the copies would have to be built or moved.       */
+#define FWX_SWEEP_MAX_N FWX_BATCH_MAX_N
+typedef struct fwx_sweep_patches {   /* variant b: entries [ptr[b], ptr[b+1]) */
+    const int64_t *ptr;              /* count + 1, ptr[0] = 0, non-decreasing */
+    int64_t total;                   /* = ptr[count]; entries in the arrays below */
+    const int64_t *index;            /* i*n + j */
+    const void *rate;                /* dtype */
+    const int32_t *next, *hops;      /* optional: NULL = that field keeps the base's value */
+} fwx_sweep_patches;
+typedef struct fwx_sweep_items {     /* variant b: items [ptr[b], ptr[b+1]) */
+    const int64_t *ptr;              /* count + 1, ptr[0] = 0, non-decreasing */
+    int64_t total;                   /* = ptr[count] */
+    const int32_t *src, *dst;
+    void *rate_out;                  /* dtype, total entries */
+    int32_t *next_out, *hops_out;    /* optional */
+} fwx_sweep_items;
+typedef struct fwx_sweep_full {      /* the solved variants whole, variant b at + b*stride */
+    void *rate;                      /* dtype; optional like the two below */
+    int32_t *next, *hops;
+    int64_t stride;                  /* elements, >= n*n */
+} fwx_sweep_full;
+int fwx_dev_solve_sweep(int32_t count, int32_t n, int32_t dtype, const void *base_rate, const int32_t *base_next,
+                        const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                        const fwx_sweep_full *full, unsigned long long *d_updates_each, void *stream);
+int fwx_solve_sweep_f64(int32_t count, int32_t n, const double *base_rate, const int32_t *base_next,
+                        const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                        uint64_t *updates_each, const fwx_opts *opts);
+int fwx_solve_sweep_f32(int32_t count, int32_t n, const float *base_rate, const int32_t *base_next,
+                        const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                        uint64_t *updates_each, const fwx_opts *opts);
+
 /* Index form of the `_path` list that optimum returns (Algorithms.hs:74-75): follow next-hops
  * from src until dst.  Returns the number of vertices written to out (dst included, src not), 0 if
  * next[src][dst] == -1 (empty path, "no exchange"), or a negative fwx_status.  Host arrays.      */
