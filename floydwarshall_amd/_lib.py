@@ -33,11 +33,17 @@ FWX_BATCH_MAX_N = 128
 FWX_BATCH_MID_MAX_N = 256
 FWX_BATCH_LARGE_MAX_N = 1024
 FWX_SWEEP_MAX_N = FWX_BATCH_MAX_N
+FWX_SWEEP_MID_MAX_N = FWX_BATCH_MID_MAX_N
 
 
 def batch_large_scratch_bytes(n):
     """FWX_BATCH_LARGE_SCRATCH_BYTES(n) of include/fwx.h: device scratch one matrix of order n needs."""
     return int(n) * 512
+
+
+def sweep_mid_scratch_bytes(n):
+    """FWX_SWEEP_MID_SCRATCH_BYTES(n) of include/fwx.h: one workspace slot of a mid-tier sweep of order n."""
+    return int(n) * int(n) * 16
 
 
 FWX_FLAG_NONNEG = 1
@@ -225,9 +231,13 @@ for _mid, _work, _extra in (("", [], []), ("_mid", [], []), ("_large", [c_vp], _
 _SWEEP = [ctypes.POINTER(FwxSweepPatches), ctypes.POINTER(FwxSweepItems)]
 SIGNATURES["fwx_dev_solve_sweep"] = (
     ctypes.c_int, _UNIFORM + [c_i32] + _ARRAYS + _SWEEP + [ctypes.POINTER(FwxSweepFull), c_vp, c_vp])
+SIGNATURES["fwx_dev_solve_sweep_mid"] = (
+    ctypes.c_int, _UNIFORM + [c_i32] + _ARRAYS + _SWEEP + [ctypes.POINTER(FwxSweepFull), c_vp] + _SCRATCH + [c_vp])
 for _t in ("f64", "f32"):
     SIGNATURES["fwx_solve_sweep_" + _t] = (ctypes.c_int, _UNIFORM + _ARRAYS + _SWEEP + [c_vp, _OPTS])
+    SIGNATURES["fwx_solve_sweep_mid_" + _t] = (ctypes.c_int, _UNIFORM + _ARRAYS + _SWEEP + [c_vp, _OPTS])
 SIGNATURES.update({
+    "fwx_test_sweep_mid_slots": (ctypes.c_int, [c_i32, c_i32, ctypes.c_size_t]),
     "fwx_test_batch_wave_max_n": (ctypes.c_int, []),
     "fwx_test_batch_mid_min_n": (ctypes.c_int, []),
     "fwx_test_batch_mid_block": (ctypes.c_int, []),

@@ -10,6 +10,8 @@
 //   dev_exact_paths_batch  fwx_dev_exact_paths_batch{,_mid,_large}
 //   dev_exact_paths_ragged fwx_dev_exact_paths_ragged{,_mid,_large}
 //   solve_batch_host       every host form
+//   dev_solve_sweep        fwx_dev_solve_sweep{,_mid}
+//   solve_sweep_host       fwx_solve_sweep{,_mid}_*
 // and the tier of an order is decided in one place, BatchFamily::tier, which run_uniform acts on.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -33,6 +35,8 @@ static_assert(FWX_RAGGED_LARGE_WORK_ENTRIES(7) == 3 * 8, "three rows of count + 
 static_assert(FWX_BATCH_LARGE_SCRATCH_BYTES(1000) == FWX_LARGE_SCRATCH_BYTES(1000) &&
                   FWX_BATCH_LARGE_SCRATCH_BYTES(1) == FWX_LARGE_SCRATCH_BYTES(1),
               "fwx.h states the scratch the large tier lays out");
+static_assert(FWX_SWEEP_MID_SCRATCH_BYTES(255) == FWX_MID_SWEEP_SLOT_BYTES(255) && FWX_SWEEP_MID_MAX_N == FWX_MID_N,
+              "fwx.h states the slot the mid tier's sweep lays out");
 
 namespace {
 
@@ -636,10 +640,39 @@ int solve_batch_host(const HostForm &form, int32_t count, int32_t n, T *rate, in
 
 // ---- what-if sweeps ---------------------------------------------------------------------------------------------------
 
-// What both sweep forms decide from their host arguments, in fwx.h's order (the dtype is the caller's); FWX_OK with
-// done set: nothing to do.
-int sweep_args(int32_t count, int32_t n, const void *base_rate, const int32_t *base_next, const int32_t *base_hops,
-               const fwx_sweep_patches *p, const fwx_sweep_items *it, const fwx_sweep_full *fu, bool &done)
+// Workgroups (= workspace slots) of a mid-tier sweep: FWX_SWEEP_MID_SLOTS, environment, read once per call: digits
+// only, >= 1, anything else means the default -- two 1024-thread workgroups on each of the 256 CUs, the most that can
+// be resident.  No result bit depends on it.
+#define FWX_SWEEP_MID_SLOTS_DEFAULT 512
+int sweep_mid_slots(int32_t count, int32_t n, size_t scratch_bytes)
+{
+    if (count <= 0 || n <= 0) return 0;
+    const long long cap = env_digits("FWX_SWEEP_MID_SLOTS", 1, INT32_MAX, FWX_SWEEP_MID_SLOTS_DEFAULT);
+    const size_t fit = scratch_bytes / FWX_SWEEP_MID_SCRATCH_BYTES((size_t)n);
+    return (int)std::min<unsigned long long>({(unsigned long long)count, (unsigned long long)fit, (unsigned long long)cap});
+}
+
+// Where a sweep of order n runs and what it needs there.  `limit` is the family's largest order; a family with the
+// mid tier (limit FWX_SWEEP_MID_MAX_N) routes by FWX_BATCH_MID_MIN_N as fwx_solve_batch_mid_*, read once here.
+struct SweepRoute {
+    bool mid;
+    SweepRoute(int32_t limit, int32_t n) : mid(limit > FWX_SWEEP_MAX_N && n >= batch_mid_min_n()) {}
+    // the launcher of the tier: scratch and slots are the mid tier's and unused otherwise
+    template <typename T>
+    hipError_t launch(const T *rate, const int32_t *next, const int32_t *hops, int32_t count, int32_t n,
+                      const fwx::SweepTables<T> &t, unsigned long long *d_updates_each, void *scratch, int slots,
+                      hipStream_t s) const
+    {
+        return mid ? fwx::launch_sweep_mid<T>(rate, next, hops, count, n, t, d_updates_each, scratch, slots, s)
+                   : fwx::launch_sweep_solve<T>(rate, next, hops, count, n, t, d_updates_each, batch_wave_max_n(), s);
+    }
+};
+
+// What both sweep forms decide from their host arguments, in fwx.h's order (the dtype is the caller's; limit: the
+// family's largest order); FWX_OK with done set: nothing to do.
+int sweep_args(int32_t limit, int32_t count, int32_t n, const void *base_rate, const int32_t *base_next,
+               const int32_t *base_hops, const fwx_sweep_patches *p, const fwx_sweep_items *it, const fwx_sweep_full *fu,
+               bool &done)
 {
     done = true;
     if (count < 0 || n < 0) return FWX_ERR_INVALID;
@@ -657,7 +690,7 @@ int sweep_args(int32_t count, int32_t n, const void *base_rate, const int32_t *b
         if ((fu->next && !base_next) || (fu->hops && !base_hops)) return FWX_ERR_INVALID;
         if ((fu->rate || fu->next || fu->hops) && fu->stride < (int64_t)n * n) return FWX_ERR_INVALID;
     }
-    if (n > FWX_SWEEP_MAX_N) return FWX_ERR_UNSUPPORTED;
+    if (n > limit) return FWX_ERR_UNSUPPORTED;
     done = false;
     return FWX_OK;
 }
@@ -704,14 +737,19 @@ bool sweep_ptr_ok(const int64_t *ptr, int32_t count, int64_t total)
 
 // fwx_solve_sweep_*: the base, the patch arrays and the item arrays go up once into ONE reservation of the pooled
 // context, the item outputs and the counters come down.  Nothing of the caller's is written before the reservation.
+// limit: the family's largest order (fwx_solve_sweep_*: FWX_SWEEP_MAX_N, fwx_solve_sweep_mid_*: FWX_SWEEP_MID_MAX_N);
+// a call routed to the mid tier takes its slots from the context's SMALL buffer, as many as fit under
+// kBatchLargeScratchCap (one at least), capped by sweep_mid_slots' rule.
 template <typename T>
-int solve_sweep_host(int32_t count, int32_t n, const T *base_rate, const int32_t *base_next, const int32_t *base_hops,
-                     const fwx_sweep_patches *p, const fwx_sweep_items *it, uint64_t *updates_each, const fwx_opts *o)
+int solve_sweep_host(int32_t limit, int32_t count, int32_t n, const T *base_rate, const int32_t *base_next,
+                     const int32_t *base_hops, const fwx_sweep_patches *p, const fwx_sweep_items *it,
+                     uint64_t *updates_each, const fwx_opts *o)
 {
     return guarded([&]() -> int {
         bool done = false;
-        int rc = sweep_args(count, n, base_rate, base_next, base_hops, p, it, nullptr, done);
+        int rc = sweep_args(limit, count, n, base_rate, base_next, base_hops, p, it, nullptr, done);
         if (rc || done) return rc;
+        const SweepRoute route(limit, n);
         Opts op{};
         if ((rc = read_opts(o, n, op))) return rc;
         if (op.k_begin != 0 || op.k_end != n) return FWX_ERR_INVALID;
@@ -765,6 +803,14 @@ int solve_sweep_host(int32_t count, int32_t n, const T *base_rate, const int32_t
         void *buf = nullptr;
         fail_point();
         if ((rc = cx.reserve(CallCtx::RATE, total, &buf))) return rc;
+        void *d_scratch = nullptr;             // mid tier: the slots, a reservation (and a point) of their own
+        int slots = 0;
+        if (route.mid) {
+            const size_t per_slot = FWX_SWEEP_MID_SCRATCH_BYTES((size_t)n);
+            slots = sweep_mid_slots(count, n, std::max(per_slot, kBatchLargeScratchCap));
+            fail_point();
+            if ((rc = cx.reserve(CallCtx::SMALL, (size_t)slots * per_slot, &d_scratch))) return rc;
+        }
         char *at = (char *)buf;
         for (Piece &a : pc) {
             if (!a.bytes) continue;
@@ -793,9 +839,9 @@ int solve_sweep_host(int32_t count, int32_t n, const T *base_rate, const int32_t
             t.item_next = (int32_t *)pc[ON].dev;
             t.item_hops = (int32_t *)pc[OH].dev;
         }
-        if ((rc = launch_status(fwx::launch_sweep_solve<T>((const T *)pc[BR].dev, (const int32_t *)pc[BN].dev,
-                                                           (const int32_t *)pc[BH].dev, count, n, t,
-                                                           (unsigned long long *)pc[UP].dev, batch_wave_max_n(), s))))
+        if ((rc = launch_status(route.launch<T>((const T *)pc[BR].dev, (const int32_t *)pc[BN].dev,
+                                                (const int32_t *)pc[BH].dev, count, n, t,
+                                                (unsigned long long *)pc[UP].dev, d_scratch, slots, s))))
             return rc;
         std::vector<unsigned long long> h_upd(counting ? (size_t)count : 0);
         if (ni > 0) {
@@ -815,6 +861,35 @@ int solve_sweep_host(int32_t count, int32_t n, const T *base_rate, const int32_t
     });
 }
 
+// fwx_dev_solve_sweep (limit FWX_SWEEP_MAX_N; scratch unused) and fwx_dev_solve_sweep_mid: one contract, the limit
+// apart.  The order of the checks is fwx.h's: the dtype and the arguments (FWX_ERR_INVALID), the order against the limit
+// (FWX_ERR_UNSUPPORTED), the scratch where the call is routed to the mid tier (FWX_ERR_INVALID), the device.
+int dev_solve_sweep(int32_t limit, int32_t count, int32_t n, int32_t dtype, const void *base_rate,
+                    const int32_t *base_next, const int32_t *base_hops, const fwx_sweep_patches *patches,
+                    const fwx_sweep_items *items, const fwx_sweep_full *full, unsigned long long *d_updates_each,
+                    void *scratch, size_t scratch_bytes, void *stream)
+{
+    return guarded([&]() -> int {
+        if (dtype != FWX_F32 && dtype != FWX_F64) return FWX_ERR_INVALID;
+        bool done = false;
+        const int rc = sweep_args(limit, count, n, base_rate, base_next, base_hops, patches, items, full, done);
+        if (rc || done) return rc;
+        const SweepRoute route(limit, n);
+        int slots = 0;
+        if (route.mid) {
+            if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < FWX_SWEEP_MID_SCRATCH_BYTES((size_t)n))
+                return FWX_ERR_INVALID;
+            slots = sweep_mid_slots(count, n, scratch_bytes);
+        }
+        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
+        return with_dtype(dtype, (void *)base_rate, [&](auto *r) {
+            using T = std::remove_pointer_t<decltype(r)>;
+            return launch_status(route.launch<T>(r, base_next, base_hops, count, n, sweep_tables<T>(patches, items, full),
+                                                 d_updates_each, scratch, slots, (hipStream_t)stream));
+        });
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -825,33 +900,49 @@ int fwx_dev_solve_sweep(int32_t count, int32_t n, int32_t dtype, const void *bas
                         const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
                         const fwx_sweep_full *full, unsigned long long *d_updates_each, void *stream)
 {
-    return guarded([&]() -> int {
-        if (dtype != FWX_F32 && dtype != FWX_F64) return FWX_ERR_INVALID;
-        bool done = false;
-        const int rc = sweep_args(count, n, base_rate, base_next, base_hops, patches, items, full, done);
-        if (rc || done) return rc;
-        if (device_count() <= 0) return FWX_ERR_NO_DEVICE;
-        return with_dtype(dtype, (void *)base_rate, [&](auto *r) {
-            using T = std::remove_pointer_t<decltype(r)>;
-            return launch_status(fwx::launch_sweep_solve<T>(r, base_next, base_hops, count, n,
-                                                            sweep_tables<T>(patches, items, full), d_updates_each,
-                                                            batch_wave_max_n(), (hipStream_t)stream));
-        });
-    });
+    return dev_solve_sweep(FWX_SWEEP_MAX_N, count, n, dtype, base_rate, base_next, base_hops, patches, items, full,
+                           d_updates_each, nullptr, 0, stream);
 }
 
 int fwx_solve_sweep_f64(int32_t count, int32_t n, const double *base_rate, const int32_t *base_next,
                         const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
                         uint64_t *updates_each, const fwx_opts *opts)
 {
-    return solve_sweep_host<double>(count, n, base_rate, base_next, base_hops, patches, items, updates_each, opts);
+    return solve_sweep_host<double>(FWX_SWEEP_MAX_N, count, n, base_rate, base_next, base_hops, patches, items,
+                                    updates_each, opts);
 }
 
 int fwx_solve_sweep_f32(int32_t count, int32_t n, const float *base_rate, const int32_t *base_next,
                         const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
                         uint64_t *updates_each, const fwx_opts *opts)
 {
-    return solve_sweep_host<float>(count, n, base_rate, base_next, base_hops, patches, items, updates_each, opts);
+    return solve_sweep_host<float>(FWX_SWEEP_MAX_N, count, n, base_rate, base_next, base_hops, patches, items,
+                                   updates_each, opts);
+}
+
+int fwx_dev_solve_sweep_mid(int32_t count, int32_t n, int32_t dtype, const void *base_rate, const int32_t *base_next,
+                            const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                            const fwx_sweep_full *full, unsigned long long *d_updates_each, void *scratch,
+                            size_t scratch_bytes, void *stream)
+{
+    return dev_solve_sweep(FWX_SWEEP_MID_MAX_N, count, n, dtype, base_rate, base_next, base_hops, patches, items, full,
+                           d_updates_each, scratch, scratch_bytes, stream);
+}
+
+int fwx_solve_sweep_mid_f64(int32_t count, int32_t n, const double *base_rate, const int32_t *base_next,
+                            const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                            uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_sweep_host<double>(FWX_SWEEP_MID_MAX_N, count, n, base_rate, base_next, base_hops, patches, items,
+                                    updates_each, opts);
+}
+
+int fwx_solve_sweep_mid_f32(int32_t count, int32_t n, const float *base_rate, const int32_t *base_next,
+                            const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                            uint64_t *updates_each, const fwx_opts *opts)
+{
+    return solve_sweep_host<float>(FWX_SWEEP_MID_MAX_N, count, n, base_rate, base_next, base_hops, patches, items,
+                                   updates_each, opts);
 }
 
 // ---- uniform batches: host forms ----------------------------------------------------------------------------------
@@ -1244,6 +1335,13 @@ int fwx_test_batch_large_geometry(int32_t out[4])
     out[2] = FWX_LARGE_TR;
     out[3] = FWX_LARGE_TC;
     return FWX_OK;
+}
+
+int fwx_test_sweep_mid_slots(int32_t count, int32_t n, size_t scratch_bytes)
+{
+    if (count < 0 || n < 0) return FWX_ERR_INVALID;
+    if (n > FWX_SWEEP_MID_MAX_N) return FWX_ERR_UNSUPPORTED;
+    return sweep_mid_slots(count, n, scratch_bytes);
 }
 
 int64_t fwx_test_batch_lists_chunk(int32_t n, int32_t cap)

@@ -281,7 +281,10 @@ constexpr size_t kMultiPoolMaxIdle = 2;        // MultiPool (fwx_multi.hip) park
 // ------------------------------------------------------------------------------------------------
 struct CallCtx {
     enum { RATE, NEXT, HOPS, WS, SMALL, NBUF };            // SMALL: update shards + domain flag; in
-                                                           // fwx_solve_batch_lists_*: next0, the trace, the walk's chunk
+                                                           // fwx_solve_batch_lists_*: next0, the trace, the walk's chunk;
+                                                           // fwx_solve_batch_large_* / ragged_large: the scratch panels in
+                                                           // front (up to 256 MiB); fwx_solve_sweep_mid_*: the workspace
+                                                           // slots of the mid tier's sweep (up to 256 MiB)
     static constexpr size_t kKeepBytes = (size_t)256 << 20;
     int device = -1;
     hipStream_t s = nullptr;

@@ -211,6 +211,19 @@ template <typename T>
 hipError_t launch_batch_mid(T *rate, int32_t *next, int32_t *hops, int count, int n, long long stride, int k_begin,
                             int k_end, unsigned long long *updates_each, hipStream_t s, PathLog plog = PathLog());
 
+// What-if sweeps on the mid tier (fwx_mid.hip): launch_sweep_solve's contract for n <= FWX_MID_N, the variants built
+// and solved in workspace slots.  ONE launch of `slots` workgroups; workgroup s owns slot s of `scratch` (device
+// memory, 16-byte aligned, FWX_MID_SWEEP_SLOT_BYTES(n) per slot -- an upper bound over dtype and field set: the rates,
+// then next, then hops, each n*n elements at pitch n) and handles the variants s, s + slots, ...: base -> slot, the
+// patches in list order, the mid tier's body on the slot, the items and the full outputs from the slot.  Nothing past
+// slots x FWX_MID_SWEEP_SLOT_BYTES(n) bytes of the scratch is touched and no result bit depends on `slots`.
+// hipErrorInvalidValue for what launch_sweep_solve refuses, for slots < 1 and for scratch that is null or misaligned.
+#define FWX_MID_SWEEP_SLOT_BYTES(n) ((size_t)(n) * (n) * 16)
+template <typename T>
+hipError_t launch_sweep_mid(const T *base_rate, const int32_t *base_next, const int32_t *base_hops, int count, int n,
+                            const SweepTables<T> &t, unsigned long long *updates_each, void *scratch, int slots,
+                            hipStream_t s);
+
 // Large tier of the batched solves (fwx_large.hip): `count` matrices of one order n <= FWX_LARGE_N, same layout and
 // counters as launch_batch_mid, several workgroups per matrix: per block of FWX_LARGE_B pivots one panel launch
 // (column strips of FWX_LARGE_S, matrices) that writes the time-k snapshot panels to `scratch`, and one sweep launch

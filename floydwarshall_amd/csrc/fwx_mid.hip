@@ -45,6 +45,17 @@
 // read (a broadcast) and the global loads / stores of a wave are one row segment.  Scalar element accesses only:
 // any pitch n, no alignment beyond the element.  The gap between matrices is never read or written, the
 // diagonal's rate neither.
+//
+// What-if sweeps (mid_solve_sweep): a third kernel on the same body.  A fixed grid of `slots` workgroups; workgroup s
+// owns slot s of a scratch buffer -- n*n rates, then n*n next, then n*n hops, pitch n -- and walks the variants
+// b = s, s + slots, ... < count.  Per variant: expand (base -> slot, every cell, the diagonal's rate too), patches (in
+// list order), solve (the body above on the slot, whole pivot range), answer (items and full outputs read from the
+// slot), with a workgroup barrier between the stages and one before the next variant's expand.  A slot is read and
+// written by its own workgroup only, so here too there is no communication between workgroups, no grid barrier and no
+// spin-wait: every stage hands over to the next through __syncthreads(), the ordering the body already relies on
+// between its sweep's stores and its next panel loads (one workgroup, one CU, one L1).  The trip count of the variant
+// loop is a function of (blockIdx.x, gridDim.x, count) alone -- workgroup-uniform -- and the kernel has no exit after
+// its first barrier.  It declares no LDS of its own.
 #include "fwx_kernels.h"
 
 #include <algorithm>
@@ -237,6 +248,104 @@ __global__ __launch_bounds__(kMidThreads) void mid_solve_ragged(T *rate, int32_t
                                                     updates, (unsigned int)id);
 }
 
+// [ptr[b], ptr[b + 1]) clamped into [0, total], as SweepIO::range (fwx_kernels.hip): a descending pair and a null
+// table are empty ranges.  b is workgroup-uniform.
+__device__ __forceinline__ void sweep_mid_range(const int64_t *ptr, long long b, long long total, long long &lo,
+                                                long long &hi)
+{
+    lo = hi = 0;
+    if (!ptr || total <= 0) return;
+    long long a = ptr[b], e = ptr[b + 1];
+    a = a < 0 ? 0 : a;
+    e = e > total ? total : e;
+    lo = a;
+    hi = e < a ? a : e;
+}
+
+// What-if sweep, mid tier: workgroup s of `gridDim.x` slots on the variants s, s + gridDim.x, ... of one base (pitch
+// n, const).  Its slot: rate at scratch + s * FWX_MID_SWEEP_SLOT_BYTES(n), next behind the n*n rates, hops behind
+// next.  The stages of one variant, a barrier after each:
+//   1. expand   e = tid, tid + 1024, ...: the slot's cell e = the base's, every field present.  The diagonal's rate is
+//               copied like any cell: the body neither reads nor writes it, so the slot keeps the base's -- or the
+//               patched -- value, which is what an item on (i, i) and a full output receive.
+//   2. patches  ONE lane (thread 0) walks [p0, p1) in program order, so a later patch of a cell wins by construction;
+//               an index outside [0, n*n) is passed over, a null patch_next / patch_hops leaves the expanded value.
+//               A sweep has a handful of patches a variant: spreading them over lanes would need a rule for two
+//               patches of one cell (the cost of the serial walk was not measured on its own).
+//   3. solve    the body on the slot.
+//   4. answer   thread t takes the items q0 + t, q0 + t + 1024, ...; an item with src or dst outside [0, n) leaves its
+//               outputs alone.  The full outputs given receive the slot's n*n cells, diagonal included, at
+//               + b * stride; the gap is never written.
+// Nothing of the base is written; nothing outside the tables' stated extents is read.
+template <typename T, bool HAS_NEXT, bool HAS_HOPS>
+__global__ __launch_bounds__(kMidThreads) void mid_solve_sweep(const T *base_rate, const int32_t *base_next,
+                                                               const int32_t *base_hops, int n, int count,
+                                                               SweepTables<T> t, unsigned long long *updates,
+                                                               char *scratch)
+{
+    const int tid = threadIdx.x;
+    const int cells = n * n;                                  // <= 65536
+    T *const rate = (T *)(scratch + (size_t)blockIdx.x * FWX_MID_SWEEP_SLOT_BYTES(n));
+    int32_t *const next = (int32_t *)(rate + cells), *const hops = next + cells;
+    for (long long b = blockIdx.x; b < count; b += gridDim.x) {
+        // ---- 1. expand ---------------------------------------------------------------------------------------
+        for (int e = tid; e < cells; e += kMidThreads) {
+            rate[e] = base_rate[e];
+            if constexpr (HAS_NEXT) next[e] = base_next[e];
+            if constexpr (HAS_HOPS) hops[e] = base_hops[e];
+        }
+        __syncthreads();
+        // ---- 2. patches --------------------------------------------------------------------------------------
+        if (tid == 0) {
+            long long p0, p1;
+            sweep_mid_range(t.patch_ptr, b, t.patch_total, p0, p1);
+#pragma unroll 1
+            for (long long q = p0; q < p1; ++q) {
+                const long long idx = t.patch_index[q];
+                if (idx < 0 || idx >= cells) continue;
+                rate[idx] = t.patch_rate[q];
+                if constexpr (HAS_NEXT) { if (t.patch_next) next[idx] = t.patch_next[q]; }
+                if constexpr (HAS_HOPS) { if (t.patch_hops) hops[idx] = t.patch_hops[q]; }
+            }
+        }
+        __syncthreads();
+        // ---- 3. solve ----------------------------------------------------------------------------------------
+        // Safe in a loop: the body's only state outside the slot is its LDS.  (a) s_cnt: thread 0 zeroes it on
+        // entry, and thread 0 is also the only reader of the previous call's total (its last statement, program
+        // order); this call's atomicAdds come after the pivot loop, which holds at least one barrier (n >= 1), so
+        // none can fall before the reset.  (b) the panels: the body's pivot loop ends on a barrier (its step 3), so
+        // every read of W / C / ... of this call is over when the call returns, and that barrier is also what makes
+        // the sweep's stores to the slot visible to stage 4 -- the same hand-over as from one pivot block to the next.
+        mid_solve_body<T, HAS_NEXT, HAS_HOPS, false>(rate, HAS_NEXT ? next : nullptr, HAS_HOPS ? hops : nullptr,
+                                                     nullptr, nullptr, nullptr, n, 0, n, updates, (unsigned int)b);
+        __syncthreads();
+        // ---- 4. answer ---------------------------------------------------------------------------------------
+        long long q0, q1;
+        sweep_mid_range(t.item_ptr, b, t.item_total, q0, q1);
+        for (long long q = q0 + tid; q < q1; q += kMidThreads) {
+            const int s = t.item_src[q], d = t.item_dst[q];
+            if ((unsigned)s >= (unsigned)n || (unsigned)d >= (unsigned)n) continue;
+            const int e = s * n + d;
+            t.item_rate[q] = rate[e];
+            if constexpr (HAS_NEXT) { if (t.item_next) t.item_next[q] = next[e]; }
+            if constexpr (HAS_HOPS) { if (t.item_hops) t.item_hops[q] = hops[e]; }
+        }
+        const size_t off = (size_t)b * (size_t)t.full_stride;
+        if (t.full_rate)
+            for (int e = tid; e < cells; e += kMidThreads) t.full_rate[off + e] = rate[e];
+        if constexpr (HAS_NEXT) {
+            if (t.full_next)
+                for (int e = tid; e < cells; e += kMidThreads) t.full_next[off + e] = next[e];
+        }
+        if constexpr (HAS_HOPS) {
+            if (t.full_hops)
+                for (int e = tid; e < cells; e += kMidThreads) t.full_hops[off + e] = hops[e];
+        }
+        // ---- 5. the slot is free for the next variant's expand -------------------------------------------------
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 template <typename T>
@@ -301,6 +410,37 @@ hipError_t launch_ragged_mid(T *rate, int32_t *next, int32_t *hops, int count, c
     }
     return hipSuccess;
 }
+
+template <typename T>
+hipError_t launch_sweep_mid(const T *base_rate, const int32_t *base_next, const int32_t *base_hops, int count, int n,
+                            const SweepTables<T> &t, unsigned long long *updates_each, void *scratch, int slots,
+                            hipStream_t s)
+{
+    if (count <= 0 || n <= 0) return hipSuccess;
+    if (n > FWX_MID_N || !base_rate || (base_hops && !base_next) || t.patch_total < 0 || t.item_total < 0 ||
+        (t.patch_total > 0 && (!t.patch_ptr || !t.patch_index || !t.patch_rate)) ||
+        (t.item_total > 0 && (!t.item_ptr || !t.item_src || !t.item_dst || !t.item_rate)) ||
+        ((t.patch_next || t.item_next || t.full_next) && !base_next) ||
+        ((t.patch_hops || t.item_hops || t.full_hops) && !base_hops) ||
+        ((t.full_rate || t.full_next || t.full_hops) && t.full_stride < (long long)n * n) || slots < 1 || !scratch ||
+        ((uintptr_t)scratch & 15))
+        return hipErrorInvalidValue;
+    const int grid = std::min(slots, count);
+#define FWX_SWEEP_MID(HN, HH)                                                                      \
+    hipLaunchKernelGGL((mid_solve_sweep<T, HN, HH>), dim3(grid), dim3(kMidThreads), 0, s, base_rate, base_next,    \
+                       base_hops, n, count, t, updates_each, (char *)scratch)
+    if (base_hops) FWX_SWEEP_MID(true, true);
+    else if (base_next) FWX_SWEEP_MID(true, false);
+    else FWX_SWEEP_MID(false, false);
+#undef FWX_SWEEP_MID
+    return hipGetLastError();
+}
+
+template hipError_t launch_sweep_mid<float>(const float *, const int32_t *, const int32_t *, int, int,
+                                            const SweepTables<float> &, unsigned long long *, void *, int, hipStream_t);
+template hipError_t launch_sweep_mid<double>(const double *, const int32_t *, const int32_t *, int, int,
+                                             const SweepTables<double> &, unsigned long long *, void *, int,
+                                             hipStream_t);
 
 template hipError_t launch_ragged_mid<float>(float *, int32_t *, int32_t *, int, const int32_t *, const int64_t *,
                                              const int32_t *, long long, unsigned long long *, hipStream_t, PathLog);

@@ -227,6 +227,18 @@ def solve_sweep(base_rate, base_next=None, base_hops=None, *, patches, items, de
 
     Returns a list with, per variant, the tuple (rate[, next[, hops]]) of arrays over its items (next with base_next,
     hops with base_hops); with count_updates (that list, the per-variant U as a uint64 array)."""
+    return _solve_sweep("fwx_solve_sweep", base_rate, base_next, base_hops, patches, items, device, count_updates)
+
+
+def solve_sweep_mid(base_rate, base_next=None, base_hops=None, *, patches, items, device=-1, count_updates=False):
+    """solve_sweep with the limit at n <= FWX_SWEEP_MID_MAX_N (fwx_solve_sweep_mid_f64 / _f32): orders from
+    FWX_BATCH_MID_MIN_N (environment, default 129) up are built and solved in workspace slots on the device, one per
+    workgroup, whatever the number of variants; smaller ones take solve_sweep's path.  Same arguments, same results,
+    same return value."""
+    return _solve_sweep("fwx_solve_sweep_mid", base_rate, base_next, base_hops, patches, items, device, count_updates)
+
+
+def _solve_sweep(stem, base_rate, base_next, base_hops, patches, items, device, count_updates):
     _check_arrays(base_rate, base_next, base_hops)
     if patches is None and items is None:
         raise ValueError("patches or items must say how many variants there are")
@@ -264,9 +276,9 @@ def solve_sweep(base_rate, base_next=None, base_hops=None, *, patches, items, de
     it.hops_out = out[2].ctypes.data if out[2] is not None else None
     o, _ = _opts(device, FWX_ENGINE_AUTO)
     each = np.zeros(count, dtype=np.uint64) if count_updates else None
-    fn = lib().fwx_solve_sweep_f64 if base_rate.dtype == np.float64 else lib().fwx_solve_sweep_f32
+    fn = getattr(lib(), stem + ("_f64" if base_rate.dtype == np.float64 else "_f32"))
     check(fn(count, n, _np_ptr(base_rate), _np_ptr(base_next), _np_ptr(base_hops), ctypes.byref(p), ctypes.byref(it),
-             _np_ptr(each), ctypes.byref(o)), "fwx_solve_sweep")
+             _np_ptr(each), ctypes.byref(o)), stem)
     res = [tuple(a[iptr[b]:iptr[b + 1]] for a in out if a is not None) for b in range(count)]
     return (res, each) if count_updates else res
 
@@ -281,6 +293,47 @@ def dev_solve_sweep(base_rate_t, count, n, *, base_next_t=None, base_hops_t=None
     hops_out]]) -- src / dst int32, the total is src's length; the outputs are written in place.  full: None or
     (rate, next, hops, stride) with any of the three None; variant b's solved n x n part goes to + b * stride.
     updates_t: device array of `count` 64-bit counters, counter b is incremented by U of variant b."""
+    _dev_solve_sweep("fwx_dev_solve_sweep", base_rate_t, count, n, base_next_t, base_hops_t, patches, items, full,
+                     updates_t, stream)
+
+
+def dev_solve_sweep_mid(base_rate_t, count, n, *, base_next_t=None, base_hops_t=None, patches=None, items=None,
+                        full=None, updates_t=None, scratch_t=None, stream=None):
+    """fwx_dev_solve_sweep_mid: dev_solve_sweep with the limit at n <= FWX_SWEEP_MID_MAX_N; routing by
+    FWX_BATCH_MID_MIN_N as solve_sweep_mid.  scratch_t: a device array of at least _lib.sweep_mid_scratch_bytes(n)
+    bytes, 16-byte aligned -- the call runs min(count, slots it holds, FWX_SWEEP_MID_SLOTS) workgroups, one slot each;
+    None: one for min(count, FWX_SWEEP_MID_SLOTS) slots is allocated here, and none where the order is forwarded to
+    dev_solve_sweep's tiers, which use no scratch.  Returns the scratch array (None where none was needed): it must
+    stay alive until the stream has run the call."""
+    if scratch_t is None and 0 < n <= _lib.FWX_SWEEP_MID_MAX_N and count > 0 and \
+            n >= lib().fwx_test_batch_mid_min_n():
+        per_slot = _lib.sweep_mid_scratch_bytes(n)
+        slots = lib().fwx_test_sweep_mid_slots(count, n, count * per_slot)
+        scratch_t = _empty_like_device(base_rate_t, (slots * per_slot,), "uint8")
+    _dev_solve_sweep("fwx_dev_solve_sweep_mid", base_rate_t, count, n, base_next_t, base_hops_t, patches, items, full,
+                     updates_t, stream, scratch_t if scratch_t is not None else _NO_SCRATCH)
+    return scratch_t
+
+
+class _NoScratch:
+    """scratch = NULL, scratch_bytes = 0, in the shape _dev_solve_sweep reads a device array."""
+
+    def data_ptr(self):
+        return None
+
+    def numel(self):
+        return 0
+
+    def element_size(self):
+        return 1
+
+
+_NO_SCRATCH = _NoScratch()
+
+
+def _dev_solve_sweep(name, base_rate_t, count, n, base_next_t, base_hops_t, patches, items, full, updates_t, stream,
+                     scratch_t=None):
+    """scratch_t None: the entry point takes no scratch arguments (fwx_dev_solve_sweep)."""
     def ptr_of(t):
         return None if t is None else t.data_ptr()
 
@@ -316,11 +369,12 @@ def dev_solve_sweep(base_rate_t, count, n, *, base_next_t=None, base_hops_t=None
         fu.rate, fu.next, fu.hops, fu.stride = ptr_of(full[0]), ptr_of(full[1]), ptr_of(full[2]), stride
     assert updates_t is None or (updates_t.element_size() == 8 and updates_t.numel() >= count)
     vp = ctypes.c_void_p
-    check(lib().fwx_dev_solve_sweep(
+    check(getattr(lib(), name)(
         count, n, _tensor_dtype_code(base_rate_t), vp(base_rate_t.data_ptr()), ptr_of(base_next_t), ptr_of(base_hops_t),
         ctypes.byref(p) if p is not None else None, ctypes.byref(it) if it is not None else None,
         ctypes.byref(fu) if fu is not None else None, vp(updates_t.data_ptr()) if updates_t is not None else None,
-        _stream_ptr(stream, base_rate_t)), "fwx_dev_solve_sweep")
+        *(() if scratch_t is None else (vp(scratch_t.data_ptr()), scratch_t.numel() * scratch_t.element_size())),
+        _stream_ptr(stream, base_rate_t)), name)
 
 
 # solve_batch_lists with cap=None: the first capacity tried, and the last (the lists of an input with arbitrage

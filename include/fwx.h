@@ -783,6 +783,60 @@ int fwx_solve_sweep_f32(int32_t count, int32_t n, const float *base_rate, const 
                         const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
                         uint64_t *updates_each, const fwx_opts *opts);
 
+/* ---- what-if sweeps up to order FWX_SWEEP_MID_MAX_N (256): variants built in per-workgroup slots -----------------
+ * The sweep above builds a variant in the registers and LDS of the two small batch tiers and stops at n = 128; the
+ * market of 20 exchanges x 12 currencies (240 vertices) needs the mid tier, whose matrix is resident in GLOBAL memory.
+ * Here a fixed number of workgroups (`slots`) is launched, each owning one workspace slot of n*n entries per field:
+ * a workgroup walks the variants b = s, s + slots, ... and per variant copies the base into its slot, applies the
+ * patches, runs the mid tier's solve on the slot, answers the items from it and goes on.  Device memory is slots x n*n
+ * entries per field whatever `count` is (materialised copies for fwx_dev_solve_batch_mid: count x n*n), the base stays
+ * in L2, and nothing but the queried entries comes back.
+ *
+ * The contract is that of fwx_dev_solve_sweep / fwx_solve_sweep_*, word for word, with the limit at
+ * FWX_SWEEP_MID_MAX_N: the same structs, the same clamping of the tables in the device form, the same table checks in
+ * the host form, the same statuses in the same order (FWX_ERR_UNSUPPORTED: n > FWX_SWEEP_MID_MAX_N; the entry points
+ * above keep refusing n > FWX_SWEEP_MAX_N), every output bit for bit what fwx_solve_batch_mid_* returns for M_b.
+ * Whole pivot range only, no path trace.  Routing by FWX_BATCH_MID_MIN_N as fwx_solve_batch_mid_*: orders below it are
+ * forwarded to fwx_dev_solve_sweep / the path of fwx_solve_sweep_* (scratch is ignored and may be NULL), orders from it
+ * up run the slots.  No result bit depends on the routing or on the number of slots.
+ *
+ * scratch (device form): device memory, 16-byte aligned, at least FWX_SWEEP_MID_SCRATCH_BYTES(n) -- one slot, an upper
+ * bound for every dtype and field set: the rates, then next, then hops, each n*n elements at pitch n.  The call
+ * launches slots = min(count, scratch_bytes / FWX_SWEEP_MID_SCRATCH_BYTES(n), FWX_SWEEP_MID_SLOTS) workgroups and
+ * touches nothing past slots x FWX_SWEEP_MID_SCRATCH_BYTES(n) bytes of it.  FWX_SWEEP_MID_SLOTS: environment, read
+ * once per call, digits only, >= 1, anything else means the default of 512 -- two 1024-thread workgroups on each of
+ * the 256 CUs, the most that can be resident (f64 + next + hops holds 133 KB of LDS and fits one per CU: 256 slots
+ * fill the chip there); more slots than can be resident queue, nothing waits on another workgroup.  Scratch that is
+ * NULL, misaligned or smaller than one slot is FWX_ERR_INVALID -- only where n is routed to the slots and count > 0 and
+ * n > 0; decided after the statuses above and before any device call.  The device form allocates nothing and
+ * synchronises nothing; the scratch must stay alive until the stream has run the call and may then hold anything.
+ * The host form takes its slots from the pooled per-call context, as many as fit under 256 MiB, capped by the rule
+ * above.
+ *
+ * When it pays (MI355X, f64 + next + hops, two patches and four items a variant; profiles/r35_sweep_mid.txt).  Host
+ * form against numpy building the copies, fwx_solve_batch_mid_f64 and indexing the answers: 13.6x at n = 256, count =
+ * 2048 (14.3 against 195.2 ms; 1.4 MB moved instead of 2 x 2.15 GB), 14.8x at n = 192, 13.9x at n = 129; 12.3 ... 13.5x
+ * at count = 256.  Device form against fwx_dev_solve_batch_mid on variants already materialised on the device: 1.06 ...
+ * 1.15x SLOWER (one more read and one more write of the matrix per variant), in a quarter of the device memory at
+ * count = 2048 and less with every further variant: it pays where the copies would have to be built, moved or held. */
+#define FWX_SWEEP_MID_MAX_N FWX_BATCH_MID_MAX_N
+#define FWX_SWEEP_MID_SCRATCH_BYTES(n) ((size_t)(n) * (n) * 16)
+int fwx_dev_solve_sweep_mid(int32_t count, int32_t n, int32_t dtype, const void *base_rate, const int32_t *base_next,
+                            const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                            const fwx_sweep_full *full, unsigned long long *d_updates_each, void *scratch,
+                            size_t scratch_bytes, void *stream);
+int fwx_solve_sweep_mid_f64(int32_t count, int32_t n, const double *base_rate, const int32_t *base_next,
+                            const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                            uint64_t *updates_each, const fwx_opts *opts);
+int fwx_solve_sweep_mid_f32(int32_t count, int32_t n, const float *base_rate, const int32_t *base_next,
+                            const int32_t *base_hops, const fwx_sweep_patches *patches, const fwx_sweep_items *items,
+                            uint64_t *updates_each, const fwx_opts *opts);
+/* TEST HOOK: the grid (= the slots) a fwx_dev_solve_sweep_mid call of `count` variants of order n with this much
+ * scratch would launch right now: min(count, scratch_bytes / FWX_SWEEP_MID_SCRATCH_BYTES(n), FWX_SWEEP_MID_SLOTS);
+ * 0 where count or n is 0; FWX_ERR_INVALID for a negative count or n, FWX_ERR_UNSUPPORTED for n >
+ * FWX_SWEEP_MID_MAX_N.  Needs no device.  Not for production use. */
+int fwx_test_sweep_mid_slots(int32_t count, int32_t n, size_t scratch_bytes);
+
 /* Index form of the `_path` list that optimum returns (Algorithms.hs:74-75): follow next-hops
  * from src until dst.  Returns the number of vertices written to out (dst included, src not), 0 if
  * next[src][dst] == -1 (empty path, "no exchange"), or a negative fwx_status.  Host arrays.      */
